@@ -11,6 +11,8 @@ input already resident in HBM:
 value = bases pushed through sketch+dist per second, summed over ranks (each rank
 owns an independent batch: weak scaling, no data-path collective).
 
+A plain run stages the batch, warms up, times --steps steps, writes --dump-outputs and prints
+the line.  The rest runs only with --full:
 Per-kernel times come from HIP events recorded by libfpmash on the launch stream;
 `roofline` is computed for the kernel with the largest share of the step.
 `cpu_baseline` times the oracle's CPU port (oracle/liboracle.so, the reference's
@@ -108,6 +110,17 @@ def parse():
     ap.add_argument("--n-seqs", type=int, default=10000)
     ap.add_argument("--seq-len", type=int, default=2000)
     ap.add_argument("--families", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed C2 steps also run everything else the bench measures "
+                         "or checks: the full-grid comparison, per-kernel event times and "
+                         "roofline, the oracle parity checks, the CPU baselines and the C3 / C4 "
+                         "/ C5 / split / CLI legs (each with its --no-* switch), and write the "
+                         "--detail file.  Without it: set-up, warm-up, the timed steps, "
+                         "--dump-outputs, the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step left in HBM as "
+                         "DIR/<name>.npy (float32 / float64; fixed seeded samples of the large "
+                         "arrays: see dump_outputs)")
     ap.add_argument("--k", type=int, default=21)
     ap.add_argument("--s", type=int, default=1000)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -154,7 +167,8 @@ def parse_args_for_test(**kw):
                            no_fp_text=True, no_c3=True, no_c4=True, c4_n=50_000,
                            no_parity=True, no_c5=True, c5_genomes=1000, no_cli=True,
                            no_split=True, split_bases=1_000_000_000, detail="",
-                           no_full_grid=True, pmc_dir=None, no_c4_shares=True)
+                           no_full_grid=True, pmc_dir=None, no_c4_shares=True, full=False,
+                           dump_outputs=None)
     for k_, v in kw.items():
         setattr(a, k_, v)
     return a
@@ -1506,6 +1520,53 @@ def split_leg(ctx, grp, ws, rank, local, length=1_000_000_000, s=10_000, k=21, s
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes less than this in all
+
+
+def dump_outputs(directory, job, outs, n, s):
+    """--dump-outputs: what the timed C2 step left in HBM, as <name>.npy files a second build's
+    run with the same arguments can be compared with array for array (the inputs are seeded).
+    The step's outputs are the sketch job's rows (u64 hashes, ascending, and their counts) and
+    the compact dist output `outs` (u16 numer / denom of every cell + the list of the cells
+    with numer > 0).  Everything is written as float32 / float64 holding exact integers: a u64
+    hash as its high and low 32 bits.  The large arrays are sampled by fixed seeded row picks
+    (sample_rows), sized to stay under DUMP_MAX_BYTES together:
+      sketch_counts [n]; sketch_rows [a] + sketch_hash_hi / sketch_hash_lo [a, s] (slots past
+      a row's count zeroed); grid_rows [b] + numer / denom [b, n]; listed_count [1];
+      listed_rows [c] + the listed cells of those query rows sorted by (query, reference):
+      listed_qry / listed_ref / listed_distance / listed_pvalue / listed_pass."""
+    os.makedirs(directory, exist_ok=True)
+    budget = DUMP_MAX_BYTES // 4                   # per group of arrays (3 groups + the small ones)
+    out = {}
+    rows_h, cnt_h = job.fetch()
+    out["sketch_counts"] = cnt_h.astype(np.float64)
+    pick = sample_rows(n, min(1000, max(1, budget // (16 * s))), salt=21)
+    sub = rows_h[pick].copy()
+    sub[np.arange(s)[None, :] >= cnt_h[pick][:, None]] = 0
+    out["sketch_rows"] = pick.astype(np.float64)
+    out["sketch_hash_hi"] = (sub >> np.uint64(32)).astype(np.float64)
+    out["sketch_hash_lo"] = (sub & np.uint64(0xFFFFFFFF)).astype(np.float64)
+    pick = sample_rows(n, min(200, max(1, budget // (8 * n))), salt=22)
+    out["grid_rows"] = pick.astype(np.float64)
+    out["numer"] = fetch_rows(outs[0], np.uint16, n, pick).astype(np.float32)
+    out["denom"] = fetch_rows(outs[1], np.uint16, n, pick).astype(np.float32)
+    out["listed_count"] = np.array([outs[2].count()], np.float64)
+    listed = outs[2].fetch()
+    pick = sample_rows(n, 2000, salt=23)
+    keep = np.isin(listed["qry"], pick.astype(np.uint32))
+    listed = {k: v[keep] for k, v in listed.items()}
+    order = np.lexsort((listed["ref"], listed["qry"]))[: budget // 40]
+    out["listed_rows"] = pick.astype(np.float64)
+    for k in ("qry", "ref", "distance", "pvalue", "pass"):
+        out["listed_" + k] = listed[k][order].astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total >= DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed {DUMP_MAX_BYTES}")
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return {"dir": directory, "arrays": len(out), "bytes": total}
+
+
 MAX_LINE_BYTES = 8192     # the driver parses one JSON line of about this size at most
 
 
@@ -1677,6 +1738,37 @@ def main():
     n_listed = cells.count()
     if n_listed > cells.cap:
         raise RuntimeError(f"C2 cell list overflow: {n_listed} cells > {cells.cap}")
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before anything else runs: the buffers hold the last timed step's results
+        dumped = dump_outputs(args.dump_outputs, job, (d_numer, d_denom, cells), n, args.s)
+    total_bases = grp.sum(n * args.seq_len) * args.steps
+    head = {
+        "metric": METRIC,
+        "value": total_bases / elapsed,
+        "unit": "bases/s",
+        "n_gpus": ws,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u64",
+        "data": "synthetic (family-structured lyn2vec-generate-shaped DNA, seeded per rank)",
+    }
+    if not args.full:
+        # a plain run ends here: the headline figure needs nothing else
+        if rank == 0:
+            head["config"] = {"n_seqs_per_gpu": n, "seq_len": args.seq_len, "k": args.k,
+                              "s": args.s, "pairs_per_gpu": n_pairs,
+                              "listed_pairs_per_gpu": n_listed, "full": False,
+                              "dumped_outputs": dumped}
+            print(json.dumps(compact_line(head)))
+        job.free()
+        grp.close()
+        ctx.close()
+        return
 
     # the same step with the full five-array output (fpm_dist_dev16: distance / p-value / pass
     # written for every cell, 21 B per pair), for comparison with rounds 1-3: not `value`
@@ -1730,8 +1822,6 @@ def main():
         c2par = c2_parity(job, seqs, (d_numer, d_denom, cells), args)
 
     bases_rank = n * args.seq_len
-    total_bases = grp.sum(bases_rank) * args.steps
-    value = total_bases / elapsed
 
     # roofline of the dominant kernel (algorithmic bytes per launch / avg launch time)
     s = args.s
@@ -1859,18 +1949,7 @@ def main():
 
     if rank == 0:
         detail = {
-            "metric": METRIC,
-            "value": value,
-            "unit": "bases/s",
-            "n_gpus": ws,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u64",
-            "data": "synthetic (family-structured lyn2vec-generate-shaped DNA, seeded per rank)",
+            **head,
             "config": {
                 "workload": (f"C2 step: sketch -i k={args.k} s={args.s} of {n} x {args.seq_len} bp "
                              f"+ all-vs-all dist of the {n} sketches ({n_pairs:.3g} pairs), per GPU; "
@@ -1882,6 +1961,7 @@ def main():
                 "pairs_per_gpu": n_pairs, "parallelism": f"independent batch per GPU x{ws}",
                 "listed_pairs_per_gpu": n_listed,
                 "full_grid_ms_per_step": full_ms,   # distance/p-value/pass written for every pair
+                "full": True, "dumped_outputs": dumped,
             },
             "kernel_timing_steps": n_timed,
             "sketch": {"bases_per_s": bases_step / (sk_ms * 1e-3) if sk_ms else None,

@@ -12,6 +12,8 @@ The reference's data fixtures copied alongside (DNA*-CFL.txt, *.msh, reads*.fast
 genomes.dist, test_sequence.*) are listed in tests/golden/README.md.
 
 Run:  make -C oracle && python tests/golden/make_golden.py
+      python tests/golden/make_golden.py --kseq    (kseq_records.json: kseq_read's results
+                                                    on the inputs of tests/test_kseq_oracle.py)
 """
 import json
 import os
@@ -168,7 +170,38 @@ def pvalue_asymp_table():
     return rows
 
 
+def kseq_table():
+    """kseq_read (the reference's kseq.h compiled into oracle/_ref, over gzopen) on the inputs
+    of tests/test_kseq_oracle.py, keyed by the SHA-256 of the file image: last return value,
+    record count, digest of the records, and for the edge cases the records themselves."""
+    import hashlib
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_kseq_oracle as T
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        cases = [(d, True) for d in T.FASTA_EDGE + T.FASTQ_EDGE] + \
+            [(d, False) for d in T.random_files()]
+        for i, (data, keep) in enumerate(cases):
+            p = os.path.join(tmp, f"{i}.fq")
+            with open(p, "wb") as f:
+                f.write(data)
+            recs, st = O.ref_kseq_records(p)
+            out[hashlib.sha256(data).hexdigest()] = T.record(recs, st, keep)
+    for name in T.FIXTURES:
+        p = os.path.join(HERE, name)
+        recs, st = O.ref_kseq_records(p)
+        out[hashlib.sha256(open(p, "rb").read()).hexdigest()] = T.record(recs, st, False)
+    return out
+
+
 def main():
+    if "--kseq" in sys.argv:
+        rows = kseq_table()
+        with open(os.path.join(HERE, "kseq_records.json"), "w") as f:
+            json.dump(rows, f, indent=0, sort_keys=True)
+        print({"kseq": len(rows)})
+        return
     if "--pvalue-asymp" in sys.argv:
         rows = pvalue_asymp_table()
         with open(os.path.join(HERE, "pvalue_asymp.json"), "w") as f:

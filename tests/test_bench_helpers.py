@@ -1,8 +1,10 @@
 """CPU tests of the bench's host-side helpers: the C++ CFL generator (C3 inputs), the -fp
-line grouping of the C3 leg, and the C4 leg's query-row sharding."""
+line grouping of the C3 leg, and the C4 leg's query-row sharding; one GPU test of a plain
+bench run's line and --dump-outputs files."""
 import os
 
 import numpy as np
+import pytest
 
 from conftest import GOLDEN
 import seqio
@@ -104,3 +106,70 @@ def test_headline_line_fits_driver_parser():
     # a pathological detail (huge strings) still yields a parseable line
     full["cpu_baseline"]["sample"] = "x" * 20000
     assert len(json.dumps(bench.compact_line(full))) < bench.MAX_LINE_BYTES
+
+
+def test_full_and_dump_outputs_are_off_by_default(monkeypatch):
+    """A plain run is the default: --full and --dump-outputs are options."""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_step_outputs(tmp_path, oracle):
+    """A plain `bench.py --dump-outputs DIR` run (a small batch whose sketches are shorter than
+    s): the line carries the headline fields and no leg, and the dumped arrays, float32 /
+    float64 under 64 MB in all, equal the oracle's sketches, shared-hash counts and listed
+    cells (distance and p-value within rtol 1e-12, the suite's tolerance for both)."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    shape = dict(n_seqs=300, seq_len=600, families=3)
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps",
+                        "2", "--warmup", "1", "--n-seqs", "300", "--seq-len", "600",
+                        "--families", "3", "--dump-outputs", str(out)],
+                       capture_output=True, timeout=120)
+    assert p.returncode == 0, p.stderr.decode()
+    line = json.loads(p.stdout.decode().strip().splitlines()[-1])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert line["unit"] == "bases/s" and line["higher_is_better"] is True
+    assert abs(line["value"] - 300 * 600 / (line["ms_per_step"] * 1e-3)) <= 1e-9 * line["value"]
+    assert line["legs"] == {} and line["cpu_baseline"] is None
+    assert line["parity"]["all_ok"] is None
+    d = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    assert sum(a.nbytes for a in d.values()) < 64 << 20
+
+    n, s, k = 300, 1000, 21
+    seqs = bench.make_batch(bench.parse_args_for_test(**shape), 0)
+    exp = oracle.sketch_batch(oracle.params(k=k, s=s), seqs)
+    assert max(len(e) for e in exp) < s
+    assert np.array_equal(d["sketch_counts"], [len(e) for e in exp])
+    rows = d["sketch_rows"].astype(np.int64)
+    assert np.array_equal(rows, np.arange(n))          # a batch this small is dumped whole
+    got = (d["sketch_hash_hi"].astype(np.uint64) << np.uint64(32)) | \
+        d["sketch_hash_lo"].astype(np.uint64)
+    for r in rows:
+        assert np.array_equal(got[r, :len(exp[r])], exp[r]) and not got[r, len(exp[r]):].any()
+
+    lengths = [600] * n
+    nu, de, di, pv = (x.reshape(n, n) for x in
+                      oracle.dist_grid(exp, lengths, exp, lengths, s, k, 4.0 ** k))
+    grid = d["grid_rows"].astype(np.int64)
+    assert len(grid) == 200 and len(set(grid)) == 200
+    assert np.array_equal(d["numer"], nu[grid]) and np.array_equal(d["denom"], de[grid])
+    assert np.array_equal(d["listed_rows"], np.arange(n))
+    q, r = np.nonzero(nu)                              # row-major: sorted by (query, reference)
+    assert d["listed_count"][0] == len(q) > n
+    assert np.array_equal(d["listed_qry"], q) and np.array_equal(d["listed_ref"], r)
+    assert np.allclose(d["listed_distance"], di[q, r], rtol=1e-12, atol=0)
+    assert np.allclose(d["listed_pvalue"], pv[q, r], rtol=1e-12, atol=0)
+    assert np.array_equal(d["listed_pass"], np.ones(len(q)))

@@ -9,7 +9,7 @@ timeout -k 10 300 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
   > gpurun_out/t_cli.log 2>&1 || { tail -20 gpurun_out/t_cli.log; exit 1; }
 tail -1 gpurun_out/t_cli.log
 for i in $(seq 1 "${1:-2}"); do
-  timeout -k 10 300 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fp-text --no-c3 \
+  timeout -k 10 300 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fp-text --no-c3 \
     --no-c4 --no-c5 --no-split > gpurun_out/cli_$i.json 2> gpurun_out/cli_$i.err \
     || { tail -20 gpurun_out/cli_$i.err; exit 1; }
   python3 -c "

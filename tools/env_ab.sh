@@ -19,7 +19,7 @@ print('$s', 'c5', round(d['ms_per_step'],3), {k: round(v['ms'],3) for k, v in d[
       continue
     fi
     if [ "${AB_LEG:-c2}" = c4 ]; then
-      env "${envs[@]}" timeout -k 10 300 python bench.py --steps 2 --warmup 1 --no-cpu-baseline \
+      env "${envs[@]}" timeout -k 10 300 python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline \
         --no-c3 --no-c5 --no-cli --no-cli-fp --no-gather-check --no-fp-text --no-split --no-parity --no-full-grid \
         --detail gpurun_out/env_$tag$i.detail.json > gpurun_out/env_$tag$i.json 2>&1 || exit 1
       python3 -c "
@@ -28,7 +28,7 @@ print('$s', 'c4', round(d['ms_per_step'],3), d['phase_ms_rank0'],
       {k[:14]: round(v['ms'], 3) for k, v in d['kernels_rank0'].items()})"
       continue
     fi
-    env "${envs[@]}" timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline \
+    env "${envs[@]}" timeout -k 10 300 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline \
       --no-c3 --no-c4 --no-c5 --no-cli --no-cli-fp --no-fp-text --no-split --no-parity --no-full-grid \
       --detail gpurun_out/env_$tag$i.detail.json > gpurun_out/env_$tag$i.json 2>&1 || exit 1
     python3 -c "

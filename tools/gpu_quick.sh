@@ -14,7 +14,7 @@ if [ -n "$K" ]; then
   tail -1 $O/tests.log
 fi
 if [ -n "$BA" ]; then
-  timeout -k 10 600 python bench.py $BA --detail $O/detail.json > $O/bench.json 2> $O/bench.err \
+  timeout -k 10 600 python bench.py --full $BA --detail $O/detail.json > $O/bench.json 2> $O/bench.err \
     || { tail -30 $O/bench.err; exit 1; }
   tail -c 1200 $O/bench.json
 fi

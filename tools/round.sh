@@ -18,7 +18,7 @@ STEPS=${*:-tests smoke pmc bench rocprof}
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 O=gpurun_out/$TAG; mkdir -p $O
-C2ONLY="--no-cpu-baseline --no-fp-text --no-c3 --no-c4 --no-c5 --no-cli --no-cli-fp --no-split --no-parity --no-full-grid --no-gather-check"
+C2ONLY="--full --no-cpu-baseline --no-fp-text --no-c3 --no-c4 --no-c5 --no-cli --no-cli-fp --no-split --no-parity --no-full-grid --no-gather-check"
 step() { echo "== $1 $(date +%T)"; }
 for s in $STEPS; do
   case $s in
@@ -46,7 +46,7 @@ for s in $STEPS; do
   bench)
     step bench
     pd=""; [ -f $O/pmc_traffic.json ] && pd="--pmc-dir $O"
-    timeout -k 10 600 python bench.py $pd ${BENCH_ARGS:-} --detail $O/bench_detail.json \
+    timeout -k 10 600 python bench.py --full $pd ${BENCH_ARGS:-} --detail $O/bench_detail.json \
       > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
     tail -c 3000 $O/bench.json ;;
   rocprof)

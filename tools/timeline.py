@@ -2,7 +2,7 @@
 """tools/timeline.py — per-step kernel timeline of bench.py from a rocprofv3 kernel trace.
 
     rocprofv3 --kernel-trace --output-format csv -d gpurun_out/tl -o tl -- \\
-        python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-c3 --no-c4
+        python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-c3 --no-c4
     python3 tools/timeline.py gpurun_out/tl          # (any directory holding *kernel_trace.csv)
 
 Steps are cut at each sketch_tiles launch; for one step (the median by span) prints every
