@@ -481,7 +481,7 @@ __global__ __launch_bounds__(64 * kRankWaves) void rank_rows_kernel(
     if (uns) s_unsorted = 1;
     __syncthreads();
     // a row that is not strictly ascending (a rank kernel enqueued before the probe's
-    // sortedness flag was read, fpm_api.cpp; its results are then dropped): nothing to rank,
+    // sortedness flag was read, fpm_dist_api.cpp; its results are then dropped): nothing to rank,
     // and its directory would not bound the bucket loop below
     if (s_unsorted) return;
     // the largest bucket: element j is the (j - Bkt[bucket(j)] + 1)-th of its bucket

@@ -855,7 +855,7 @@ void probe_rows_kernel(
     if (threadIdx.x == 0) {
         row_base = tot ? atomicAdd(n_cand, (unsigned long long)tot) : 0ULL;
         // past the candidate buffer (a call enqueued before its posting events were known,
-        // fpm_api.cpp's speculated probe): nothing written, the row flagged and left empty
+        // fpm_dist_api.cpp's speculated probe): nothing written, the row flagged and left empty
         const bool over = row_base + tot > cap;
         if (over) atomicOr(cand_over, 1u);
         // (offset << 24 | count) of this row's candidates; one ref chunk per row here

@@ -15,21 +15,15 @@
 // so processes that never build a communicator (the CLI) do not pay for mapping it.  The
 // unique id travels over the caller's host channel (fpm_comm_unique_id on one rank, then any
 // broadcast of its 128 bytes), as ncclGetUniqueId's contract asks.
-#include "../../include/fpmash.h"
+#include "fpm_internal.hpp"
 
-#include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
 #include <dlfcn.h>
 
 #include <chrono>
-#include <condition_variable>
 #include <cstdlib>
-#include <cstring>
 #include <memory>
-#include <mutex>
-#include <string>
-#include <thread>
 
 namespace {
 
@@ -76,19 +70,10 @@ Rccl &rccl()
     return r;
 }
 
-}  // namespace
-
-// fpm_api.cpp: the message fpm_last_error() returns (one error text for the whole ABI)
-int fpm_detail_fail(int code, const std::string &msg);
-
-namespace {
-
-int cfail(int code, const std::string &m) { return fpm_detail_fail(code, m); }
-
 int rccl_fail(const char *what, ncclResult_t rc)
 {
     const Rccl &r = rccl();
-    return cfail(FPM_EHIP, std::string(what) + ": " +
+    return fail(FPM_EHIP, std::string(what) + ": " +
                                (r.error_string ? r.error_string(rc) : "rccl error"));
 }
 
@@ -122,9 +107,9 @@ extern "C" {
 
 int fpm_comm_unique_id(uint8_t id[FPM_COMM_ID_BYTES])
 {
-    if (!id) return cfail(FPM_EINVAL, "null id");
+    if (!id) return fail(FPM_EINVAL, "null id");
     Rccl &r = rccl();
-    if (!r.why.empty()) return cfail(FPM_ENODEV, r.why);
+    if (!r.why.empty()) return fail(FPM_ENODEV, r.why);
     ncclUniqueId u;
     if (ncclResult_t rc = r.get_unique_id(&u)) return rccl_fail("ncclGetUniqueId", rc);
     static_assert(sizeof(u) == FPM_COMM_ID_BYTES, "RCCL unique id size");
@@ -136,18 +121,18 @@ int fpm_comm_create(fpm_ctx *ctx, int nranks, int rank, const uint8_t id[FPM_COM
                     fpm_comm **out)
 {
     if (!ctx || !id || !out || nranks < 1 || rank < 0 || rank >= nranks)
-        return cfail(FPM_EINVAL, "comm_create: bad argument");
+        return fail(FPM_EINVAL, "comm_create: bad argument");
     *out = nullptr;
     Rccl &r = rccl();
-    if (!r.why.empty()) return cfail(FPM_ENODEV, r.why);
+    if (!r.why.empty()) return fail(FPM_ENODEV, r.why);
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return cfail(FPM_EHIP, "hipGetDevice");
+    if (hipGetDevice(&dev) != hipSuccess) return fail(FPM_EHIP, "hipGetDevice");
     // the communicator binds to the current device: the context's (fpm_ctx_stream's device)
     hipStream_t st = (hipStream_t)fpm_ctx_stream(ctx);
     int sdev = dev;
     if (hipStreamGetDevice(st, &sdev) == hipSuccess && sdev != dev &&
         hipSetDevice(sdev) != hipSuccess)
-        return cfail(FPM_EHIP, "hipSetDevice");
+        return fail(FPM_EHIP, "hipSetDevice");
     ncclUniqueId u;
     memcpy(&u, id, sizeof(u));
     fpm_comm *c = new fpm_comm();
@@ -183,7 +168,7 @@ int fpm_comm_create(fpm_ctx *ctx, int nranks, int rank, const uint8_t id[FPM_COM
         if (!su->cv.wait_for(lk, std::chrono::duration<double>(limit), [&] { return su->done; })) {
             su->abandoned = true;
             delete c;
-            return cfail(FPM_EHIP, "ncclCommInitRank: not every rank joined within " +
+            return fail(FPM_EHIP, "ncclCommInitRank: not every rank joined within " +
                                        std::to_string((int)limit) + " s (FPM_COMM_INIT_TIMEOUT_S)");
         }
         if (su->rc != ncclSuccess) {
@@ -208,9 +193,9 @@ void fpm_comm_destroy(fpm_comm *c)
 
 int fpm_comm_all_gather(fpm_comm *c, const void *d_send, void *d_recv, size_t bytes, void *stream)
 {
-    if (!c || (bytes && (!d_send || !d_recv))) return cfail(FPM_EINVAL, "all_gather: bad argument");
+    if (!c || (bytes && (!d_send || !d_recv))) return fail(FPM_EINVAL, "all_gather: bad argument");
     if (!bytes) return FPM_OK;
-    if (hipSetDevice(c->device) != hipSuccess) return cfail(FPM_EHIP, "hipSetDevice");
+    if (hipSetDevice(c->device) != hipSuccess) return fail(FPM_EHIP, "hipSetDevice");
     hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)fpm_ctx_stream(c->ctx);
     if (ncclResult_t rc = rccl().all_gather(d_send, d_recv, bytes, ncclUint8, c->comm, st))
         return rccl_fail("ncclAllGather", rc);
@@ -221,18 +206,18 @@ int fpm_sketch_min_merge_comm(fpm_comm *c, const uint64_t *d_row, const uint32_t
                               uint32_t s, uint64_t *d_out, uint32_t *d_out_count, void *stream)
 {
     if (!c || !d_row || !d_count || !d_out || !d_out_count || s == 0)
-        return cfail(FPM_EINVAL, "min_merge_comm: bad argument");
-    if (hipSetDevice(c->device) != hipSuccess) return cfail(FPM_EHIP, "hipSetDevice");
+        return fail(FPM_EINVAL, "min_merge_comm: bad argument");
+    if (hipSetDevice(c->device) != hipSuccess) return fail(FPM_EHIP, "hipSetDevice");
     hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)fpm_ctx_stream(c->ctx);
     const size_t rb = (size_t)c->nranks * s * 8, cb = (size_t)c->nranks * 4;
     auto grow = [&](void **p, size_t *have, size_t want) -> int {
         if (*have >= want) return FPM_OK;
         // the previous gather into it may still be queued
         if (*p && (hipStreamSynchronize(st) != hipSuccess || hipFree(*p) != hipSuccess))
-            return cfail(FPM_EHIP, "min_merge_comm: buffer release");
+            return fail(FPM_EHIP, "min_merge_comm: buffer release");
         *p = nullptr;
         *have = 0;
-        if (hipMalloc(p, want) != hipSuccess) return cfail(FPM_ENOMEM, "min_merge_comm: hipMalloc");
+        if (hipMalloc(p, want) != hipSuccess) return fail(FPM_ENOMEM, "min_merge_comm: hipMalloc");
         *have = want;
         return FPM_OK;
     };
@@ -248,7 +233,7 @@ int fpm_sketch_min_merge_comm(fpm_comm *c, const uint64_t *d_row, const uint32_t
     const int rc = fpm_sketch_merge_dev(c->ctx, (const uint64_t *)c->rows,
                                         (const uint32_t *)c->counts, (uint32_t)c->nranks, s,
                                         d_out, d_out_count, st);
-    if (rc) return cfail(rc, std::string("min_merge_comm: ") + fpm_last_error());
+    if (rc) return fail(rc, std::string("min_merge_comm: ") + fpm_last_error());
     return FPM_OK;
 }
 

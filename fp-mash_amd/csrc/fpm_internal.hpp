@@ -1,0 +1,293 @@
+// fpm_internal.hpp — what the files implementing the C ABI of include/fpmash.h share:
+// the context, its pool / ring / copy helpers, the device scratch slots and the counter block.
+// fpm_ctx.cpp defines the helpers; fpm_sketch_api.cpp, fpm_text_api.cpp, fpm_dist_api.cpp and
+// fpm_comm.cpp use them.  Nothing declared here is exported from the library.
+#pragma once
+
+#include "fpm_kernels.hpp"
+#include "../../include/fpmash.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <condition_variable>
+#include <cstdint>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <system_error>
+#include <thread>
+#include <vector>
+
+using namespace fpm;
+
+#define FPM_HIDDEN __attribute__((visibility("hidden")))
+
+// sets the text fpm_last_error() returns (one error text for the whole ABI); returns `code`
+FPM_HIDDEN int fail(int code, const std::string &msg);
+
+#define HIP_TRY(expr)                                                                      \
+    do {                                                                                   \
+        hipError_t e_ = (expr);                                                            \
+        if (e_ != hipSuccess)                                                              \
+            return fail(FPM_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
+    } while (0)
+
+// Host memcpy split over a few persistent threads: the pinned ring's copies of pageable caller
+// memory ran at one thread's ~8 GB/s, below the DMA behind them (C3's 301 MB of -fp text:
+// ~40 ms of the parse wall).  Parts of >= 1 MB; the caller copies the first part itself.
+class CopyPool {
+  public:
+    ~CopyPool()
+    {
+        {
+            std::lock_guard<std::mutex> g(mu_);
+            stop_ = true;
+        }
+        cv_.notify_all();
+        for (auto &t : th_) t.join();
+    }
+    void copy(void *dst, const void *src, size_t n)
+    {
+        constexpr size_t kPart = size_t(1) << 20;
+        const unsigned want = (unsigned)std::min<size_t>(kMaxThreads + 1, n / kPart);
+        if (want <= 1) { memcpy(dst, src, n); return; }
+        std::unique_lock<std::mutex> lk(mu_);
+        while (th_.size() + 1 < want && th_.size() < threads()) {
+            // (at the process's thread limit: fewer parts, never an exception through the C ABI)
+            try {
+                th_.emplace_back([this] { work(); });
+            } catch (const std::system_error &) {
+                break;
+            }
+        }
+        const unsigned parts = (unsigned)std::min<size_t>(want, th_.size() + 1);
+        const size_t per = (n + parts - 1) / parts;
+        char *d = static_cast<char *>(dst);
+        const char *sp = static_cast<const char *>(src);
+        for (unsigned i = 1; i < parts; i++) {
+            const size_t a = i * per, b = std::min(n, a + per);
+            if (a < b) { q_.push_back({d + a, sp + a, b - a}); pending_++; }
+        }
+        lk.unlock();
+        cv_.notify_all();
+        memcpy(d, sp, std::min(n, per));
+        lk.lock();
+        done_.wait(lk, [this] { return pending_ == 0; });
+    }
+
+  private:
+    static constexpr unsigned kMaxThreads = 7;
+    static unsigned threads()
+    {
+        const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+        return std::min(kMaxThreads, std::max(1u, hw / 2));
+    }
+    struct Task { char *d; const char *s; size_t n; };
+    void work()
+    {
+        std::unique_lock<std::mutex> lk(mu_);
+        for (;;) {
+            cv_.wait(lk, [this] { return stop_ || !q_.empty(); });
+            if (q_.empty()) return;
+            const Task t = q_.back();
+            q_.pop_back();
+            lk.unlock();
+            memcpy(t.d, t.s, t.n);
+            lk.lock();
+            if (--pending_ == 0) done_.notify_all();
+        }
+    }
+    std::mutex mu_;
+    std::condition_variable cv_, done_;
+    std::vector<std::thread> th_;
+    std::vector<Task> q_;
+    size_t pending_ = 0;
+    bool stop_ = false;
+};
+
+// The context's grow-only device scratch buffers, by what they hold.  A slot belongs to one
+// call at a time: calls on a context are stream-ordered, and growing a buffer goes through
+// hipFree, which waits for the device.  Slots named twice below are claimed from two places
+// of one dist call on purpose: the speculated launch (probe, rank kernel) and the regular one
+// ask for the same candidates / row segments / results, and only one of the two runs, or the
+// second reuses what the first wrote; the query-side record rows are built by whichever index
+// source the call takes (resident-recorded or transient), never both.
+enum ScratchSlot : int {
+    kSlotTileHist = 0,     // index build: level-1 histograms per tile
+    kSlotTileOff = 1,      // index build: their scan
+    kSlotTent = 2,         // index build: level-1 staging entries
+    kSlotCandRes = 3,      // rank kernel: per-candidate numer | denom (shared, see above)
+    kSlotDir = 4,          // bucket directory
+    kSlotEntries = 5,      // bucket entries
+    kSlotScan = 6,         // index build: scan scratch
+    kSlotCounters = 7,     // the counter block (CtrWord)
+    kSlotCand = 8,         // the probe's candidates (shared)
+    kSlotRowSeg = 9,       // their per-query-row segments (shared)
+    kSlotRecRef = 10,      // record rows of the references
+    kSlotRecRefLen = 11,   // their lengths
+    kSlotRecQry = 12,      // record rows of the queries (shared)
+    kSlotRecQryLen = 13,   // their lengths (shared)
+    kSlotImgBlocks = 14,   // dense image compare: union blocks
+    kSlotImg = 15,         // dense image compare: bit images
+    kSlotPartFill = 16,    // index build: one-pass partition fill counts
+    kSlotMergeRows = 16,   // fpm_sketch_merge_dev: intermediate lists (no index build beside it)
+    kSlotMergeCounts = 17, // fpm_sketch_merge_dev: their counts
+    kSlotMergeDescs = 18,  // fpm_sketch_merge_dev: merge descriptors
+    kSlotRecRefPos = 19,   // record positions of the references
+    kSlotRecQryPos = 20,   // record positions of the queries (shared)
+    kSlotCount
+};
+
+// The dist counter block (kSlotCounters), in u64 words.  The flags are the low u32 of their word.
+enum CtrWord : uint32_t {
+    kCtrEvents = 0,        // posting events
+    kCtrPartials = 1,      // ..64: per-block partial events
+    kCtrCand = 65,         // candidates the probe appended
+    kCtrUnsorted = 66,     // flag: some row is unsorted / carries duplicates
+    kCtrOverflow = 67,     // flag: a one-pass index build overflowed a partition slot
+    kCtrKmax = 68,         // the largest indexed key (the bucket scale)
+    kCtrCandOver = 69,     // flag: a probe ran past its candidate buffer (only a speculated one can)
+    kCtrKmaxAcc = 72,      // ..73: idx_kmax_kernel's accumulator, kept at zero between calls
+    kCtrWords = 80,
+    kCtrProbeWords = kCtrOverflow,   // [0, 67): cleared before, and read after, a probe count
+    kCtrBuildWords = kCtrKmax,       // [0, 68): published after an index build
+    kCtrZeroWords = kCtrKmaxAcc      // [0, 72): cleared by the index build's first kernel
+};
+
+struct fpm_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool timing = false;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[FPM_K_COUNT];
+    // grow-only device scratch, one buffer per named slot (no allocation in steady state)
+    struct Slot { void *p = nullptr; size_t bytes = 0; };
+    Slot scratch[kSlotCount];
+    unsigned long long *host_counters = nullptr;   // pinned + mapped, for the events read-back
+    unsigned long long *dev_counters = nullptr;    // its device-side address
+    unsigned long long pub_seq = 0;                // last sequence number published into it
+    int dist_mode = FPM_DIST_AUTO;
+    int fill_counts = -1;      // the side-stream fill also writes the numer / denom defaults
+                               // (-1: for grids of >= 2^28 pairs; FPM_FILL_COUNTS=0/1 forces)
+    int last_sparse = 0;
+    uint64_t last_events = 0, last_cand = 0;
+    const unsigned long long *last_cand_dev = nullptr;   // the last sparse call's counter
+    hipStream_t last_cand_stream = nullptr;
+    // side stream for the sparse dist's fill (a pure write stream that runs beside the
+    // latency-bound candidate compare); ev_in / ev_fill order it against `stream`
+    hipStream_t aux = nullptr;
+    hipEvent_t ev_in = nullptr, ev_fill = nullptr;
+    // a compact grid's counts written ahead on `aux` (fpm_dist_list_prefill), until the dist
+    // call on that grid takes it over (or any other dist call waits for it): ev_prefill
+    struct Prefill {
+        const void *numer = nullptr, *denom = nullptr;
+        uint32_t n_ref = 0, n_qry = 0, S = 0;
+        bool pending = false;
+    } prefill;
+    hipEvent_t ev_prefill = nullptr;
+    // pinned staging ring for host -> device copies of pageable caller memory
+    static constexpr int kRing = 4;
+    static constexpr size_t kRingBytes = 8u << 20;
+    void *ring[kRing] = {};
+    hipEvent_t ring_ev[kRing] = {};
+    CopyPool copier;                       // the ring's host-side copies
+    // device buffers of released -fp text jobs, reused by the next jobs: a fresh hipMalloc of
+    // tens of MB is cleared by the driver before first use, and a kernel writing it could wait
+    // ~27 ms for that (tools/micro/fp_text_time.py under rocprofv3: fp_line_kernel 0.06 ms,
+    // now and then 27 ms)
+    static constexpr size_t kPoolBytes = size_t(2) << 30;
+    uint64_t idx_rebuilds = 0;             // one-pass index builds that overflowed a slot
+    // The last sparse rank-kernel call's shape and candidate capacity: a call of the same
+    // shape enqueues its probe right behind the index build, before the host reads the
+    // build's counters (compare_impl), and checks afterwards that the path and the capacity
+    // held; otherwise the probe's output is dropped and the call proceeds as without it.
+    struct SpecProfile {
+        bool valid = false;
+        uint32_t n_ref = 0, n_qry = 0, S = 0;
+        uint64_t ref_stride = 0, qry_stride = 0, cap = 0;
+        bool self_set = false, defaults = false;
+    } spec;
+    uint64_t spec_hits = 0, spec_misses = 0;
+    std::vector<std::pair<void *, size_t>> pool;
+    size_t pool_bytes = 0;
+    std::mutex pool_mu;
+};
+
+// RAII-free event bracket: records start before and stop after a launch.
+struct TimedLaunch {
+    fpm_ctx *ctx; int kid; hipStream_t st; hipEvent_t a = nullptr, b = nullptr;
+    TimedLaunch(fpm_ctx *c, int k, hipStream_t s) : ctx(c), kid(k), st(s)
+    {
+        if (ctx->timing) {
+            (void)hipEventCreate(&a);
+            (void)hipEventCreate(&b);
+            (void)hipEventRecord(a, st);
+        }
+    }
+    void done()
+    {
+        if (ctx->timing) {
+            (void)hipEventRecord(b, st);
+            ctx->ev[kid].push_back({a, b});
+        }
+    }
+};
+
+#pragma GCC visibility push(hidden)
+
+int set_device(fpm_ctx *ctx);
+inline hipStream_t pick_stream(fpm_ctx *ctx, void *stream)
+{
+    return stream ? (hipStream_t)stream : ctx->stream;
+}
+
+// device buffers of released jobs, reused by the next (fpm_ctx::pool)
+hipError_t pool_alloc(fpm_ctx *ctx, void **p, size_t bytes);
+void pool_free(fpm_ctx *ctx, void *p, size_t bytes);
+
+// copies on the context stream, pageable caller memory through the pinned ring
+hipError_t ensure_ring(fpm_ctx *ctx);
+hipError_t memset_sync(fpm_ctx *ctx, void *dst, int v, size_t bytes);
+hipError_t h2d_staged(fpm_ctx *ctx, void *dst, const void *src, size_t bytes);
+hipError_t d2h_staged(fpm_ctx *ctx, void *dst, const void *src, size_t bytes);
+hipError_t copy_out(fpm_ctx *ctx, void *dst, const void *src, size_t bytes);
+hipError_t copy_in(fpm_ctx *ctx, void *dst, const void *src, size_t bytes);
+hipError_t ensure_aux(fpm_ctx *ctx);
+
+// grow-only device buffers: a slot of at least `bytes`; scratch() is the context's named slot
+hipError_t grow_slot(fpm_ctx::Slot &s, size_t bytes, void **out);
+hipError_t scratch(fpm_ctx *ctx, ScratchSlot id, size_t bytes, void **out);
+
+// device counters -> the context's host-mapped block (fpm_ctx.cpp)
+int publish_counters(fpm_ctx *ctx, const unsigned long long *d_src, uint32_t n, hipStream_t st,
+                     unsigned long long *seq_out);
+int wait_counters(fpm_ctx *ctx, unsigned long long seq, hipStream_t st);
+int read_counters(fpm_ctx *ctx, const unsigned long long *d_src, uint32_t n, hipStream_t st);
+
+// the host copy of the counter block, after read_counters / wait_counters
+inline uint64_t host_events(const fpm_ctx *ctx) { return ctx->host_counters[kCtrEvents]; }
+inline bool host_flag(const fpm_ctx *ctx, CtrWord w)
+{
+    return ((const uint32_t *)(ctx->host_counters + w))[0] != 0;
+}
+inline bool host_unsorted(const fpm_ctx *ctx) { return host_flag(ctx, kCtrUnsorted); }
+inline bool host_overflow(const fpm_ctx *ctx) { return host_flag(ctx, kCtrOverflow); }
+
+#pragma GCC visibility pop
+
+// Records to sketch, in the order their groups stream them: `rec_len(r)` bytes at `rec_pos(r)`
+// of the device sequence buffer.  Host path: fpm_sketch_stage packs the records itself
+// (host_packed); device path: fpm_sketch_stage_seq adopts the buffer seqparse.hip packed.
+struct StageRecords {
+    std::vector<uint32_t> order;        // records in group order (records of no group left out)
+    std::vector<uint64_t> pos, len;     // per record (indexed by record id)
+    std::vector<uint32_t> group;        // per record
+    uint32_t n_groups = 0;
+    const char *host_seq = nullptr;     // host path: record r is host_seq[pos..pos+len)
+    uint8_t *d_seq = nullptr;           // device path: packed buffer (ownership moves to the job)
+    uint64_t d_seq_bytes = 0;
+};
+
+// fpm_sketch_api.cpp: the staging behind fpm_sketch_stage and fpm_sketch_stage_seq
+FPM_HIDDEN int stage_core(fpm_ctx *ctx, const fpm_sketch_params *p, StageRecords &R,
+                          fpm_sketch_job **job_out);

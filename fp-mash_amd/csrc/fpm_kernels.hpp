@@ -1,4 +1,4 @@
-// fpm_kernels.hpp — launch interface between the C-ABI (fpm_api.cpp) and the
+// fpm_kernels.hpp — launch interface between the C-ABI (fpm_*_api.cpp) and the
 // gfx950 kernels (sketch.hip, dist.hip, fingerprint.hip).  Host-only types.
 #pragma once
 

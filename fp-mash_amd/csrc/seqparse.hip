@@ -25,7 +25,7 @@
 // kept: such summaries compose associatively, so a whole file is parsed with two passes of
 // block scans and one chunk-level scan (no sequential dependence between workgroups).
 //
-// Text layout (set up by the caller, fpm_api.cpp): each file starts on a kSpChunk boundary
+// Text layout (set up by the caller, fpm_text_api.cpp): each file starts on a kSpChunk boundary
 // (its first chunk resets the state to S0), the gap after it and the tail of the buffer are
 // '\n' bytes (so every header line ends with a '\n' inside the buffer).
 #include "fpm_device.hpp"

@@ -378,7 +378,7 @@ __device__ __forceinline__ uint32_t tile_hash(const TileDesc &td, const SketchKP
 // and no shared area sent 2.7 % of C5's tiles to the redo pass.)
 constexpr int kSurv = 2;
 constexpr int kSurvShared = 512;
-static_assert(kBlock * kSurv + kSurvShared == (int)kThrTileKeys, "fpm_api.cpp sizes thr4 by it");
+static_assert(kBlock * kSurv + kSurvShared == (int)kThrTileKeys, "fpm_sketch_api.cpp sizes thr4 by it");
 // One tile: the body of sketch_tiles_kernel (one workgroup per tile) and of
 // sketch_redo_kernel (the tiles a THR pass listed, taken in turn by a fixed grid).
 template <int P, int K, bool THR>
