@@ -286,6 +286,8 @@ struct StageRecords {
     const char *host_seq = nullptr;     // host path: record r is host_seq[pos..pos+len)
     uint8_t *d_seq = nullptr;           // device path: packed buffer (ownership moves to the job)
     uint64_t d_seq_bytes = 0;
+    bool borrow = false;                // device path: d_seq stays with its owner (reads mode's
+                                        // wide jobs over the staged job's buffer)
 };
 
 // fpm_sketch_api.cpp: the staging behind fpm_sketch_stage and fpm_sketch_stage_seq

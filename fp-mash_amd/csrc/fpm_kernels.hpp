@@ -74,6 +74,25 @@ hipError_t launch_sketch_mult(int cls, int pass, const uint8_t *d_seq, const Til
                               unsigned long long *d_first, const uint64_t *d_ttop, hipStream_t st);
 hipError_t launch_mult_ttop(const uint32_t *d_count, uint32_t n_groups, uint32_t s,
                             const unsigned long long *d_first, uint64_t *d_ttop, hipStream_t st);
+// reads mode (min-copies m): counts and the m smallest positions (d_slots: m u64 per entry,
+// all-ones before) of the entries of the wide rows d_rows (stride p.s); then per group not
+// yet done the first s entries with count >= m into the output row (d_done[g] = round when
+// that is final); then the count of a full sketch's maximum up to T (d_ttop)
+hipError_t launch_reads_count(int cls, const uint8_t *d_seq, const TileDesc *d_tiles,
+                              uint32_t n_tiles, const SketchKParams &p, const uint64_t *d_rows,
+                              const uint32_t *d_count, uint32_t m, uint32_t *d_wcnt,
+                              unsigned long long *d_slots, hipStream_t st);
+hipError_t launch_reads_filter(const uint64_t *d_rows, const uint32_t *d_count, uint32_t wide,
+                               uint32_t n_groups, const uint32_t *d_wcnt,
+                               const unsigned long long *d_slots, uint32_t m, uint32_t s,
+                               uint32_t round, uint32_t *d_done, uint64_t *d_out_rows,
+                               uint32_t *d_out_count, uint32_t *d_out_mult, uint64_t *d_ttop,
+                               hipStream_t st);
+hipError_t launch_reads_maxcount(int cls, const uint8_t *d_seq, const TileDesc *d_tiles,
+                                 uint32_t n_tiles, const SketchKParams &p, uint32_t s,
+                                 uint32_t round, const uint32_t *d_done, const uint64_t *d_out_rows,
+                                 const uint32_t *d_out_count, uint32_t *d_out_mult,
+                                 const uint64_t *d_ttop, hipStream_t st);
 // thr_safe[i] = s-th smallest of sample row srow[i] when it holds s hashes, else no bound;
 // thr[i] = its kt[i]-th smallest (d_kt null: thr = thr_safe)
 hipError_t launch_sketch_threshold(const uint32_t *d_srow, uint32_t n_slots, const uint64_t *d_rows,

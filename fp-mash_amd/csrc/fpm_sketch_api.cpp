@@ -118,12 +118,29 @@ struct fpm_sketch_job {
     uint32_t *d_mult = nullptr;
     unsigned long long *d_first = nullptr;
     uint64_t *d_ttop = nullptr;
+    // reads mode (fpm_sketch_job_set_min_copies, fpm_sketch_reads_run): the parameters and
+    // records as staged (pos = offsets in d_seq), from which the widening rounds stage their
+    // wide jobs over this job's d_seq (borrowed_seq: such a job does not free it); the
+    // filtered rows, counts and T, allocated on first use
+    fpm_sketch_params params{};
+    StageRecords recs;
+    bool borrowed_seq = false;
+    uint32_t min_copies = 1;
+    uint64_t *d_rrows = nullptr, *d_rttop = nullptr;
+    uint32_t *d_rcount = nullptr, *d_rmult = nullptr, *d_rdone = nullptr;
+    std::vector<uint32_t> h_rdone;          // per group: the round that completed it
+    int32_t reads_rounds = -1;              // rounds of the last reads run (-1: none yet)
+    int32_t reads_sampled = -1;             // long groups its last round's wide job sampled
 };
 
 static void job_release(fpm_sketch_job *j)
 {
     if (!j) return;
     (void)hipSetDevice(j->ctx->device);
+    if (j->borrowed_seq) j->d_seq = nullptr;
+    for (void *p : {(void *)j->d_rrows, (void *)j->d_rttop, (void *)j->d_rcount,
+                    (void *)j->d_rmult, (void *)j->d_rdone})
+        (void)hipFree(p);
     for (void *p : {(void *)j->d_seq, (void *)j->d_tiles, (void *)j->d_rows, (void *)j->d_count,
                     (void *)j->d_merge, (void *)j->d_stiles, (void *)j->d_smerge, (void *)j->d_srow,
                     (void *)j->d_thr, (void *)j->d_redo, (void *)j->d_redo_n, (void *)j->d_kt,
@@ -526,6 +543,7 @@ int stage_core(fpm_ctx *ctx, const fpm_sketch_params *p, StageRecords &R,
         if (e == hipSuccess) e = hipMalloc(ptr, bytes ? bytes : 16);
     };
     if (R.host_seq) alloc((void **)&job->d_seq, packed.size() + 64);
+    else if (R.borrow) { job->d_seq = R.d_seq; job->borrowed_seq = true; }
     else { job->d_seq = R.d_seq; R.d_seq = nullptr; }   // the parse's packed records
     alloc((void **)&job->d_tiles, by_class.size() * sizeof(TileDesc));
     alloc((void **)&job->d_rows, (size_t)n_core * s * sizeof(uint64_t));
@@ -647,6 +665,13 @@ int stage_core(fpm_ctx *ctx, const fpm_sketch_params *p, StageRecords &R,
         delete job;
         return fail(FPM_EHIP, std::string("sketch staging copy: ") + hipGetErrorString(e));
     }
+    // kept for reads mode's widening rounds (moved, not copied: the callers are done with them)
+    job->params = *p;
+    job->recs.n_groups = n_groups;
+    job->recs.order = std::move(R.order);
+    job->recs.pos = std::move(R.pos);
+    job->recs.len = std::move(R.len);
+    job->recs.group = std::move(R.group);
     *job_out = job;
     return FPM_OK;
 }
@@ -996,6 +1021,201 @@ int fpm_sketch_job_redo_tiles(fpm_sketch_job *job, int32_t *n_redo)
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(&v, job->d_redo_n, sizeof v, hipMemcpyDeviceToHost));
     *n_redo = (int32_t)v;
+    return FPM_OK;
+}
+
+int fpm_sketch_job_set_min_copies(fpm_sketch_job *job, uint32_t min_copies)
+{
+    if (!job) return fail(FPM_EINVAL, "null job");
+    if (min_copies == 0) return fail(FPM_EINVAL, "min_copies must be >= 1");
+    job->min_copies = min_copies;
+    return FPM_OK;
+}
+
+// One widening round of reads mode over `wide` (the staged job itself, or a job staged with a
+// wider sketch size over the groups still open): its exact bottom-S' rows, the counts and
+// positions of their entries, the filter, the full sketches' maximum.
+static int reads_round(fpm_sketch_job *job, fpm_sketch_job *wide, uint32_t round, hipStream_t st)
+{
+    fpm_ctx *ctx = job->ctx;
+    const uint32_t m = job->min_copies, s = job->kp.s, S = wide->kp.s, ng = job->n_groups;
+    if (int rc = fpm_sketch_run(wide, st)) return rc;
+    job->reads_sampled = (int32_t)wide->n_slots;
+    // per wide-row entry: a u32 count and min_copies u64 position slots, from the context's
+    // pool of released buffers (no device-wide allocation per round once it is warm)
+    const size_t n_ent = (size_t)ng * S;
+    const size_t wcnt_bytes = n_ent * sizeof(uint32_t);
+    const size_t slots_bytes = n_ent * m * sizeof(unsigned long long);
+    uint32_t *d_wcnt = nullptr;
+    unsigned long long *d_slots = nullptr;
+    auto body = [&]() -> int {
+        size_t mem_free = 0, mem_total = 0;
+        HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
+        if (wcnt_bytes + slots_bytes > mem_free)
+            return fail(FPM_ENOMEM, "reads mode: " + std::to_string((wcnt_bytes + slots_bytes) >> 20) +
+                                        " MB of counts and position slots (groups x wide sketch x "
+                                        "(4 + 8 min_copies) B) exceed the free device memory");
+        HIP_TRY(pool_alloc(ctx, (void **)&d_wcnt, wcnt_bytes));
+        HIP_TRY(pool_alloc(ctx, (void **)&d_slots, slots_bytes));
+        HIP_TRY(hipMemsetAsync(d_wcnt, 0, n_ent * sizeof(uint32_t), st));
+        HIP_TRY(hipMemsetAsync(d_slots, 0xff, n_ent * m * sizeof(unsigned long long), st));
+        for (int c = 0; c < kTileClasses; c++) {
+            const uint32_t b = wide->class_begin[c], n = wide->class_begin[c + 1] - b;
+            if (!n) continue;
+            TimedLaunch tl(ctx, FPM_K_SKETCH, st);
+            HIP_TRY(launch_reads_count(c, wide->d_seq, wide->d_tiles + b, n, wide->kp, wide->d_rows,
+                                       wide->d_count, m, d_wcnt, d_slots, st));
+            tl.done();
+        }
+        HIP_TRY(launch_reads_filter(wide->d_rows, wide->d_count, S, ng, d_wcnt, d_slots, m, s, round,
+                                    job->d_rdone, job->d_rrows, job->d_rcount, job->d_rmult,
+                                    job->d_rttop, st));
+        for (int c = 0; c < kTileClasses; c++) {
+            const uint32_t b = wide->class_begin[c], n = wide->class_begin[c + 1] - b;
+            if (!n) continue;
+            TimedLaunch tl(ctx, FPM_K_SKETCH, st);
+            HIP_TRY(launch_reads_maxcount(c, wide->d_seq, wide->d_tiles + b, n, wide->kp, s, round,
+                                          job->d_rdone, job->d_rrows, job->d_rcount, job->d_rmult,
+                                          job->d_rttop, st));
+            tl.done();
+        }
+        // the one host read of the round: which groups are final
+        HIP_TRY(hipMemcpyAsync(job->h_rdone.data(), job->d_rdone, ng * sizeof(uint32_t),
+                               hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return FPM_OK;
+    };
+    const int rc = body();
+    if (rc) (void)hipStreamSynchronize(st);
+    pool_free(ctx, d_wcnt, wcnt_bytes);
+    pool_free(ctx, d_slots, slots_bytes);
+    return rc;
+}
+
+int fpm_sketch_reads_run(fpm_sketch_job *job, void *stream)
+{
+    if (!job) return fail(FPM_EINVAL, "null job");
+    fpm_ctx *ctx = job->ctx;
+    if (int rc = set_device(ctx)) return rc;
+    hipStream_t st = pick_stream(ctx, stream);
+    const uint64_t s = job->kp.s, ng = job->n_groups;
+    job->reads_rounds = 0;
+    if (!ng) return FPM_OK;
+    if (!job->d_rrows) {
+        // all five or none: a later run must not find some of them missing
+        hipError_t e = hipMalloc((void **)&job->d_rrows, ng * s * sizeof(uint64_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&job->d_rmult, ng * s * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&job->d_rcount, ng * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&job->d_rdone, ng * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&job->d_rttop, ng * sizeof(uint64_t));
+        if (e != hipSuccess) {
+            for (void *p : {(void *)job->d_rrows, (void *)job->d_rmult, (void *)job->d_rcount,
+                            (void *)job->d_rdone, (void *)job->d_rttop})
+                (void)hipFree(p);
+            job->d_rrows = job->d_rttop = nullptr;
+            job->d_rmult = job->d_rcount = job->d_rdone = nullptr;
+            job->reads_rounds = -1;
+            return fail(FPM_ENOMEM, std::string("reads mode output alloc: ") + hipGetErrorString(e));
+        }
+    }
+    job->h_rdone.assign(ng, 0);
+    HIP_TRY(hipMemsetAsync(job->d_rdone, 0, ng * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(job->d_rcount, 0, ng * sizeof(uint32_t), st));
+    // The wide row must reach the s-th hash with min_copies occurrences: sequencing errors put
+    // several single-copy k-mers below each repeated one, so the first width is 8 s and each
+    // further round has 4 x the last, up to one more than the windows of the largest group
+    // still open (a row of that width is never full: it holds every distinct hash of its
+    // group).  min_copies 1 needs no widening: every entry qualifies.
+    std::vector<uint64_t> windows(ng, 0);
+    for (uint32_t r : job->recs.order)
+        if (job->recs.len[r] >= job->kp.k)
+            windows[job->recs.group[r]] += job->recs.len[r] - job->kp.k + 1;
+    auto open_cap = [&]() {
+        uint64_t c = 0;
+        for (uint64_t g = 0; g < ng; g++)
+            if (!job->h_rdone[g]) c = std::max(c, windows[g]);
+        return std::min<uint64_t>(c + 1, 0x7fffffffULL);
+    };
+    uint64_t cap = open_cap();
+    uint64_t wide = job->min_copies == 1 ? s : std::min<uint64_t>(8 * s, cap);
+    for (uint32_t round = 1;; round++) {
+        if (wide == s) {
+            if (int rc = reads_round(job, job, round, st)) return rc;
+        } else {
+            StageRecords R;
+            R.n_groups = job->n_groups;
+            R.pos = job->recs.pos;
+            R.len = job->recs.len;
+            R.group = job->recs.group;
+            for (uint32_t r : job->recs.order)
+                if (!job->h_rdone[R.group[r]]) R.order.push_back(r);
+            R.d_seq = job->d_seq;
+            R.d_seq_bytes = job->seq_bytes;
+            R.borrow = true;
+            fpm_sketch_params p = job->params;
+            p.sketch_size = (uint32_t)wide;
+            fpm_sketch_job *wj = nullptr;
+            if (int rc = stage_core(ctx, &p, R, &wj)) return rc;
+            const int rc = reads_round(job, wj, round, st);
+            fpm_sketch_job_free(wj);
+            if (rc) return rc;
+        }
+        job->reads_rounds = (int32_t)round;
+        bool open = false;
+        for (uint32_t d : job->h_rdone) open = open || !d;
+        if (!open) return FPM_OK;
+        if (wide >= cap) return fail(FPM_EHIP, "internal: reads mode left a group open");
+        cap = open_cap();
+        wide = std::min<uint64_t>(wide * 4, cap);
+    }
+}
+
+int fpm_sketch_reads_fetch(fpm_sketch_job *job, uint64_t *out_hashes, uint32_t *out_count,
+                           uint32_t *out_mult, uint64_t *out_estimate)
+{
+    if (!job) return fail(FPM_EINVAL, "null job");
+    if (job->reads_rounds < 0) return fail(FPM_EINVAL, "reads_fetch before reads_run");
+    fpm_ctx *ctx = job->ctx;
+    if (int rc = set_device(ctx)) return rc;
+    const size_t s = job->kp.s, ng = job->n_groups;
+    if (!ng) return FPM_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<uint32_t> cnt(ng);
+    HIP_TRY(copy_out(ctx, cnt.data(), job->d_rcount, ng * sizeof(uint32_t)));
+    if (out_count) memcpy(out_count, cnt.data(), ng * sizeof(uint32_t));
+    std::vector<uint64_t> tmp;
+    if (!out_hashes && out_estimate) {
+        tmp.resize(ng * s);
+        out_hashes = tmp.data();
+    }
+    if (out_hashes) HIP_TRY(d2h_staged(ctx, out_hashes, job->d_rrows, ng * s * sizeof(uint64_t)));
+    if (out_mult) HIP_TRY(d2h_staged(ctx, out_mult, job->d_rmult, ng * s * sizeof(uint32_t)));
+    if (out_estimate) {
+        // MinHashHeap::estimateSetSize (MinHashHeap.h:45), truncated as Sketch.cpp:1432 stores it
+        const double range = job->kp.use64 ? 18446744073709551616.0 : 4294967296.0;
+        for (size_t g = 0; g < ng; g++) {
+            out_estimate[g] = 0;
+            if (!cnt[g]) continue;
+            const double e = range * (double)cnt[g] / (double)out_hashes[g * s + cnt[g] - 1];
+            out_estimate[g] = e < 18446744073709551616.0 ? (uint64_t)e : ~0ULL;
+        }
+    }
+    return FPM_OK;
+}
+
+int fpm_sketch_job_reads_rounds(fpm_sketch_job *job, int32_t *n_rounds, uint32_t *group_round)
+{
+    if (!job || !n_rounds) return fail(FPM_EINVAL, "null argument");
+    *n_rounds = job->reads_rounds;
+    if (group_round && job->reads_rounds >= 0)
+        for (uint32_t g = 0; g < job->n_groups; g++) group_round[g] = job->h_rdone[g];
+    return FPM_OK;
+}
+
+int fpm_sketch_job_reads_sampled(fpm_sketch_job *job, int32_t *n_sampled)
+{
+    if (!job || !n_sampled) return fail(FPM_EINVAL, "null argument");
+    *n_sampled = job->reads_rounds < 0 ? -1 : job->reads_sampled;
     return FPM_OK;
 }
 

@@ -948,6 +948,216 @@ hipError_t launch_mult_ttop(const uint32_t *d_count, uint32_t n_groups, uint32_t
     return hipGetLastError();
 }
 
+// ---- reads mode (-r / -m N): MinHashHeap::tryInsert with multiplicityMinimum = m and no Bloom
+// filter (MinHashHeap.cpp:68-146).  The heap's top only falls, so the final hashes are F, the
+// s smallest hashes with >= m occurrences in the group, each with its full count -- except
+// the maximum of a full F, which stops counting once the heap holds exactly F (`hash < top`
+// fails, :73): at T = the largest m-th-occurrence position among F.
+//   reads_count_kernel:    every window hashing into its group's wide row (the exact bottom-S'
+//                          distinct sketch, S' > s) adds 1 to that entry's count and passes its
+//                          position down the entry's m slots: slot j ends as the (j+1)-th
+//                          smallest position whatever the interleaving (each atomicMin step
+//                          conserves the multiset {slot, x})
+//                          (the wide row's own maximum is counted too, unlike the final
+//                          maximum in sketch_mult_kernel's pass 0: this pass runs over all the
+//                          windows after the row is final, so that entry's count is complete
+//                          and it may be the s-th qualifier)
+//   reads_filter_kernel:   per group, the first s entries with count >= m -> the output row,
+//                          counts, T; complete when s were found or the wide row holds every
+//                          hash of the group (it is not full)
+//   reads_maxcount_kernel: occurrences of the maximum of a full F at positions <= T
+// Positions are byte offsets in the staged buffer, as in the -M pass above.
+template <int P>
+__global__ __launch_bounds__(kBlock) void reads_count_kernel(
+    const uint8_t *__restrict__ seq, const TileDesc *__restrict__ tiles, SketchKParams p,
+    const uint64_t *__restrict__ rows, const uint32_t *__restrict__ count, uint32_t m,
+    uint32_t *__restrict__ wcnt, unsigned long long *__restrict__ slots)
+{
+    using I = TileImg<P>;
+    constexpr int E = I::E;
+    __shared__ __attribute__((aligned(16))) uint32_t img[I::kBytes / 4];
+    uint8_t *const alpha = reinterpret_cast<uint8_t *>(img + (I::kFBytes + I::kRBytes) / 4 +
+                                                       I::kMaskWords);
+    uint8_t *const compl_tab = alpha + 256;
+    const TileDesc td = tiles[blockIdx.x];
+    const uint32_t g = td.pad;
+    const uint32_t ng = count[g];
+    if (ng == 0) return;                                   // block-uniform
+    const int tid = threadIdx.x;
+    alpha[tid] = p.alphabet[tid];
+    compl_tab[tid] = p.complement[tid];
+    __syncthreads();
+    tile_stage<P>(seq, td, p, img, tid);
+    __syncthreads();
+    uint64_t kr[E];
+#pragma unroll
+    for (int e = 0; e < E; e++) kr[e] = ~0ULL;
+    const uint32_t vbits = tile_hash<P, 0>(td, p, img, tid, [&](int e, uint64_t h) { kr[e] = h; });
+    const uint64_t *row = rows + (uint64_t)g * p.s;
+    const uint64_t hmax = row[ng - 1];
+#pragma unroll
+    for (int e = 0; e < E; e++) {
+        if (!(vbits >> e & 1) || kr[e] > hmax) continue;
+        const uint32_t i = lower_bound_row(row, ng, kr[e]);
+        if (row[i] != kr[e]) continue;
+        const uint64_t at = (uint64_t)g * p.s + i;
+        atomicAdd(&wcnt[at], 1u);
+        unsigned long long x = td.byte_off + (uint64_t)tid * E + e;
+        for (uint32_t j = 0; j < m; j++) {
+            const unsigned long long old = atomicMin(&slots[at * m + j], x);
+            x = max(old, x);
+            if (x == ~0ULL) break;                         // the later slots are still empty
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void reads_filter_kernel(
+    const uint64_t *__restrict__ rows, const uint32_t *__restrict__ count, uint32_t wide,
+    const uint32_t *__restrict__ wcnt, const unsigned long long *__restrict__ slots, uint32_t m,
+    uint32_t s, uint32_t round, uint32_t *__restrict__ done, uint64_t *__restrict__ out_rows,
+    uint32_t *__restrict__ out_count, uint32_t *__restrict__ out_mult,
+    uint64_t *__restrict__ ttop)
+{
+    __shared__ uint32_t scan_tmp[kWaves + 1];
+    __shared__ unsigned long long red[kWaves];
+    const uint32_t g = blockIdx.x;
+    if (done[g]) return;                                   // completed by an earlier round
+    const uint32_t ng = count[g];
+    const uint64_t *row = rows + (uint64_t)g * wide;
+    uint32_t carry = 0;
+    unsigned long long tmax = 0;
+    for (uint32_t c0 = 0; c0 < ng && carry < s; c0 += kBlock) {   // block-uniform bounds
+        const uint32_t i = c0 + threadIdx.x;
+        const uint64_t at = (uint64_t)g * wide + i;
+        const uint32_t c = i < ng ? wcnt[at] : 0u;
+        const uint32_t q = c >= m ? 1u : 0u;
+        uint32_t tot;
+        const uint32_t r = carry + block_exscan(q, scan_tmp, &tot);
+        if (q && r < s) {
+            out_rows[(uint64_t)g * s + r] = row[i];
+            out_mult[(uint64_t)g * s + r] = c;
+            tmax = max(tmax, slots[at * m + (m - 1)]);
+        }
+        carry += tot;
+    }
+    // fewer than s qualifiers are final only when the wide row holds all the group's hashes
+    if (carry < s && ng >= wide) return;
+    for (int o = 32; o; o >>= 1) tmax = max(tmax, __shfl_xor(tmax, o, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = tmax;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kWaves; w++) tmax = max(tmax, red[w]);
+        const bool full = carry >= s;
+        out_count[g] = full ? s : carry;
+        ttop[g] = tmax;
+        // the maximum of a full sketch is counted again, up to T (reads_maxcount_kernel)
+        if (full) out_mult[(uint64_t)g * s + s - 1] = 0;
+        done[g] = round;
+    }
+}
+
+template <int P>
+__global__ __launch_bounds__(kBlock) void reads_maxcount_kernel(
+    const uint8_t *__restrict__ seq, const TileDesc *__restrict__ tiles, SketchKParams p,
+    uint32_t s, uint32_t round, const uint32_t *__restrict__ done,
+    const uint64_t *__restrict__ out_rows, const uint32_t *__restrict__ out_count,
+    uint32_t *__restrict__ out_mult, const uint64_t *__restrict__ ttop)
+{
+    using I = TileImg<P>;
+    constexpr int E = I::E;
+    __shared__ __attribute__((aligned(16))) uint32_t img[I::kBytes / 4];
+    uint8_t *const alpha = reinterpret_cast<uint8_t *>(img + (I::kFBytes + I::kRBytes) / 4 +
+                                                       I::kMaskWords);
+    uint8_t *const compl_tab = alpha + 256;
+    const TileDesc td = tiles[blockIdx.x];
+    const uint32_t g = td.pad;
+    // block-uniform exits: groups this round did not complete, sketches that are not full,
+    // tiles past T
+    if (done[g] != round || out_count[g] < s || td.byte_off > ttop[g]) return;
+    const int tid = threadIdx.x;
+    alpha[tid] = p.alphabet[tid];
+    compl_tab[tid] = p.complement[tid];
+    __syncthreads();
+    tile_stage<P>(seq, td, p, img, tid);
+    __syncthreads();
+    uint64_t kr[E];
+#pragma unroll
+    for (int e = 0; e < E; e++) kr[e] = ~0ULL;
+    const uint32_t vbits = tile_hash<P, 0>(td, p, img, tid, [&](int e, uint64_t h) { kr[e] = h; });
+    const uint64_t hmax = out_rows[(uint64_t)g * s + s - 1];
+    const uint64_t t = ttop[g];
+#pragma unroll
+    for (int e = 0; e < E; e++) {
+        if (!(vbits >> e & 1) || kr[e] != hmax) continue;
+        const uint64_t pos = td.byte_off + (uint64_t)tid * E + e;
+        if (pos <= t) atomicAdd(&out_mult[(uint64_t)g * s + s - 1], 1u);
+    }
+}
+
+hipError_t launch_reads_count(int cls, const uint8_t *d_seq, const TileDesc *d_tiles,
+                              uint32_t n_tiles, const SketchKParams &p, const uint64_t *d_rows,
+                              const uint32_t *d_count, uint32_t m, uint32_t *d_wcnt,
+                              unsigned long long *d_slots, hipStream_t st)
+{
+    if (n_tiles == 0) return hipSuccess;
+#define FPM_READS_CASE(c, P)                                                                   \
+    case c:                                                                                    \
+        hipLaunchKernelGGL((reads_count_kernel<P>), dim3(n_tiles), dim3(kBlock), 0, st, d_seq,  \
+                           d_tiles, p, d_rows, d_count, m, d_wcnt, d_slots);                    \
+        break;
+    switch (cls) {
+        FPM_READS_CASE(0, 256)
+        FPM_READS_CASE(1, 512)
+        FPM_READS_CASE(2, 1024)
+        FPM_READS_CASE(3, 2048)
+        FPM_READS_CASE(4, 4096)
+        FPM_READS_CASE(5, 8192)
+    default: return hipErrorInvalidValue;
+    }
+#undef FPM_READS_CASE
+    return hipGetLastError();
+}
+
+hipError_t launch_reads_filter(const uint64_t *d_rows, const uint32_t *d_count, uint32_t wide,
+                               uint32_t n_groups, const uint32_t *d_wcnt,
+                               const unsigned long long *d_slots, uint32_t m, uint32_t s,
+                               uint32_t round, uint32_t *d_done, uint64_t *d_out_rows,
+                               uint32_t *d_out_count, uint32_t *d_out_mult, uint64_t *d_ttop,
+                               hipStream_t st)
+{
+    if (n_groups == 0) return hipSuccess;
+    hipLaunchKernelGGL(reads_filter_kernel, dim3(n_groups), dim3(kBlock), 0, st, d_rows, d_count,
+                       wide, d_wcnt, d_slots, m, s, round, d_done, d_out_rows, d_out_count,
+                       d_out_mult, d_ttop);
+    return hipGetLastError();
+}
+
+hipError_t launch_reads_maxcount(int cls, const uint8_t *d_seq, const TileDesc *d_tiles,
+                                 uint32_t n_tiles, const SketchKParams &p, uint32_t s,
+                                 uint32_t round, const uint32_t *d_done, const uint64_t *d_out_rows,
+                                 const uint32_t *d_out_count, uint32_t *d_out_mult,
+                                 const uint64_t *d_ttop, hipStream_t st)
+{
+    if (n_tiles == 0) return hipSuccess;
+#define FPM_READS_CASE(c, P)                                                                   \
+    case c:                                                                                    \
+        hipLaunchKernelGGL((reads_maxcount_kernel<P>), dim3(n_tiles), dim3(kBlock), 0, st,      \
+                           d_seq, d_tiles, p, s, round, d_done, d_out_rows, d_out_count,        \
+                           d_out_mult, d_ttop);                                                 \
+        break;
+    switch (cls) {
+        FPM_READS_CASE(0, 256)
+        FPM_READS_CASE(1, 512)
+        FPM_READS_CASE(2, 1024)
+        FPM_READS_CASE(3, 2048)
+        FPM_READS_CASE(4, 4096)
+        FPM_READS_CASE(5, 8192)
+    default: return hipErrorInvalidValue;
+    }
+#undef FPM_READS_CASE
+    return hipGetLastError();
+}
+
 // thr_safe[i] = the s-th smallest of sample row srow[i] when it holds s hashes (a subset's
 // order statistic: >= the group's own s-th smallest), else no bound.  thr[i] = the tighter
 // kt[i]-th smallest (kt: null = the safe bound): the sample holds ~f of the group's windows,

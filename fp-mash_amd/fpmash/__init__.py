@@ -78,6 +78,11 @@ SYMBOLS = [
     ("fpm_sketch_device_output", C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), u32p, u32p]),
     ("fpm_sketch_fetch", C.c_int, [vp, u64p, u32p]),
     ("fpm_sketch_mult", C.c_int, [vp, vp, u32p]),
+    ("fpm_sketch_job_set_min_copies", C.c_int, [vp, C.c_uint32]),
+    ("fpm_sketch_reads_run", C.c_int, [vp, vp]),
+    ("fpm_sketch_reads_fetch", C.c_int, [vp, u64p, u32p, u32p, u64p]),
+    ("fpm_sketch_job_reads_rounds", C.c_int, [vp, C.POINTER(C.c_int32), u32p]),
+    ("fpm_sketch_job_reads_sampled", C.c_int, [vp, C.POINTER(C.c_int32)]),
     ("fpm_merge_small_spills", C.c_int, [vp, u64p]),
     ("fpm_sketch_job_info", C.c_int, [vp, u64p, u64p, u64p]),
     ("fpm_sketch_job_redo_tiles", C.c_int, [vp, C.POINTER(C.c_int32)]),
@@ -365,8 +370,10 @@ def expand_compact(numer, denom, listed, n_ref, max_dist=-1.0, max_pvalue=-1.0):
 class SketchJob:
     """fpm_sketch_stage/run/fetch: inputs staged once in HBM, kernels re-runnable."""
 
-    def __init__(self, ctx, params, seqs, groups=None, n_groups=None):
+    def __init__(self, ctx, params, seqs, groups=None, n_groups=None, min_copies=1):
         self.ctx, self.params = ctx, params
+        if min_copies < 1:
+            raise FpmError(FPM_EINVAL, "min_copies must be >= 1")
         data, off = pack_records(seqs)
         self._keep = (data, off)
         n_rec = len(seqs)
@@ -380,9 +387,46 @@ class SketchJob:
         _check(lib().fpm_sketch_stage(ctx.h, C.byref(params), data, _p(off, u64p), n_rec, gp,
                                       self.n_groups, C.byref(h)))
         self.h = h.value
+        if min_copies != 1:
+            self.set_min_copies(min_copies)
 
     def run(self, stream=None):
         _check(lib().fpm_sketch_run(self.h, stream))
+
+    # --- reads mode (sketch -r / -m N) ---
+    def set_min_copies(self, min_copies):
+        _check(lib().fpm_sketch_job_set_min_copies(self.h, min_copies))
+
+    def run_reads(self, stream=None):
+        """fpm_sketch_reads_run: the sketches of the hashes seen >= min_copies times."""
+        _check(lib().fpm_sketch_reads_run(self.h, stream))
+
+    def fetch_reads(self):
+        """-> rows [n_groups, s] u64, counts per row u32, multiplicities [n_groups, s] u32,
+        set-size estimates u64 (MinHashHeap::estimateSetSize; 0 for an empty sketch)."""
+        s, n = int(self.params.sketch_size), self.n_groups
+        out = np.zeros(max(n, 1) * s, dtype=np.uint64)
+        cnt = np.zeros(max(n, 1), dtype=np.uint32)
+        mult = np.zeros(max(n, 1) * s, dtype=np.uint32)
+        est = np.zeros(max(n, 1), dtype=np.uint64)
+        _check(lib().fpm_sketch_reads_fetch(self.h, _p(out, u64p), _p(cnt, u32p), _p(mult, u32p),
+                                            _p(est, u64p)))
+        return out[: n * s].reshape(n, s), cnt[:n], mult[: n * s].reshape(n, s), est[:n]
+
+    def reads_rounds(self):
+        """widening rounds of the last run_reads() (-1: none yet) and, per group, the round
+        that completed it"""
+        r = C.c_int32()
+        per = np.zeros(max(self.n_groups, 1), dtype=np.uint32)
+        _check(lib().fpm_sketch_job_reads_rounds(self.h, C.byref(r), _p(per, u32p)))
+        return r.value, per[: self.n_groups]
+
+    def reads_sampled(self):
+        """long groups the last round's wide sketch of the last run_reads() sampled (-1: none
+        yet)"""
+        n = C.c_int32()
+        _check(lib().fpm_sketch_job_reads_sampled(self.h, C.byref(n)))
+        return n.value
 
     def info(self):
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -567,9 +611,13 @@ class Context:
         return {"sparse": sp.value, "events": ev.value, "candidates": ca.value}
 
     # --- sketch -----------------------------------------------------------
-    def sketch(self, params, seqs, groups=None, n_groups=None, counts=False):
+    def sketch(self, params, seqs, groups=None, n_groups=None, counts=False, min_copies=1):
         """-> list of ascending u64 arrays (one per sketch); counts=True (-M): also the list
-        of their u32 multiplicities."""
+        of their u32 multiplicities.  min_copies > 1: reads mode, only hashes seen at least
+        min_copies times (sketch_reads has the estimates too)."""
+        if min_copies != 1:
+            r = self.sketch_reads(params, seqs, groups, n_groups, min_copies)
+            return (r["hashes"], r["counts"]) if counts else r["hashes"]
         job = SketchJob(self, params, seqs, groups, n_groups)
         try:
             job.run()
@@ -582,8 +630,28 @@ class Context:
             return hashes, [mult[i, : cnt[i]].copy() for i in range(len(cnt))]
         return hashes
 
-    def sketch_job(self, params, seqs, groups=None, n_groups=None):
-        return SketchJob(self, params, seqs, groups, n_groups)
+    def sketch_job(self, params, seqs, groups=None, n_groups=None, min_copies=1):
+        return SketchJob(self, params, seqs, groups, n_groups, min_copies)
+
+    @staticmethod
+    def _reads_result(job):
+        job.run_reads()
+        rows, cnt, mult, est = job.fetch_reads()
+        rounds, per = job.reads_rounds()
+        return {"hashes": [rows[i, : cnt[i]].copy() for i in range(len(cnt))],
+                "counts": [mult[i, : cnt[i]].copy() for i in range(len(cnt))],
+                "estimate": est.copy(), "rounds": rounds, "group_round": per,
+                "sampled": job.reads_sampled()}
+
+    def sketch_reads(self, params, seqs, groups=None, n_groups=None, min_copies=1):
+        """Reads mode (sketch -r -m min_copies): per group the s smallest hashes seen at least
+        min_copies times -> dict of hashes, counts (lists of arrays), estimate (u64 set-size
+        estimates), rounds and group_round (the widening rounds hook)."""
+        job = SketchJob(self, params, seqs, groups, n_groups, min_copies)
+        try:
+            return self._reads_result(job)
+        finally:
+            job.free()
 
     # --- FASTA text on the device -------------------------------------------------
     def seq_parse(self, files):
@@ -607,9 +675,10 @@ class Context:
         return job.value, {"seg": seg[:n], "hdr_off": ho[:n], "hdr_len": hl[:n],
                            "seq_len": sl[:n]}, bool(q.value)
 
-    def sketch_seq(self, params, seq_job, groups, n_groups, counts=False):
+    def sketch_seq(self, params, seq_job, groups, n_groups, counts=False, min_copies=1):
         """fpm_sketch_stage_seq + run + fetch over parsed records (the job takes the packed
-        records; free the parse handle with seq_free afterwards)."""
+        records; free the parse handle with seq_free afterwards).  min_copies > 1: reads mode,
+        only hashes seen at least min_copies times."""
         g = np.ascontiguousarray(groups, dtype=np.uint32)
         if g.size == 0:
             g = np.zeros(1, np.uint32)
@@ -618,6 +687,13 @@ class Context:
                                           n_groups, C.byref(h)))
         job = SketchJob.__new__(SketchJob)
         job.ctx, job.params, job.n_groups, job.h, job._keep = self, params, n_groups, h.value, None
+        if min_copies != 1:
+            try:
+                job.set_min_copies(min_copies)
+                r = self._reads_result(job)
+            finally:
+                job.free()
+            return (r["hashes"], r["counts"]) if counts else r["hashes"]
         try:
             job.run()
             rows, cnt = job.fetch()

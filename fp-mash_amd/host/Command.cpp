@@ -287,13 +287,38 @@ int sketchParameterSetup(Parameters &p, const Command &c)
     p.parallelism = (int)c.getOption("threads").getArgumentAsNumber();
     p.preserveCase = c.getOption("case").active;
     if (c.hasOption("warning")) p.warning = c.getOption("warning").getArgumentAsNumber();
-    if (c.getOption("memory").active || c.getOption("minCov").active ||
-        c.getOption("targetCov").active || c.getOption("genome").active)
+    p.minCov = (uint32_t)c.getOption("minCov").getArgumentAsNumber();
+    // sketchParameterSetup.cpp:33-70
+    if (c.getOption("memory").active && c.getOption("minCov").active) {
+        std::cerr << "ERROR: The option " << c.getOption("minCov").identifier
+                  << " cannot be used with " << c.getOption("memory").identifier << "." << std::endl;
+        return 1;
+    }
+    if (c.getOption("memory").active || c.getOption("targetCov").active) {
+        // the Bloom filter's result depends on its false positives, target coverage is a
+        // sequential early stop per read: neither has an exact parallel form
+        std::cerr << "ERROR: the reads-mode options -" << c.getOption("memory").identifier
+                  << " (Bloom filter) and -" << c.getOption("targetCov").identifier
+                  << " (target coverage) are not supported by fpmash." << std::endl;
+        return 1;
+    }
+    if (c.getOption("minCov").active) p.reads = true;
+    if (c.getOption("genome").active) {
         p.reads = true;
-    if (p.reads) {
-        // reads mode (Bloom / minCov / targetCov / genome size) is outside the MI355X hot path
-        std::cerr << "ERROR: reads mode (-r/-b/-m/-c/-g) is not supported by fpmash; sketch "
-                     "assemblies or -fp k-finger files." << std::endl;
+        p.genomeSize = (uint64_t)c.getOption("genome").getArgumentAsNumber();
+    }
+    if (p.reads) p.counts = true;
+    if (p.reads && p.minCov < 1) {
+        std::cerr << "ERROR: -" << c.getOption("minCov").identifier << " must be at least 1."
+                  << std::endl;
+        return 1;
+    }
+    if (p.reads && c.getOption("threads").active)
+        std::cerr << "WARNING: The option " << c.getOption("threads").identifier
+                  << " will be ignored with " << c.getOption("reads").identifier << "." << std::endl;
+    if (p.reads && !p.concatenated) {
+        std::cerr << "ERROR: The option " << c.getOption("individual").identifier
+                  << " cannot be used with " << c.getOption("reads").identifier << "." << std::endl;
         return 1;
     }
     if (p.fingerprint) {

@@ -268,6 +268,14 @@ int CommandDistance::run() const
     const double lengthThreshold =
         (parameters.warning * sketchRef.getKmerSpace()) / (1. - parameters.warning);
     if (isSketch) {
+        // (CommandDistance.cpp:137-144)
+        if (options.at("sketchSize").active && parameters.reads &&
+            parameters.minHashesPerWindow != (uint64_t)sketchRef.getMinHashesPerWindow()) {
+            std::cerr << "ERROR: The sketch size must match the reference when using a bloom "
+                         "filter (leave this option out to inherit from the reference sketch)."
+                      << std::endl;
+            return 1;
+        }
         parameters.minHashesPerWindow = (uint64_t)sketchRef.getMinHashesPerWindow();
         parameters.kmerSize = sketchRef.getKmerSize();
         parameters.noncanonical = sketchRef.getNoncanonical();

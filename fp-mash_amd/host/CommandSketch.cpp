@@ -62,7 +62,8 @@ int CommandSketch::run() const
     std::unique_ptr<Sketch> owned(new Sketch());
     Sketch &sketch = *owned;
     sketch.keepDeviceRows();   // the rows are only written to the .msh
-    if (fingerprint) sketch.initFromFingerprints(files, parameters);
+    if (parameters.reads) sketch.initFromReads(files, parameters);
+    else if (fingerprint) sketch.initFromFingerprints(files, parameters);
     else sketch.initFromFiles(files, parameters, verbosity);
     if (getOption("id").active) sketch.setReferenceName(0, getOption("id").argument);
     if (getOption("comment").active) sketch.setReferenceComment(0, getOption("comment").argument);

@@ -223,7 +223,7 @@ static void sketchFiles(fpm_ctx *ctx, const Parameters &parameters,
                         const std::vector<std::string> &seqFiles, std::vector<std::string> &images,
                         size_t f0, size_t f1, std::vector<std::vector<Reference>> &fileRefs,
                         bool timing, std::vector<std::shared_ptr<void>> *stores = nullptr,
-                        std::mutex *storeMu = nullptr)
+                        std::mutex *storeMu = nullptr, bool oneGroup = false)
 {
     const size_t nF = f1 - f0;
     auto mark = [&](const char *what) { if (timing) phaseMark(what); };
@@ -246,7 +246,10 @@ static void sketchFiles(fpm_ctx *ctx, const Parameters &parameters,
     mark("device parse (upload + scan + emit)");
     std::string hostSeq;               // host fallback: the records' bytes
     std::vector<uint64_t> hostOff{0};
-    if (!quality) {
+    // one sketch of several read files takes their records in turn (below): the stream order
+    // is then not the parse's file order, so the records are walked and packed on the host
+    const bool hostWalk = quality || (oneGroup && nF > 1);
+    if (!hostWalk) {
         std::vector<uint32_t> seg(nRec);
         std::vector<uint64_t> ho(nRec), hl(nRec), sl(nRec);
         check(fpm_seq_records(parsed, seg.data(), ho.data(), hl.data(), sl.data()),
@@ -283,7 +286,44 @@ static void sketchFiles(fpm_ctx *ctx, const Parameters &parameters,
     std::vector<uint32_t> groupOf(nIds, FPM_NO_GROUP);
     uint32_t nGroups = 0;
     std::vector<std::vector<uint32_t>> fileGroups(nF);
-    for (size_t f = 0; f < nF; f++) {
+    std::vector<char> groupSkipped;     // reads mode: the group skipped a record shorter than k
+    std::vector<uint32_t> stageOrder;   // oneGroup: its records in stream order
+    if (oneGroup) {
+        // sketchFile over all the files (Sketch.cpp:1317-1444): the name is the first file's
+        // that is not stdin, the records come round-robin from the files still open (a
+        // record shorter than k does not end its file's turn, :1374-1378)
+        Reference ref;
+        const uint32_t g = nGroups++;
+        int count = 0;
+        bool skipped = false;
+        for (size_t f = 0; f < nF; f++)
+            if (ref.name.empty() && seqFiles[f0 + f] != "-") ref.name = seqFiles[f0 + f];
+        std::vector<size_t> at(nF, 0), open(nF);
+        for (size_t f = 0; f < nF; f++) open[f] = f;
+        for (size_t it = 0; !open.empty();) {
+            const size_t f = open[it];
+            if (at[f] == recs[f].size()) {
+                open.erase(open.begin() + it);
+                if (it == open.size()) it = 0;
+                continue;
+            }
+            const SeqRec &x = recs[f][at[f]++];
+            if (x.length < (uint64_t)parameters.kmerSize) { skipped = true; continue; }
+            if (count == 0) {
+                if (seqFiles[f0] == "-") { ref.name = x.name; ref.comment = x.comment; }
+                else ref.comment = x.name + " " + x.comment;
+            }
+            count++;
+            groupOf[x.id] = g;
+            stageOrder.push_back(x.id);
+            if (++it == open.size()) it = 0;
+        }
+        if (count > 1) ref.comment = "[" + std::to_string(count) + " seqs] " + ref.comment + " [...]";
+        groupSkipped.push_back(skipped);
+        fileRefs[f0].push_back(std::move(ref));
+        fileGroups[0].push_back(g);
+    }
+    for (size_t f = 0; f < nF && !oneGroup; f++) {
         const std::string &file = seqFiles[f0 + f];
         if (parameters.concatenated) {
             Reference ref;
@@ -298,11 +338,13 @@ static void sketchFiles(fpm_ctx *ctx, const Parameters &parameters,
                     else ref.comment = x.name + " " + x.comment;
                 }
                 count++;
-                ref.length += x.length;
+                if (!parameters.reads) ref.length += x.length;   // (Sketch.cpp:1403-1406)
                 groupOf[x.id] = g;
             }
             if (count > 1) ref.comment = "[" + std::to_string(count) + " seqs] " + ref.comment + " [...]";
-            if (ref.length == 0) {
+            groupSkipped.push_back(skipped);
+            // (a read set's length is known after its sketch: checked there)
+            if (ref.length == 0 && !parameters.reads) {
                 if (skipped)
                     std::cerr << "\nWARNING: All fasta records in input files were shorter than the "
                                  "k-mer size (" << parameters.kmerSize << ")." << std::endl;
@@ -355,7 +397,11 @@ static void sketchFiles(fpm_ctx *ctx, const Parameters &parameters,
             std::vector<uint64_t> off{0};
             std::vector<uint32_t> grp;
             std::string packed;
-            for (uint64_t r = 0; r < nIds; r++) {
+            if (!oneGroup) {
+                stageOrder.resize(nIds);
+                for (uint64_t r = 0; r < nIds; r++) stageOrder[r] = (uint32_t)r;
+            }
+            for (const uint32_t r : stageOrder) {
                 if (groupOf[r] == FPM_NO_GROUP) continue;
                 packed.append(hostSeq, hostOff[r], hostOff[r + 1] - hostOff[r]);
                 off.push_back(packed.size());
@@ -365,19 +411,64 @@ static void sketchFiles(fpm_ctx *ctx, const Parameters &parameters,
                                    grp.data(), nGroups, &job),
                   "sketch");
         }
-        int rc = fpm_sketch_run(job, nullptr);
-        populate.join();
-        if (rc == FPM_OK) rc = fpm_sketch_fetch(job, out.data(), cnt.data());
-        // -M: the heap's multiplicities (Sketch.cpp:584-596)
         auto multp = std::make_shared<std::vector<uint32_t>>();
         std::vector<uint32_t> &mult = *multp;
-        if (rc == FPM_OK && parameters.counts) {
+        int rc;
+        if (parameters.reads) {
+            // MinHashHeap with minCov (Sketch.cpp:1308): reads mode implies the counts
+            rc = fpm_sketch_job_set_min_copies(job, parameters.minCov);
+            if (rc == FPM_OK) rc = fpm_sketch_reads_run(job, nullptr);
+            populate.join();
             mult.resize((size_t)nGroups * s);
-            rc = fpm_sketch_mult(job, nullptr, mult.data());
+            if (rc == FPM_OK)
+                rc = fpm_sketch_reads_fetch(job, out.data(), cnt.data(), mult.data(), nullptr);
+        } else {
+            rc = fpm_sketch_run(job, nullptr);
+            populate.join();
+            if (rc == FPM_OK) rc = fpm_sketch_fetch(job, out.data(), cnt.data());
+            // -M: the heap's multiplicities (Sketch.cpp:584-596)
+            if (rc == FPM_OK && parameters.counts) {
+                mult.resize((size_t)nGroups * s);
+                rc = fpm_sketch_mult(job, nullptr, mult.data());
+            }
         }
         fpm_sketch_job_free(job);
         check(rc, "sketch");
-        mark("device sketch (stage + run + fetch)");
+        mark(parameters.reads ? "device sketch, reads mode on one device (stage + run + fetch)"
+                              : "device sketch (stage + run + fetch)");
+        if (parameters.reads) {
+            // Reference::length of a read set (Sketch.cpp:1424-1434): -g, or
+            // MinHashHeap::estimateSetSize (MinHashHeap.h:45); an empty sketch ends the run
+            // (:1452-1464); the two estimates go to stderr (:1471-1474)
+            for (size_t f = 0; f < nF; f++)
+                for (size_t i = 0; i < fileRefs[f0 + f].size(); i++) {
+                    const uint32_t g = fileGroups[f][i];
+                    Reference &ref = fileRefs[f0 + f][i];
+                    double setSize = 0, coverage = 0;
+                    if (cnt[g]) {
+                        const uint64_t top = out.data()[(size_t)g * s + cnt[g] - 1];
+                        setSize = pow(2.0, parameters.use64 ? 64.0 : 32.0) * (double)cnt[g] / (double)top;
+                        uint64_t sum = 0;
+                        for (uint32_t j = 0; j < cnt[g]; j++) sum += mult[(size_t)g * s + j];
+                        coverage = (double)sum / cnt[g];
+                    }
+                    ref.length = parameters.genomeSize ? parameters.genomeSize : (uint64_t)setSize;
+                    if (ref.length == 0) {
+                        if (groupSkipped[g])
+                            std::cerr << "\nWARNING: All fasta records in input files were shorter "
+                                         "than the k-mer size (" << parameters.kmerSize << ")."
+                                      << std::endl;
+                        else
+                            std::cerr << "\nERROR: Did not find fasta records in \"input files\"."
+                                      << std::endl;
+                        fatalExit();
+                    }
+                    // (the estimate as Reference::length holds it, every digit: the
+                    // reference streams the double, which keeps six)
+                    std::cerr << "Estimated genome size: " << (uint64_t)setSize << std::endl;
+                    std::cerr << "Estimated coverage:    " << coverage << std::endl;
+                }
+        }
         if (stores) {
             // views into the fetched arrays (kept alive by the Sketch)
             for (size_t f = 0; f < nF; f++)
@@ -536,7 +627,9 @@ int Sketch::initFromFiles(const std::vector<std::string> &files, const Parameter
         std::vector<std::vector<Reference>> fileRefs(seqFiles.size());
         std::mutex storeMu;
         const int nDev = deviceCount();
-        const size_t nParts = std::min<size_t>((size_t)std::max(1, nDev), seqFiles.size());
+        // (reads mode: one device, whose timing line says so)
+        const size_t nParts = parameters.reads ? 1
+                              : std::min<size_t>((size_t)std::max(1, nDev), seqFiles.size());
         if (nParts <= 1) {
             fpm_ctx *ctx = device();
             phaseMark("device context");
@@ -570,6 +663,32 @@ int Sketch::initFromFiles(const std::vector<std::string> &files, const Parameter
         for (auto &r : it.refs) references.push_back(std::move(r));
     createIndex();
     return 0;
+}
+
+void Sketch::initFromReads(const std::vector<std::string> &files, const Parameters &p)
+{
+    parameters = p;
+    for (size_t f = 0; f < files.size(); f++)
+        if (files[f] == "-" && f > 1) {
+            std::cerr << "ERROR: '-' for stdin must be first input" << std::endl;
+            fatalExit();
+        }
+    std::vector<std::string> images(files.size());
+    for (size_t f = 0; f < files.size(); f++)
+        if (!loadSequenceFile(files[f], images[f])) {
+            std::cerr << "ERROR: could not open " << files[f] << std::endl;
+            fatalExit();
+        }
+    phaseMark("read input");
+    // counts of parts would have to be summed, not min-merged: one device
+    fpm_ctx *ctx = device();
+    phaseMark("device context");
+    std::vector<std::vector<Reference>> fileRefs(files.size());
+    std::mutex storeMu;
+    sketchFiles(ctx, parameters, files, images, 0, files.size(), fileRefs, true,
+                rowViews ? &rowStores : nullptr, &storeMu, true);
+    references = std::move(fileRefs[0]);
+    createIndex();
 }
 
 void Sketch::initFromFingerprints(const std::vector<std::string> &files, const Parameters &p)

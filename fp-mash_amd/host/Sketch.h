@@ -30,7 +30,9 @@ struct Parameters {
     uint64_t windowSize = 0;
     bool concatenated = false;
     bool noncanonical = false;
-    bool reads = false;
+    bool reads = false;        // -r / -m / -g: MinHashHeap with minCov, length = set-size estimate
+    uint32_t minCov = 1;       // -m: copies of a k-mer needed to enter the sketch
+    uint64_t genomeSize = 0;   // -g: Reference::length of a read set (0: the estimate)
     bool counts = false;
     bool fingerprint = false;
 };
@@ -60,6 +62,9 @@ public:
     // files are sketched on the GPU (one sketch per file, or per record with -i).
     int initFromFiles(const std::vector<std::string> &files, const Parameters &p,
                       int verbosity = 0, bool enforceParameters = false, bool contain = false);
+    // Sketch::initFromReads (Sketch.cpp:203-210): ONE sketch of all the files' records, taken
+    // round-robin across the files (sketchFile, :1352-1422), on the first device
+    void initFromReads(const std::vector<std::string> &files, const Parameters &p);
     // Sketch::initFromFingerprints (Sketch.cpp:56-151)
     void initFromFingerprints(const std::vector<std::string> &files, const Parameters &p);
     // Sketch::initParametersFromCapnp (Sketch.cpp:401-470); returns reference count

@@ -169,6 +169,42 @@ int fpm_sketch_fetch(fpm_sketch_job *job, uint64_t *out_hashes, uint32_t *out_co
  * counts32 that sketch -M writes (Sketch.cpp:584-596).  After run() on the same stream;
  * out_mult: n_groups x sketch_size u32, row g's first out_count[g] entries in hash order. */
 int fpm_sketch_mult(fpm_sketch_job *job, void *stream, uint32_t *out_mult);
+/* ---- reads mode (sketch -r / -m N) ----
+ * MinHashHeap::tryInsert with multiplicityMinimum = min_copies and no Bloom filter
+ * (MinHashHeap.cpp:68-146), as sketchFile drives it for a read set (Sketch.cpp:1299-1488, the
+ * reads branches at :1308, :1403, :1424-1434, :1471-1480): only hashes seen at least
+ * min_copies times enter the sketch.  The heap's threshold only falls, so sketch g is the
+ * sketch_size smallest hashes with >= min_copies occurrences in group g, each with its full
+ * number of occurrences; only the maximum of a full sketch stops counting once the heap holds
+ * the final set (`hash < top` fails at :73), i.e. after the last of the final hashes'
+ * min_copies-th occurrences in stream order.
+ * set_min_copies: on a staged job (fpm_sketch_stage / fpm_sketch_stage_seq), before
+ * reads_run; 0 is FPM_EINVAL; the default 1 is sketch -r without -m.
+ * reads_run: in place of fpm_sketch_run (which it calls; the job's plain output is then
+ * unspecified).  It widens the exact bottom-s' sketch (s' > s) until every group holds s
+ * qualifying hashes or all of its hashes, reading one flag per group per round, so it
+ * synchronises `stream`.  One device: counts of parts would have to be summed, not merged.
+ * reads_fetch: row g's hashes (stride sketch_size), out_count[g] of them, their counts (the
+ * counts32 of the .msh, Sketch.cpp:584-596; reads mode implies them,
+ * sketchParameterSetup.cpp:56-59) and MinHashHeap::estimateSetSize (MinHashHeap.h:45: 2^64, or
+ * 2^32 for u32 hashes, x count / maximum, in double, truncated; 0 for an empty sketch), the
+ * Reference::length of a read set without -g (Sketch.cpp:1424-1434).  Any output may be NULL.
+ * With min_copies 1 hashes and counts are those of fpm_sketch_run + fpm_sketch_mult.
+ * Device memory per round: the wide job's rows ((groups + tiles of the open groups) x s' x
+ * 8 B, s' = 8 s, then x 4 per round up to the open groups' window count) and (4 + 8 min_copies)
+ * B per group x s' entry; FPM_ENOMEM / FPM_EHIP when the device cannot hold them.
+ * reads_rounds: widening rounds of the last reads_run (-1 before any; a test hook, the result
+ * does not depend on it) and, when group_round is given, the round that completed each group. */
+int fpm_sketch_job_set_min_copies(fpm_sketch_job *job, uint32_t min_copies);
+int fpm_sketch_reads_run(fpm_sketch_job *job, void *stream);
+int fpm_sketch_reads_fetch(fpm_sketch_job *job, uint64_t *out_hashes, uint32_t *out_count,
+                           uint32_t *out_mult, uint64_t *out_estimate);
+int fpm_sketch_job_reads_rounds(fpm_sketch_job *job, int32_t *n_rounds, uint32_t *group_round);
+/* Long groups whose wide sketch in the last round of the last reads_run took the sampled
+ * long-group path of fpm_sketch_run (a sample of their tiles bounds what every tile keeps), -1
+ * before any run: a test hook beside the MinHashHeap restatement (MinHashHeap.cpp:68-146), the
+ * result does not depend on it. */
+int fpm_sketch_job_reads_sampled(fpm_sketch_job *job, int32_t *n_sampled);
 /* bytes the run() kernels read + write by algorithm (for roofline accounting) */
 int fpm_sketch_job_info(fpm_sketch_job *job, uint64_t *seq_bytes, uint64_t *n_tiles,
                         uint64_t *n_kmers);
