@@ -672,10 +672,12 @@ static hipError_t merge_rows_c(const uint64_t *d_cand, const uint64_t *row_seg, 
                                uint64_t ref_stride, uint32_t n_ref, const uint64_t *d_qry,
                                const uint32_t *d_qry_len, uint64_t qry_stride, uint32_t S,
                                bool sym, C *d_numer, C *d_denom, uint32_t *d_cnum,
-                               uint32_t *d_cden, hipStream_t st, uint32_t q_lo)
+                               uint32_t *d_cden, hipStream_t st, uint32_t q_lo,
+                               uint32_t *rank_cap)
 {
     const dim3 g(xcd_grid(n_qry)), b(64 * kRankWaves);
     const uint64_t cap = std::max(ref_stride, qry_stride);
+    if (rank_cap) *rank_cap = cap <= 1024 ? 1024u : 2048u;
     if (cap <= 1024)
         hipLaunchKernelGGL((rank_rows_kernel<1024, C>), g, b, 0, st, d_cand, row_seg, n_qry, q_lo,
                            d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len, qry_stride, S,
@@ -693,16 +695,17 @@ hipError_t launch_merge_rows(const uint64_t *d_cand, const uint64_t *row_seg, ui
                              const uint64_t *d_ref, const uint32_t *d_ref_len, uint64_t ref_stride,
                              uint32_t n_ref, const uint64_t *d_qry, const uint32_t *d_qry_len,
                              uint64_t qry_stride, uint32_t S, bool sym, Counts cnt,
-                             uint32_t *d_cnum, uint32_t *d_cden, hipStream_t st, uint32_t q_lo)
+                             uint32_t *d_cnum, uint32_t *d_cden, hipStream_t st, uint32_t q_lo,
+                             uint32_t *rank_cap)
 {
     if (!n_qry) return hipSuccess;
     if (cnt.c16)
         return merge_rows_c(d_cand, row_seg, n_qry, d_ref, d_ref_len, ref_stride, n_ref, d_qry,
                             d_qry_len, qry_stride, S, sym, (uint16_t *)cnt.numer,
-                            (uint16_t *)cnt.denom, d_cnum, d_cden, st, q_lo);
+                            (uint16_t *)cnt.denom, d_cnum, d_cden, st, q_lo, rank_cap);
     return merge_rows_c(d_cand, row_seg, n_qry, d_ref, d_ref_len, ref_stride, n_ref, d_qry,
                         d_qry_len, qry_stride, S, sym, (uint32_t *)cnt.numer,
-                        (uint32_t *)cnt.denom, d_cnum, d_cden, st, q_lo);
+                        (uint32_t *)cnt.denom, d_cnum, d_cden, st, q_lo, rank_cap);
 }
 
 // ---- FP64 p-value (same algorithm as the oracle restatement)
@@ -1512,8 +1515,10 @@ template <typename C>
 static hipError_t compare_grid_c(const void *d_ref, const uint32_t *d_ref_len, uint64_t ref_stride,
                                  uint32_t n_ref, const void *d_qry, const uint32_t *d_qry_len,
                                  uint64_t qry_stride, uint32_t n_qry, uint32_t hash_bytes,
-                                 uint32_t sketch_size, C *d_numer, C *d_denom, hipStream_t st)
+                                 uint32_t sketch_size, C *d_numer, C *d_denom, hipStream_t st,
+                                 bool *took_lds)
 {
+    if (took_lds) *took_lds = false;
     if (n_ref == 0 || n_qry == 0) return hipSuccess;
     dim3 grid((n_ref + kTile - 1) / kTile, (n_qry + kTile - 1) / kTile);
     // LDS-staged walk when the tile's 32 lists of W = min(S, stride) entries fit
@@ -1527,6 +1532,7 @@ static hipError_t compare_grid_c(const void *d_ref, const uint32_t *d_ref_len, u
                                              : (const void *)compare_grid_lds_kernel<uint32_t, kBlk, C>;
             if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds) ==
                 hipSuccess) {
+                if (took_lds) *took_lds = true;
                 if (hash_bytes == 8)
                     hipLaunchKernelGGL((compare_grid_lds_kernel<uint64_t, kBlk, C>), grid, dim3(256), lds, st,
                                        (const uint64_t *)d_ref, d_ref_len, ref_stride, n_ref,
@@ -1560,15 +1566,15 @@ static hipError_t compare_grid_c(const void *d_ref, const uint32_t *d_ref_len, u
 hipError_t launch_compare_grid(const void *d_ref, const uint32_t *d_ref_len, uint64_t ref_stride,
                                uint32_t n_ref, const void *d_qry, const uint32_t *d_qry_len,
                                uint64_t qry_stride, uint32_t n_qry, uint32_t hash_bytes,
-                               uint32_t sketch_size, Counts cnt, hipStream_t st)
+                               uint32_t sketch_size, Counts cnt, hipStream_t st, bool *lds)
 {
     if (cnt.c16)
         return compare_grid_c(d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len, qry_stride,
                               n_qry, hash_bytes, sketch_size, (uint16_t *)cnt.numer,
-                              (uint16_t *)cnt.denom, st);
+                              (uint16_t *)cnt.denom, st, lds);
     return compare_grid_c(d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len, qry_stride, n_qry,
                           hash_bytes, sketch_size, (uint32_t *)cnt.numer, (uint32_t *)cnt.denom,
-                          st);
+                          st, lds);
 }
 
 // ---- Dense walk of u32 lists on 16-bit rank images (the -fp shape: C3).

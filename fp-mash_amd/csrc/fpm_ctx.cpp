@@ -504,6 +504,13 @@ int fpm_ctx_last_dist_stats(fpm_ctx *ctx, int *sparse, uint64_t *events, uint64_
     return FPM_OK;
 }
 
+int fpm_ctx_last_dist_kernel(fpm_ctx *ctx, int *kernel)
+{
+    if (!ctx || !kernel) return fail(FPM_EINVAL, "null argument");
+    *kernel = ctx->last_kernel;
+    return FPM_OK;
+}
+
 int fpm_ctx_index_rebuilds(fpm_ctx *ctx, uint64_t *count)
 {
     if (!ctx || !count) return fail(FPM_EINVAL, "null argument");

@@ -541,10 +541,14 @@ static int index_phase(Compare &c, SparsePlan &p)
 static hipError_t rank_candidates(const Compare &c, const void *cand, const void *row_seg,
                                   bool sym, uint32_t *cnum, uint32_t *cden)
 {
-    return launch_merge_rows((const uint64_t *)cand, (const uint64_t *)row_seg, c.Q.n,
-                             (const uint64_t *)c.R.rows, c.R.len, c.R.stride, c.R.n,
-                             (const uint64_t *)c.Q.rows, c.Q.len, c.Q.stride, c.S, sym, c.cnt,
-                             cnum, cden, c.st);
+    uint32_t rank_cap = 0;
+    const hipError_t e =
+        launch_merge_rows((const uint64_t *)cand, (const uint64_t *)row_seg, c.Q.n,
+                          (const uint64_t *)c.R.rows, c.R.len, c.R.stride, c.R.n,
+                          (const uint64_t *)c.Q.rows, c.Q.len, c.Q.stride, c.S, sym, c.cnt, cnum,
+                          cden, c.st, 0, &rank_cap);
+    c.ctx->last_kernel = rank_cap == 1024 ? FPM_DK_CAND_RANK_1024 : FPM_DK_CAND_RANK_2048;
+    return e;
 }
 
 // Candidate phase: the probe (unless speculated), the candidate compare (rank kernel, or the
@@ -638,10 +642,12 @@ static int candidate_phase(Compare &c, SparsePlan &p, bool rows_merge, uint64_t 
         TimedLaunch tl(ctx, FPM_K_COMPARE, st);
         if (rows_merge)
             HIP_TRY(rank_candidates(c, cand, row_seg, sym, cnum, cden));
-        else
+        else {
             HIP_TRY(launch_walk_candidates((const uint64_t *)cand, p.n_cand(), cap, R.rows, R.len,
                                            R.stride, R.n, Q.rows, Q.len, Q.stride, c.hash_bytes,
                                            c.S, c.cnt, p.rec_r, p.rec_q, st));
+            ctx->last_kernel = FPM_DK_CAND_WALK;
+        }
         tl.done();
     }
     if (defer_fill)
@@ -702,12 +708,16 @@ static int dense_phase(Compare &c)
         HIP_TRY(scratch(ctx, kSlotImg, bb, &bimg));
     }
     TimedLaunch tl(ctx, FPM_K_COMPARE, st);
-    if (img)
+    if (img) {
         HIP_TRY(launch_compare_grid_img(R.rows, R.len, R.stride, R.n, Q.rows, Q.len, Q.stride,
                                         Q.n, c.S, ublk, bimg, c.cnt, st));
-    else
+        ctx->last_kernel = FPM_DK_GRID_IMG;
+    } else {
+        bool lds = false;
         HIP_TRY(launch_compare_grid(R.rows, R.len, R.stride, R.n, Q.rows, Q.len, Q.stride, Q.n,
-                                    c.hash_bytes, c.S, c.cnt, st));
+                                    c.hash_bytes, c.S, c.cnt, st, &lds));
+        ctx->last_kernel = lds ? FPM_DK_GRID_LDS : FPM_DK_GRID_GLOBAL;
+    }
     tl.done();
     return FPM_OK;
 }
@@ -731,6 +741,7 @@ static int compare_impl(fpm_ctx *ctx, const RowSet &R, const RowSet &Q, uint32_t
     }
     const uint64_t n_pairs = (uint64_t)R.n * Q.n;
     ctx->last_sparse = 0;
+    ctx->last_kernel = FPM_DK_NONE;
     ctx->last_events = 0;
     ctx->last_cand = 0;
     if (n_pairs == 0) {

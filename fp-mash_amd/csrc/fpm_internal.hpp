@@ -170,6 +170,7 @@ struct fpm_ctx {
     int fill_counts = -1;      // the side-stream fill also writes the numer / denom defaults
                                // (-1: for grids of >= 2^28 pairs; FPM_FILL_COUNTS=0/1 forces)
     int last_sparse = 0;
+    int last_kernel = FPM_DK_NONE;   // fpm_ctx_last_dist_kernel
     uint64_t last_events = 0, last_cand = 0;
     const unsigned long long *last_cand_dev = nullptr;   // the last sparse call's counter
     hipStream_t last_cand_stream = nullptr;

@@ -134,7 +134,9 @@ hipError_t launch_fp_hash(const uint64_t *d_vals, const uint64_t *d_line_off, ui
 hipError_t launch_compare_grid(const void *d_ref, const uint32_t *d_ref_len, uint64_t ref_stride,
                                uint32_t n_ref, const void *d_qry, const uint32_t *d_qry_len,
                                uint64_t qry_stride, uint32_t n_qry, uint32_t hash_bytes,
-                               uint32_t sketch_size, Counts cnt, hipStream_t st);
+                               uint32_t sketch_size, Counts cnt, hipStream_t st,
+                               bool *lds = nullptr);
+// (*lds: whether the LDS-staged walk was launched, else the walk from global memory)
 
 // dense walk of u32 lists on 16-bit rank images (dist.hip), for 64 <= min(S, stride) <= 1023;
 // scratch from compare_grid_img_scratch
@@ -260,9 +262,11 @@ hipError_t launch_merge_rows(const uint64_t *d_cand, const uint64_t *row_seg, ui
                              const uint64_t *d_ref, const uint32_t *d_ref_len, uint64_t ref_stride,
                              uint32_t n_ref, const uint64_t *d_qry, const uint32_t *d_qry_len,
                              uint64_t qry_stride, uint32_t S, bool sym, Counts cnt,
-                             uint32_t *d_cnum, uint32_t *d_cden, hipStream_t st, uint32_t q_lo = 0);
+                             uint32_t *d_cnum, uint32_t *d_cden, hipStream_t st, uint32_t q_lo = 0,
+                             uint32_t *rank_cap = nullptr);
 // (d_cnum, d_cden non-null: results go to candidate slot c instead of the grid cells;
-// q_lo, n_qry: the query rows [q_lo, q_lo + n_qry), whose probe has run)
+// q_lo, n_qry: the query rows [q_lo, q_lo + n_qry), whose probe has run;
+// *rank_cap: the CAP of the rank_rows_kernel instance launched, 1024 or 2048)
 
 // -fp CFL text: newline index, then one lane per line (fingerprint.hip)
 uint32_t text_blocks(uint64_t len);

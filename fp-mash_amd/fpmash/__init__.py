@@ -32,6 +32,12 @@ KERNEL_NAMES = {K_SKETCH: "sketch_tiles_kernel", K_MERGE: "merge_kernel",
 DIST_AUTO, DIST_DENSE, DIST_SPARSE = 0, 1, 2
 # fpm_ctx_last_dist_stats path codes
 DIST_PATHS = ["dense walk", "bucket index + literal walk", "bucket index + bucketed rank"]
+# fpm_ctx_last_dist_kernel codes (FPM_DK_*)
+(DK_NONE, DK_GRID_GLOBAL, DK_GRID_LDS, DK_GRID_IMG, DK_CAND_WALK, DK_CAND_RANK_1024,
+ DK_CAND_RANK_2048) = range(7)
+DIST_KERNELS = ["none", "compare_grid_kernel", "compare_grid_lds_kernel",
+                "compare_grid_img_kernel", "walk_cand_kernel", "rank_rows_kernel<1024>",
+                "rank_rows_kernel<2048>"]
 
 ALPHABET_NUCLEOTIDE = "ACGT"                     # Sketch.h alphabetNucleotide
 ALPHABET_PROTEIN = "ACDEFGHIKLMNPQRSTVWY"         # Sketch.h alphabetProtein
@@ -70,6 +76,7 @@ SYMBOLS = [
     ("fpm_ctx_kernel_time", C.c_int, [vp, C.c_int, f64p, u64p]),
     ("fpm_ctx_set_dist_mode", C.c_int, [vp, C.c_int]),
     ("fpm_ctx_last_dist_stats", C.c_int, [vp, C.POINTER(C.c_int), u64p, u64p]),
+    ("fpm_ctx_last_dist_kernel", C.c_int, [vp, C.POINTER(C.c_int)]),
     ("fpm_sketch_batch", C.c_int, [vp, vp, C.c_char_p, u64p, C.c_uint32, u32p, C.c_uint32,
                                    u64p, u32p]),
     ("fpm_sketch_stage", C.c_int, [vp, vp, C.c_char_p, u64p, C.c_uint32, u32p, C.c_uint32,
@@ -609,6 +616,13 @@ class Context:
         sp, ev, ca = C.c_int(), C.c_uint64(), C.c_uint64()
         _check(lib().fpm_ctx_last_dist_stats(self.h, C.byref(sp), C.byref(ev), C.byref(ca)))
         return {"sparse": sp.value, "events": ev.value, "candidates": ca.value}
+
+    def last_dist_kernel(self):
+        """fpm_ctx_last_dist_kernel: the compare kernel of the last compare (a DK_* code; a
+        test hook)"""
+        k = C.c_int()
+        _check(lib().fpm_ctx_last_dist_kernel(self.h, C.byref(k)))
+        return k.value
 
     # --- sketch -----------------------------------------------------------
     def sketch(self, params, seqs, groups=None, n_groups=None, counts=False, min_copies=1):

@@ -133,6 +133,20 @@ int fpm_ctx_set_dist_mode(fpm_ctx *ctx, int mode);
 /* statistics of the last compare: path (0 dense walk, 1 index + literal walk of the
  * candidates, 2 index + sorted-set merge of the candidates), posting events, candidates */
 int fpm_ctx_last_dist_stats(fpm_ctx *ctx, int *sparse, uint64_t *events, uint64_t *candidates);
+/* The compare kernel the last compare launched (a test hook, the result does not depend on
+ * it): the dense grid walk from global memory, staged in LDS or on the u32 lists' 16-bit rank
+ * images; or, on the index path, the literal walk of the candidates or their rank kernel with
+ * 1024 / 2048 staged query hashes.  NONE: no pairs.  When a transposed grid was computed by a
+ * swapped call (fpm_refset_dist_mirror_dev*), the kernel of that call.  Decided on the host:
+ * no synchronisation. */
+#define FPM_DK_NONE 0
+#define FPM_DK_GRID_GLOBAL 1
+#define FPM_DK_GRID_LDS 2
+#define FPM_DK_GRID_IMG 3
+#define FPM_DK_CAND_WALK 4
+#define FPM_DK_CAND_RANK_1024 5
+#define FPM_DK_CAND_RANK_2048 6
+int fpm_ctx_last_dist_kernel(fpm_ctx *ctx, int *kernel);
 
 /* ---- k-mer sketch ------------------------------------------------------------
  * Replaces addMinHashes (Sketch.cpp:664-735) + MinHashHeap::tryInsert

@@ -314,6 +314,45 @@ def test_c1_two_files_sketch_then_dist(tmp_path, oracle):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("k", [16, 12])
+def test_sketch_then_dist_u32_hashes(tmp_path, oracle, k):
+    """`sketch -i -k 16 -s 400` (and -k 12): 4^k <= 2^32, so the .msh holds sorted u32 hashes
+    and `dist` compares them with hash_bytes = 4 (CommandDistance.cpp:333-334).  The .msh
+    against itself and against a second file: the hashes equal the oracle's u32 sketches and
+    every dist line equals the oracle's grid on them, as in
+    test_c1_two_files_sketch_then_dist."""
+    from fpmash import datagen
+    seqs = datagen.family_dna(4, 6, 1500, sub_rate=(0.0, 0.08), seed=40 + k)
+    seqs.insert(4, seqs[2][:200])                       # fewer k-mers than s
+    ids = datagen.lyn2vec_ids(len(seqs), seed=k)
+    split = {"a": list(range(0, len(seqs), 2)) + [1], "b": list(range(3, len(seqs), 2))}
+    sets = {}
+    for f, idx in split.items():
+        (tmp_path / f"{f}.fa").write_bytes(datagen.fasta_bytes([seqs[i] for i in idx],
+                                                               [ids[i] for i in idx]))
+        run(["sketch", "-i", "-k", str(k), "-s", "400", "-o", f, f"{f}.fa"], cwd=tmp_path)
+        got = mshfmt.read_msh(str(tmp_path / f"{f}.msh"))
+        exp_h = [h.astype(np.uint32) for h in oracle.sketch_batch(
+            oracle.params(k=k, s=400), [seqs[i] for i in idx])]
+        assert got["kmer"] == k and len(got["references"]) == len(idx)
+        for r, i, h in zip(got["references"], idx, exp_h):
+            assert r["name"] == b"T00000" + ids[i].encode()
+            assert r["hashes64"] is None or len(r["hashes64"]) == 0
+            assert np.array_equal(r["hashes32"], h)
+        assert any(len(h) < 400 for h in exp_h) == (f == "a")
+        sets[f] = ([r["name"].decode() for r in got["references"]],
+                   [len(seqs[i]) for i in idx], exp_h)
+    for q in ("a", "b"):
+        out = run(["dist", "a.msh", f"{q}.msh"], cwd=tmp_path).stdout.decode().splitlines()
+        (rn, rl, rh), (qn, ql, qh) = sets["a"], sets[q]
+        nu, de, di, pv = oracle.dist_grid(rh, rl, qh, ql, 400, k, 4.0 ** k, use64=False)
+        assert (nu > 0).any() and (nu == 0).any()
+        exp = [f"{rn[r]}\t{qn[x]}\t{di[o]:g}\t{pv[o]:g}\t{nu[o]}/{de[o]}"
+               for x in range(len(qn)) for r in range(len(rn)) for o in [x * len(rn) + r]]
+        assert out == exp
+
+
+@pytest.mark.gpu
 def test_dist_genomes_golden():
     """mash/test/ref/genomes.dist: distance, p-value and shared-hash fields."""
     lines = open(os.path.join(GOLDEN, "genomes.dist")).read().splitlines()
