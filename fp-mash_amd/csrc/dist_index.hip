@@ -6,8 +6,9 @@
 // for sorted sketches and for the unsorted -fp lists alike.  So only pairs that
 // share at least one hash ("candidates") need the walk.  The candidates come from
 // an index over the reference lists:
-//   1. bucket index: every ref hash becomes one packed u32 entry (key fingerprint << rbits
-//      | ref id) in a bucket array grouped by the key's bucket (its value scaled to the
+//   1. bucket index: every ref hash becomes one packed u32 entry (flag << 31 | key fingerprint
+//      << rbits | ref id; the flag: the hash sits inside its row's visited prefix, see 2) in a
+//      bucket array grouped by the key's bucket (its value scaled to the
 //      indexed range [0, kmax]: bottom-s sketches only use the low part of the hash range),
 //      with a directory dir[b] = first entry of bucket b.  Hashes are uniform (MurmurHash3),
 //      so this is a two-level counting sort with no global atomics: per-tile LDS histograms
@@ -17,7 +18,13 @@
 //   2. one workgroup per query row looks up the bucket of each of its hashes; each wave
 //      flattens the buckets of 64 hashes into one event range and reads it coalesced,
 //      ORing the ref id of every entry whose fingerprint matches into a row bitmap in LDS
-//      (no global atomics), then appends the row's candidate pairs;
+//      (no global atomics), then appends the row's candidate pairs.  One sorted set against
+//      itself probes only the first half of each row: a pair's smallest shared value is
+//      counted iff its positions i0 + p0 < S, so it lies in the first ceil(S / 2) positions
+//      of one of the two rows (rows shorter than S are visited whole: their denom may
+//      differ).  The entry flags tell a row whether the pair's other row sees the event too,
+//      and each pair is taken once: by its parity owner if that row sees it, else by the
+//      other (the rule and its proof: probe_rows_kernel);
 //   3. the rank / literal-walk kernels (dist.hip) run on the candidates only; every other
 //      pair keeps the (0, min(S, la+lb)) written in step 2.
 // Work is O(N*S + sum_v n_v^2 + candidates*S) instead of O(pairs*S).  When the
@@ -67,13 +74,22 @@ __device__ __forceinline__ uint32_t bucket_of(uint64_t K, const IdxGeom &g, uint
     const uint64_t top = (1ULL << g.nbits) - 1;
     return (uint32_t)(b < top ? b : top);
 }
-// u32 entry = fingerprint << rbits | ref id, fingerprint = the top fbits of the low half of
-// K * mult (for a power-of-two range: the key bits just below the bucket bits).  A fingerprint
-// collision only adds a candidate pair that shares no hash; the exact candidate kernels then
-// produce the same (0, min(S, la+lb)) the probe already wrote.
+// u32 entry = flag << 31 | fingerprint << rbits | ref id, fingerprint = the top fbits (31 -
+// rbits) of the low half of K * mult (for a power-of-two range: the key bits just below the
+// bucket bits).  A fingerprint collision only adds a candidate pair that shares no hash; the
+// exact candidate kernels then produce the same (0, min(S, la+lb)) the probe already wrote.
+// The flag (entry_flag) is no part of the fingerprint: the probe compares bits [rbits, 31).
+constexpr uint32_t kEntryFlag = 1u << 31;
 __device__ __forceinline__ uint32_t key_fp(uint64_t K, const IdxGeom &g, uint64_t mult)
 {
     return (uint32_t)((K * mult) >> (64 - g.fbits));
+}
+// the entry at position pos of a row of len entries is inside its row's visited prefix (the
+// half probe, step 2): always without a cut, in a row shorter than the cut's S, else in the
+// first ceil(S / 2) positions
+__device__ __forceinline__ uint32_t entry_flag(uint32_t pos, uint32_t len, const IdxGeom &g)
+{
+    return g.cut == 0 || len < g.cut || pos < (g.cut + 1) / 2 ? kEntryFlag : 0u;
 }
 
 // Tiles of g.tile (<= kIdxTile) matrix cells, 1024 threads each (16 cells per thread, 4 loads in
@@ -190,11 +206,13 @@ __global__ __launch_bounds__(kIdxThreads) void idx_part_hist_kernel(
 
 // ---- 1b. level-1 scatter into partitions.  One u64 per entry: the key bits below the
 // partition bits that level 2 needs (l2 sub-bucket bits, then the fbits fingerprint) over
-// the ref id, i.e. (sub << 32) | final u32 entry, since fbits + rbits = 32.
-__device__ __forceinline__ uint64_t pack_l1(uint64_t K, uint32_t r, const IdxGeom &g, uint64_t mult)
+// the ref id, i.e. (sub << 32) | final u32 entry (1 + fbits + rbits = 32: on top the cell's
+// flag, entry_flag of its position and its row's length).
+__device__ __forceinline__ uint64_t pack_l1(uint64_t K, uint32_t r, uint32_t flag,
+                                            const IdxGeom &g, uint64_t mult)
 {
     const uint32_t sub = bucket_of(K, g, mult) & ((1u << g.l2) - 1);
-    return ((uint64_t)sub << 32) | ((uint64_t)key_fp(K, g, mult) << g.rbits) | r;
+    return ((uint64_t)sub << 32) | flag | ((uint64_t)key_fp(K, g, mult) << g.rbits) | r;
 }
 
 // The tile's entries are first grouped by partition in LDS (a counting sort on the hist
@@ -237,14 +255,16 @@ __global__ __launch_bounds__(kIdxThreads) void idx_part_scatter_kernel(
     const uint32_t n = min(n_ref * stride, e0 + g.tile);     // this tile's cells end here
     for (uint32_t c0 = 0; c0 < g.tile; c0 += kIdxU * kIdxThreads) {
         uint64_t K[kIdxU];
-        uint32_t rr[kIdxU];
+        uint32_t rr[kIdxU], fl[kIdxU];
         bool v[kIdxU];
 #pragma unroll
         for (int u = 0; u < kIdxU; u++) {
             const uint32_t e = e0 + c0 + u * kIdxThreads + threadIdx.x;
             const uint32_t r = row_of(e, stride, magic), i = e - r * stride;
-            v[u] = e < n && i < ref_len[min(r, n_ref - 1)];
+            const uint32_t la = ref_len[min(r, n_ref - 1)];
+            v[u] = e < n && i < la;
             rr[u] = r;
+            fl[u] = entry_flag(i, la, g);
             K[u] = v[u] ? norm_key(load_key(ref, hash_bytes, e), hash_bytes) : 0;
         }
 #pragma unroll
@@ -252,7 +272,7 @@ __global__ __launch_bounds__(kIdxThreads) void idx_part_scatter_kernel(
             if (v[u]) {
                 const uint32_t part = bucket_of(K[u], g, mult) >> g.l2;
                 const uint32_t pos = atomicAdd(&lcur[part], 1u);
-                stage[pos] = ((uint64_t)part << kPartShift) | pack_l1(K[u], rr[u], g, mult);
+                stage[pos] = ((uint64_t)part << kPartShift) | pack_l1(K[u], rr[u], fl[u], g, mult);
             }
     }
     __syncthreads();
@@ -317,6 +337,7 @@ __global__ __launch_bounds__(kIdxThreads) void idx_part_scatter1_kernel(
     __syncthreads();                                          // lcur cleared, first[] written
     bool uns = false;
     uint32_t vbits = 0;                                       // bit u: cell u is a list entry
+    uint32_t fbits = 0;                                       // bit u: and carries the entry flag
     // pass 1: the tile's partition counts (and the sortedness flags)
 #pragma unroll
     for (int u = 0; u < kPer; u++) {
@@ -329,6 +350,7 @@ __global__ __launch_bounds__(kIdxThreads) void idx_part_scatter1_kernel(
         uns |= nx && !(key[u] < nk);
         if (v) {
             vbits |= 1u << u;
+            fbits |= entry_flag(i, la[u], g) ? 1u << u : 0u;
             atomicAdd(&lcur[bucket_of(norm_key(key[u], hash_bytes), g, mult) >> g.l2], 1u);
         }
     }
@@ -358,7 +380,8 @@ __global__ __launch_bounds__(kIdxThreads) void idx_part_scatter1_kernel(
             const uint64_t K = norm_key(key[u], hash_bytes);
             const uint32_t part = bucket_of(K, g, mult) >> g.l2;
             const uint32_t pos = atomicAdd(&lcur[part], 1u);
-            stage[pos] = ((uint64_t)part << kPartShift) | pack_l1(K, row_of(e, stride, magic), g, mult);
+            stage[pos] = ((uint64_t)part << kPartShift) |
+                         pack_l1(K, row_of(e, stride, magic), fbits >> u & 1u ? kEntryFlag : 0u, g, mult);
         }
     __syncthreads();
     const uint32_t total = lcur[kParts - 1];
@@ -383,7 +406,8 @@ __global__ __launch_bounds__(kIdxThreads) void idx_part_scatter1_kernel(
 // of counters) and the entries below it, reads the slice again and scatters its range's
 // entries through the LDS, so every entry is written coalesced.  A range past `cap` scatters
 // straight to `entries` in 4-B pieces (the round-4 form for C4: tent read twice, entries
-// written ~6.5x their bytes: 0.64 ms).
+// written ~6.5x their bytes: 0.64 ms).  The sort key is the sub-bucket field (bits 32 up, under
+// sbmask); the low u32 is copied whole, the entry's flag in bit 31 with it.
 constexpr int kBucketThreads = 1024;
 static_assert(kBucketThreads == (int)kParts, "one-pass build: one partition fill per thread");
 static_assert(kParts % 8 == 0, "split partitions map to one XCD");
@@ -689,7 +713,26 @@ __global__ void sum64_kernel(unsigned long long *events)
 // a per-wave byte map filled by the lanes for 1024-event windows (one LDS read per event).
 // 8 waves per SIMD (without the attribute: 7): the kernel waits on its
 // event loads most of the time, and at 105 SGPRs the compiler's own allocation left 7
-template <typename C>
+//
+// HALF (one sorted set against itself, rank kernel, index cut at this S: g.cut == S): the row
+// probes only its visited prefix, positions [0, H_q) with H_q = lq >= S ? ceil(S / 2) : lq.
+// Why that finds every pair whose cell differs from the defaults: a shared value at
+// position i of row q and p of row r has union rank i + p - (shared values below it) and is
+// counted iff that is < S; for the pair's smallest shared value it is i0 + p0, so numer > 0
+// implies min(i0, p0) < ceil(S / 2), and denom differs from min(S, la + lb) only when both
+// rows are shorter than S (visited whole).  So such a pair has an event inside the visited
+// prefix of at least one of its rows.  Each entry's flag says whether its position is inside
+// its own row's visited prefix, and the row keeps two bits per ref: seen (a probed hash hit
+// an entry of r) and both (such an entry had its flag set: r's own probe sees that event
+// too).  With M the pair-parity owner mask (word_mask) the row takes (seen & M) | (seen &
+// ~both & ~M): the owner takes the pair whenever it sees it, the other row only when it sees
+// it and knows the owner cannot.  Exactly once, fingerprint collisions included: events pair
+// entries of equal (bucket, fingerprint), a class key monotone in the hash.  If the owner q
+// saw r through class c and r took the pair too, r saw q only through classes whose members
+// in q are unvisited, say c'; q holds c inside its prefix and c' outside, so c <= c'; r holds
+// c' inside and c outside, so c' <= c; then c = c' has a visited member on both sides, which
+// sets both.
+template <typename C, bool HALF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8)))
 void probe_rows_kernel(
     const void *__restrict__ qry, const uint32_t *__restrict__ qry_len, uint64_t stride,
@@ -732,15 +775,21 @@ void probe_rows_kernel(
         return (odd & gt) | (~odd & ~gt);
     };
     const uint32_t nwords = (r1 - r0 + 31) / 32;
-    for (uint32_t w = threadIdx.x; w < nwords; w += 256) rowbits[w] = 0;
+    // ref i of the chunk: bit i of rowbits (seen); HALF: its both bit at both0 + i, in a
+    // second bitmap of nwords words behind the first
+    const uint32_t both0 = nwords * 32;
+    for (uint32_t w = threadIdx.x; w < nwords * (HALF ? 2 : 1); w += 256) rowbits[w] = 0;
     __syncthreads();
     // lq: the row's list length (the defaults); lit: the hashes probed, which differ from lq
-    // when the probed rows are the record rows of unsorted lists (record_rows_kernel)
+    // when the probed rows are the record rows of unsorted lists (record_rows_kernel), and
+    // with HALF: the visited prefix.  (The order test and the event count below are the
+    // skip-count path's, a resident set against another block: never HALF, which the launcher
+    // enforces.  The defaults always cover the whole row.)
     const uint32_t lq = qry_len[q];
-    const uint32_t lit = qry_it_len ? qry_it_len[q] : lq;
+    const uint32_t lit = HALF ? (lq >= S ? (S + 1) / 2 : lq) : qry_it_len ? qry_it_len[q] : lq;
     // one set against itself: row q's own entry sits in the bucket of each of its hashes,
     // so a bucket of one entry holds only that entry.  Such buckets (the unique hashes, most
-    // of a sketch) are not read; the pair (q, q) they would mark is set here.
+    // of a sketch) are not read; the pair (q, q) they would mark is set here (seen).
     if (self_set && threadIdx.x == 0 && lq > 0 && q >= r0 && q < r1)
         atomicOr(&rowbits[(q - r0) >> 5], 1u << ((q - r0) & 31));
     const uint64_t rowoff = (uint64_t)q * stride;
@@ -757,7 +806,7 @@ void probe_rows_kernel(
         for (int bi = 0; bi < kB; bi++) {
             const uint32_t j = jb + 256 * bi + lane;
             const uint64_t raw = j < lit ? load_key(qry, hash_bytes, rowoff + j) : 0;
-            if (q_unsorted) {
+            if (!HALF && q_unsorted) {
                 // the next value of the row: the next lane's, or a load for the last lane
                 uint64_t nx = __shfl_down(raw, 1, 64);
                 if (lane == 63 && j + 1 < lit) nx = load_key(qry, hash_bytes, rowoff + j + 1);
@@ -816,21 +865,30 @@ void probe_rows_kernel(
                 // every lane, at word 0 when the event is not this row's), the rare atomics
                 // after the kU events: a branch per event cost 11 scalar instructions of exec
                 // mask handling each
+                // HALF: still one read per event.  A both bit is only ever set together with its
+                // seen bit, so an event of a flagged entry reads (and sets) the ref's both bit,
+                // at bit index both0 + ref, and any other event its seen bit
                 uint32_t wi[kU], need = 0;
 #pragma unroll
                 for (int u = 0; u < kU; u++) {
                     const uint32_t e = e0 + 64 * u;
                     const uint32_t r = en[u] & rmask;
-                    const bool hit = e < wn && (en[u] >> g.rbits) == (uint32_t)(tab[u] >> 32) &&
+                    const bool hit = e < wn &&
+                                     ((en[u] & ~kEntryFlag) >> g.rbits) == (uint32_t)(tab[u] >> 32) &&
                                      r >= r0 && r < r1;
                     wi[u] = hit ? r - r0 : 0u;
+                    if (HALF) wi[u] += hit && (en[u] & kEntryFlag) ? both0 : 0u;
                     const uint32_t word = rowbits[wi[u] >> 5];
                     need |= (hit && !(word & (1u << (wi[u] & 31)))) ? (1u << u) : 0u;
                 }
                 if (__any(need != 0)) {
 #pragma unroll
                     for (int u = 0; u < kU; u++)
-                        if (need >> u & 1u) atomicOr(&rowbits[wi[u] >> 5], 1u << (wi[u] & 31));
+                        if (need >> u & 1u) {
+                            atomicOr(&rowbits[wi[u] >> 5], 1u << (wi[u] & 31));
+                            if (HALF && wi[u] >= both0)
+                                atomicOr(&rowbits[(wi[u] - both0) >> 5], 1u << (wi[u] & 31));
+                        }
                 }
             }
             __builtin_amdgcn_wave_barrier();   // before the next window's owner map
@@ -838,13 +896,20 @@ void probe_rows_kernel(
         __builtin_amdgcn_wave_barrier();
       }
     }
-    if (q_unsorted && __any(uns) && lane == 0) atomicOr(q_unsorted, 1u);
-    if (events && blockIdx.y == 0 && lane == 0 && ev_w)
+    if (!HALF && q_unsorted && __any(uns) && lane == 0) atomicOr(q_unsorted, 1u);
+    if (!HALF && events && blockIdx.y == 0 && lane == 0 && ev_w)
         atomicAdd(&events[1 + (blockIdx.x & 63)], ev_w);
     __syncthreads();
     // candidates of this row: popcount per word -> block scan -> append
+    // the row's candidates among the refs of word w
+    auto taken = [&](uint32_t w) -> uint32_t {
+        const uint32_t m = word_mask(w);
+        if (!HALF) return rowbits[w] & m;
+        const uint32_t seen = rowbits[w], both = rowbits[nwords + w];
+        return (seen & m) | (seen & ~both & ~m);
+    };
     uint32_t mycnt = 0;
-    for (uint32_t w = threadIdx.x; w < nwords; w += 256) mycnt += __popc(rowbits[w] & word_mask(w));
+    for (uint32_t w = threadIdx.x; w < nwords; w += 256) mycnt += __popc(taken(w));
     uint32_t x = mycnt;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) { uint32_t y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
@@ -867,7 +932,7 @@ void probe_rows_kernel(
     uint64_t pos = row_base + wpre + x - mycnt;
     const uint64_t pair_row = (uint64_t)q * n_ref;
     for (uint32_t w = threadIdx.x; !dropped && w < nwords; w += 256) {
-        uint32_t b = rowbits[w] & word_mask(w);
+        uint32_t b = taken(w);
         const uint64_t bit0 = pair_row + r0 + (uint64_t)w * 32;
         while (b) {
             int t = __builtin_ctz(b);
@@ -1087,7 +1152,7 @@ hipError_t launch_exscan(const uint32_t *in, uint32_t *out, uint32_t *out2, uint
 static hipError_t dyn_lds_attr(int slot, const void *fn, int bytes)
 {
     constexpr int kMaxDev = 64;
-    static std::atomic<int> done[3][kMaxDev];
+    static std::atomic<int> done[5][kMaxDev];
     int dev = 0;
     if (hipError_t e = hipGetDevice(&dev)) return e;
     if (dev < 0 || dev >= kMaxDev) return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
@@ -1190,27 +1255,39 @@ hipError_t launch_probe_rows(const void *d_qry, const uint32_t *d_qry_len, uint6
                              unsigned long long *n_cand, uint64_t *row_seg,
                              const uint32_t *d_qry_it_len, uint32_t *q_unsorted,
                              unsigned long long *events, uint64_t cap, uint32_t *cand_over,
-                             hipStream_t st, uint32_t q_lo)
+                             hipStream_t st, uint32_t q_lo, bool half)
 {
     if (!n_qry || !n_ref) return hipSuccess;
+    // the half form is the symmetric probe's, over an index whose flags were cut at this S
+    // (and never the skip-count path's: no record rows, no order test, no event count)
+    if (half && (!sym || !self_set || g.cut != S || d_qry_it_len || q_unsorted || events))
+        return hipErrorInvalidValue;
     const uint32_t chunk = 1u << 19;   // refs per workgroup: 64 KiB of LDS bitmap
     const uint32_t nchunks = (n_ref + chunk - 1) / chunk;
     const uint32_t cref = nchunks == 1 ? n_ref : chunk;
-    const size_t lds = ((cref + 31) / 32) * 4;
+    // (half: the seen and both bitmaps, up to 128 KiB, past the default dynamic-LDS limit)
+    const size_t lds = ((cref + 31) / 32) * 4 * (half ? 2 : 1);
+    if (lds > 64 * 1024) {
+        const void *fn = cnt.c16 ? (const void *)probe_rows_kernel<uint16_t, true>
+                                 : (const void *)probe_rows_kernel<uint32_t, true>;
+        if (hipError_t e = dyn_lds_attr(cnt.c16 ? 3 : 4, fn, 128 * 1024)) return e;
+    }
     // vector default stores (4 cells): every row and chunk start 4-cell aligned, buffers
     // 16-B aligned
     const auto al = [](const void *p) { return ((uintptr_t)p & 15) == 0; };
     const uint32_t vec_defaults = n_ref % 4 == 0 && cref % 4 == 0 && al(d_ref_len) &&
                                   al(cnt.numer) && al(cnt.denom);
-#define FPM_PROBE(C)                                                                            \
-    hipLaunchKernelGGL(probe_rows_kernel<C>, dim3(xcd_grid(n_qry), nchunks), dim3(256), lds, st,  \
-                       d_qry, d_qry_len, stride, n_qry, q_lo, n_ref, hash_bytes, g, dir, entries, \
-                       cref,                                                                     \
+#define FPM_PROBE(C, H)                                                                         \
+    hipLaunchKernelGGL((probe_rows_kernel<C, H>), dim3(xcd_grid(n_qry), nchunks), dim3(256), lds, \
+                       st, d_qry, d_qry_len, stride, n_qry, q_lo, n_ref, hash_bytes, g, dir,     \
+                       entries, cref,                                                            \
                        d_ref_len, S, (uint32_t)sym, (uint32_t)defaults, vec_defaults,           \
                        (uint32_t)self_set, (C *)cnt.numer, (C *)cnt.denom, cand, n_cand, row_seg, \
                        d_qry_it_len, q_unsorted, events, cap, cand_over)
-    if (cnt.c16) FPM_PROBE(uint16_t);
-    else FPM_PROBE(uint32_t);
+    if (cnt.c16 && half) FPM_PROBE(uint16_t, true);
+    else if (cnt.c16) FPM_PROBE(uint16_t, false);
+    else if (half) FPM_PROBE(uint32_t, true);
+    else FPM_PROBE(uint32_t, false);
 #undef FPM_PROBE
     return hipGetLastError();
 }

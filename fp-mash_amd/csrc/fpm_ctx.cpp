@@ -309,6 +309,7 @@ int fpm_ctx_create(int device, fpm_ctx **out)
     fpm_ctx *ctx = new fpm_ctx();
     ctx->device = device;
     if (const char *v = getenv("FPM_FILL_COUNTS")) ctx->fill_counts = atoi(v) != 0 ? 1 : 0;
+    if (const char *v = getenv("FPM_PROBE_HALF")) ctx->probe_half = atoi(v) != 0;
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
@@ -508,6 +509,20 @@ int fpm_ctx_last_dist_kernel(fpm_ctx *ctx, int *kernel)
 {
     if (!ctx || !kernel) return fail(FPM_EINVAL, "null argument");
     *kernel = ctx->last_kernel;
+    return FPM_OK;
+}
+
+int fpm_ctx_set_probe_half(fpm_ctx *ctx, int on)
+{
+    if (!ctx) return fail(FPM_EINVAL, "null context");
+    ctx->probe_half = on != 0;
+    return FPM_OK;
+}
+
+int fpm_ctx_last_dist_probe(fpm_ctx *ctx, int *form)
+{
+    if (!ctx || !form) return fail(FPM_EINVAL, "null argument");
+    *form = ctx->last_probe;
     return FPM_OK;
 }
 

@@ -53,8 +53,8 @@ struct DistFinal {
 };
 
 // bucket index geometry for E entries over n_ref rows: ~2.4 entries per bucket (2^nbits >=
-// E/4, at most 2^24 buckets); entries are u32 (ref id in rbits, key fingerprint in the other
-// >= 8 bits).  4K level-2 counters (16 KiB of LDS) and a 16 MB directory at the bench's
+// E/4, at most 2^24 buckets); entries are u32 (ref id in rbits, key fingerprint in the next
+// >= 7 bits, the visited-prefix flag of the half probe's cut at sketch size `cut` on top).  4K level-2 counters (16 KiB of LDS) and a 16 MB directory at the bench's
 // E = 1e7.  Same-box A/B: E/2 buckets cost 0.04 ms more in the bucket pass than the extra
 // probe events saved; E/8 a wash.
 // FPM_IDX_ONEPASS=0: always the exact two-pass index build (A/B)
@@ -63,7 +63,7 @@ static const bool g_idx_one_pass = [] {
     return !(v && v[0] == '0');
 }();
 
-static IdxGeom make_geom(uint32_t n_ref, uint64_t E)
+static IdxGeom make_geom(uint32_t n_ref, uint64_t E, uint32_t cut)
 {
     IdxGeom geom{};
     uint32_t rbits = 1, lg = 1;
@@ -72,7 +72,8 @@ static IdxGeom make_geom(uint32_t n_ref, uint64_t E)
     geom.l2 = lg > kIdxL1 + 2 ? std::min<uint32_t>(lg - 2 - kIdxL1, 14) : 1;
     geom.nbits = kIdxL1 + geom.l2;
     geom.rbits = rbits;
-    geom.fbits = 32 - rbits;
+    geom.fbits = rbits < 31 ? 31 - rbits : 0;
+    geom.cut = cut;
     // level-1 tiles (one 1024-thread workgroup per CU: their LDS staging holds 8 B per cell)
     // in whole rounds of 256: the cells per tile trimmed so that the last round is not a
     // fraction of the chip (C2's 1e7 cells: 752 tiles of 13,312 instead of 611 of 16,384)
@@ -185,7 +186,7 @@ static int refset_build_index(fpm_refset *rs, hipStream_t st)
     fpm_ctx *ctx = rs->ctx;
     const RowSet &R = rs->ref;
     const uint64_t E = (uint64_t)R.n * R.stride;
-    IdxGeom geom = make_geom(R.n, E);
+    IdxGeom geom = make_geom(R.n, E, rs->sketch_size);
     rs->sparse_ok = E > 0 && geom.rbits <= 24 && E < (1ULL << 31);
     if (!rs->sparse_ok) return FPM_OK;
     void *ctr;
@@ -218,7 +219,7 @@ static int refset_build_index(fpm_refset *rs, hipStream_t st)
                                        (uint32_t *)dref_len, rs->mr, st));
             tl.done();
         }
-        geom = make_geom(R.n, (uint64_t)R.n * rs->mr);
+        geom = make_geom(R.n, (uint64_t)R.n * rs->mr, 0);
         geom.kmax = rs->kmax;
         if (int rc = build(RowSet{dref, (const uint32_t *)dref_len, nullptr, rs->mr, R.n}, geom,
                            false))
@@ -277,10 +278,21 @@ struct SparsePlan {
     RecRows rec_r{}, rec_q{};                   // record rows (unsorted lists) for the walk
     bool skip_count = false;                    // no probe count ran: the probe counts and tests
     bool spec_probe = false;                    // the probe is enqueued already (speculated)
+    bool spec_half = false;                     // and took the half form
     unsigned long long *n_cand() const { return ctr + kCtrCand; }
     uint32_t *unsorted() const { return (uint32_t *)(ctr + kCtrUnsorted); }
     uint32_t *cand_over() const { return (uint32_t *)(ctr + kCtrCandOver); }
 };
+
+// The symmetric probe (one sorted set against itself on the rank kernel's path) takes the half
+// form when the index's flags were cut at this call's sketch size (a resident set built at
+// another S: the full form) and the context's switch is on.
+static bool probe_half(const Compare &c, const SparsePlan &p, bool sym)
+{
+    // (sym already excludes record rows and the skip-count path: neither is a sorted set
+    // against itself; the launcher refuses the half form with either)
+    return sym && c.ctx->probe_half && p.geom.cut == c.S && !p.p_len && !p.skip_count;
+}
 
 static int zero_list(Compare &c)
 {
@@ -399,7 +411,7 @@ static int index_transient(Compare &c, SparsePlan &p)
         p.p_rows = p.rec_q.val;
         p.p_len = p.rec_q.len;
         p.p_stride = p.rec_q.stride;
-        p.geom = make_geom(R.n, (uint64_t)R.n * mr);
+        p.geom = make_geom(R.n, (uint64_t)R.n * mr, 0);
         p.geom.kmax = events + kCtrKmax;
         if (int rc = build_index(ctx, RowSet{dref, p.rec_r.len, nullptr, mr, R.n}, hash_bytes,
                                  p.geom, (uint32_t *)dir_, (uint32_t *)entries_, events, self_set,
@@ -439,11 +451,14 @@ static int index_transient(Compare &c, SparsePlan &p)
         void *cand, *row_seg;
         HIP_TRY(scratch(ctx, kSlotCand, pf.cap * 8, &cand));
         HIP_TRY(scratch(ctx, kSlotRowSeg, (size_t)Q.n * 8, &row_seg));
+        // the form the confirmed call takes (sym = self_set there: it is kept only on the
+        // rank kernel's path)
+        p.spec_half = probe_half(c, p, self_set);
         TimedLaunch tl(ctx, FPM_K_PROBE, st);
         HIP_TRY(launch_probe_rows(Q.rows, Q.len, Q.stride, Q.n, R.n, hash_bytes, p.geom, p.dir,
                                   p.entries, R.len, c.S, self_set, pf.defaults, self_set, c.cnt,
                                   (uint64_t *)cand, p.n_cand(), (uint64_t *)row_seg, nullptr,
-                                  nullptr, nullptr, pf.cap, p.cand_over(), st));
+                                  nullptr, nullptr, pf.cap, p.cand_over(), st, 0, p.spec_half));
         tl.done();
         p.spec_probe = true;
         return FPM_OK;
@@ -567,6 +582,8 @@ static int candidate_phase(Compare &c, SparsePlan &p, bool rows_merge, uint64_t 
     // probe gives it: pair parity) and each result is written to both cells (q, r) and
     // (r, q)
     const bool sym = rows_merge && c.self_set;
+    const bool half = p.spec_probe ? p.spec_half : probe_half(c, p, sym);
+    ctx->last_probe = half ? FPM_PROBE_HALF : FPM_PROBE_FULL;
     if (!p.spec_probe) {
         TimedLaunch tl(ctx, FPM_K_PROBE, st);
         HIP_TRY(launch_probe_rows(p.p_rows, Q.len, p.p_stride, Q.n, R.n, c.hash_bytes, p.geom,
@@ -574,7 +591,8 @@ static int candidate_phase(Compare &c, SparsePlan &p, bool rows_merge, uint64_t 
                                   c.self_set, c.cnt, (uint64_t *)cand, p.n_cand(),
                                   (uint64_t *)row_seg, p.p_len,
                                   p.skip_count ? p.unsorted() : nullptr,
-                                  p.skip_count ? p.ctr : nullptr, cap, p.cand_over(), st));
+                                  p.skip_count ? p.ctr : nullptr, cap, p.cand_over(), st, 0,
+                                  half));
         tl.done();
     }
     // A resident sorted set against a block without a count (skip_count): the rank
@@ -742,6 +760,7 @@ static int compare_impl(fpm_ctx *ctx, const RowSet &R, const RowSet &Q, uint32_t
     const uint64_t n_pairs = (uint64_t)R.n * Q.n;
     ctx->last_sparse = 0;
     ctx->last_kernel = FPM_DK_NONE;
+    ctx->last_probe = FPM_PROBE_NONE;
     ctx->last_events = 0;
     ctx->last_cand = 0;
     if (n_pairs == 0) {
@@ -753,7 +772,7 @@ static int compare_impl(fpm_ctx *ctx, const RowSet &R, const RowSet &Q, uint32_t
                       (ctx->dist_mode == FPM_DIST_AUTO && n_pairs >= 4096 && E > 0);
     if (E == 0) try_sparse = false;
     SparsePlan p;
-    p.geom = make_geom(R.n, E);
+    p.geom = make_geom(R.n, E, sketch_size);
     if (p.geom.rbits > 24 || E >= (1ULL << 31)) try_sparse = false;
     if (rs && !rs->sparse_ok) try_sparse = false;
     Compare c{ctx, st, R, Q, hash_bytes, sketch_size, cnt, fin, rs, n_pairs};
@@ -942,7 +961,10 @@ static int refset_check(fpm_refset *rs, uint32_t sketch_size, uint32_t count_byt
                         const char *who)
 {
     if (!rs) return fail(FPM_EINVAL, std::string(who) + ": null set");
-    if (sketch_size != rs->sketch_size)
+    // an index over records holds those of each row's first min(len, S) entries: S is the
+    // set's.  Sorted rows are indexed whole, so a call at another S probes the same index
+    // (the set against itself then takes the full probe: the flags were cut at the set's S)
+    if (sketch_size != rs->sketch_size && rs->recorded)
         return fail(FPM_EINVAL, std::string(who) + ": sketch_size differs from the set's");
     if (count_bytes != 2 && count_bytes != 4) return fail(FPM_EINVAL, "count_bytes must be 2 or 4");
     if (count_bytes == 2 && sketch_size > 65535)

@@ -171,6 +171,8 @@ struct fpm_ctx {
                                // (-1: for grids of >= 2^28 pairs; FPM_FILL_COUNTS=0/1 forces)
     int last_sparse = 0;
     int last_kernel = FPM_DK_NONE;   // fpm_ctx_last_dist_kernel
+    bool probe_half = true;          // fpm_ctx_set_probe_half (FPM_PROBE_HALF=0 starts it off)
+    int last_probe = FPM_PROBE_NONE; // fpm_ctx_last_dist_probe
     uint64_t last_events = 0, last_cand = 0;
     const unsigned long long *last_cand_dev = nullptr;   // the last sparse call's counter
     hipStream_t last_cand_stream = nullptr;

@@ -172,7 +172,7 @@ struct IdxGeom {
     uint32_t l2;       // level-2 bits (1..14)
     uint32_t nbits;    // bucket bits = kIdxL1 + l2
     uint32_t rbits;    // ref-id bits in a u32 entry
-    uint32_t fbits;    // key-fingerprint bits in a u32 entry (32 - rbits, >= 8)
+    uint32_t fbits;    // key-fingerprint bits in a u32 entry (31 - rbits, >= 7); bit 31: the flag
     uint32_t ntiles;   // level-1 tiles
     uint32_t tile;     // matrix cells per level-1 tile (<= kIdxTile, a multiple of 1024)
     // device pointer: the largest indexed key (idx_kmax_kernel), from which every kernel
@@ -182,6 +182,10 @@ struct IdxGeom {
     // each tile appends to its partitions by one atomic per partition); 0 = the exact
     // two-pass build (histogram + scan, tent holds E entries)
     uint32_t cap;
+    // the sketch size S of the half probe's cut: an entry's flag (bit 31) says that its
+    // position is inside its own row's visited prefix, pos < (len >= S ? (S + 1) / 2 : len);
+    // 0 = no cut, every entry flagged (record-row indexes)
+    uint32_t cut;
 };
 // entries of the level-1 staging buffer `tent` the build needs
 uint64_t idx_tent_words(const IdxGeom &g, uint64_t E);
@@ -251,7 +255,11 @@ hipError_t launch_probe_rows(const void *d_qry, const uint32_t *d_qry_len, uint6
                              unsigned long long *n_cand, uint64_t *row_seg,
                              const uint32_t *d_qry_it_len, uint32_t *q_unsorted,
                              unsigned long long *events, uint64_t cap, uint32_t *cand_over,
-                             hipStream_t st, uint32_t q_lo = 0);
+                             hipStream_t st, uint32_t q_lo = 0, bool half = false);
+// (half: the symmetric probe of one sorted set against itself over an index cut at this S
+// (g.cut == S): each row probes only its visited prefix and a pair is taken by its parity
+// owner when that row sees it, else by the other row; dist_index.hip step 2.  Needs sym and
+// self_set, and none of d_qry_it_len / q_unsorted / events: hipErrorInvalidValue otherwise)
 // (q_lo, n_qry: the query rows [q_lo, q_lo + n_qry) of the grid)
 // (d_qry_it_len non-null: the probed query rows are launch_record_rows copies of length
 // d_qry_it_len[q]; d_qry_len stays the original list lengths for the default cells)

@@ -38,6 +38,8 @@ DIST_PATHS = ["dense walk", "bucket index + literal walk", "bucket index + bucke
 DIST_KERNELS = ["none", "compare_grid_kernel", "compare_grid_lds_kernel",
                 "compare_grid_img_kernel", "walk_cand_kernel", "rank_rows_kernel<1024>",
                 "rank_rows_kernel<2048>"]
+# fpm_ctx_last_dist_probe codes (FPM_PROBE_*)
+PROBE_NONE, PROBE_FULL, PROBE_HALF = range(3)
 
 ALPHABET_NUCLEOTIDE = "ACGT"                     # Sketch.h alphabetNucleotide
 ALPHABET_PROTEIN = "ACDEFGHIKLMNPQRSTVWY"         # Sketch.h alphabetProtein
@@ -77,6 +79,8 @@ SYMBOLS = [
     ("fpm_ctx_set_dist_mode", C.c_int, [vp, C.c_int]),
     ("fpm_ctx_last_dist_stats", C.c_int, [vp, C.POINTER(C.c_int), u64p, u64p]),
     ("fpm_ctx_last_dist_kernel", C.c_int, [vp, C.POINTER(C.c_int)]),
+    ("fpm_ctx_set_probe_half", C.c_int, [vp, C.c_int]),
+    ("fpm_ctx_last_dist_probe", C.c_int, [vp, C.POINTER(C.c_int)]),
     ("fpm_sketch_batch", C.c_int, [vp, vp, C.c_char_p, u64p, C.c_uint32, u32p, C.c_uint32,
                                    u64p, u32p]),
     ("fpm_sketch_stage", C.c_int, [vp, vp, C.c_char_p, u64p, C.c_uint32, u32p, C.c_uint32,
@@ -623,6 +627,18 @@ class Context:
         k = C.c_int()
         _check(lib().fpm_ctx_last_dist_kernel(self.h, C.byref(k)))
         return k.value
+
+    def set_probe_half(self, on=True):
+        """fpm_ctx_set_probe_half: the symmetric self probe reads only the first half of each
+        row (default on; same results)"""
+        _check(lib().fpm_ctx_set_probe_half(self.h, int(on)))
+
+    def last_dist_probe(self):
+        """fpm_ctx_last_dist_probe: the form of the last compare's row probe (a PROBE_* code;
+        a test hook)"""
+        f = C.c_int()
+        _check(lib().fpm_ctx_last_dist_probe(self.h, C.byref(f)))
+        return f.value
 
     # --- sketch -----------------------------------------------------------
     def sketch(self, params, seqs, groups=None, n_groups=None, counts=False, min_copies=1):

@@ -147,6 +147,18 @@ int fpm_ctx_last_dist_stats(fpm_ctx *ctx, int *sparse, uint64_t *events, uint64_
 #define FPM_DK_CAND_RANK_1024 5
 #define FPM_DK_CAND_RANK_2048 6
 int fpm_ctx_last_dist_kernel(fpm_ctx *ctx, int *kernel);
+/* The symmetric probe of one sorted set against itself (index path, rank kernel) reads only
+ * the first half of each row: a pair's smallest shared hash can count only from the first
+ * ceil(S / 2) positions of one of its rows.  On by default; a context created with
+ * FPM_PROBE_HALF=0 in the environment starts with it off.  Same results either way. */
+int fpm_ctx_set_probe_half(fpm_ctx *ctx, int on);
+/* The form of the last compare's row probe (a test hook): NONE without a probe (dense walk, no
+ * pairs), else FULL or HALF.  When a transposed grid was computed by a swapped call, the form
+ * of that call.  Decided on the host: no synchronisation. */
+#define FPM_PROBE_NONE 0
+#define FPM_PROBE_FULL 1
+#define FPM_PROBE_HALF 2
+int fpm_ctx_last_dist_probe(fpm_ctx *ctx, int *form);
 
 /* ---- k-mer sketch ------------------------------------------------------------
  * Replaces addMinHashes (Sketch.cpp:664-735) + MinHashHeap::tryInsert
@@ -417,7 +429,9 @@ int fpm_dist(fpm_ctx *ctx, const void *ref, const uint32_t *ref_len, const uint6
  * for all query chunks).  A refset keeps the reference rows on the device and builds their
  * bucket index ONCE; each query block then only uploads its own rows, probes the resident
  * index and runs the exact candidate compare + distance / p-value (the same results as
- * fpm_dist_dev).  sketch_size (min of the two sketches' s, :342-344) is fixed per set.
+ * fpm_dist_dev).  sketch_size (min of the two sketches' s, :342-344) is fixed per set when
+ * its rows are unsorted (-fp lists: FPM_EINVAL for another); a set of sorted rows may be
+ * compared at another sketch_size, at the cost of the half probe when it is its own query.
  * _create copies host rows to the device (owned); _create_dev borrows device rows, which
  * must outlive the set.  count_bytes selects u16 (2, sketch_size <= 65535) or u32 (4)
  * numer / denom cells.  fpm_refset_dist takes host query rows and host outputs (pinned
