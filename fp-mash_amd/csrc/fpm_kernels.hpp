@@ -125,6 +125,9 @@ hipError_t launch_group_select(const SelDesc *d_desc, uint32_t n, const uint32_t
 // small: the round's lists are estimated short (merge_small_kernel; exact for any length)
 // merge_small_kernel launches whose lists overflowed its LDS cap since the last call (reset)
 hipError_t merge_small_spills(uint64_t *count);
+// sketch sizes up to which the other rounds stage a list in LDS (128 KiB; merge_lds_kernel),
+// beyond it they search in global memory (merge_kernel)
+constexpr uint32_t kMergeLdsKeys = 16384;
 hipError_t launch_merge(const MergeDesc *d_desc, uint32_t n, uint32_t s, bool small,
                         hipStream_t st);
 

@@ -930,6 +930,34 @@ int fpm_sketch_job_sample_short(fpm_sketch_job *job, int32_t *n_short)
     return FPM_OK;
 }
 
+int fpm_sketch_job_plan(fpm_sketch_job *job, fpm_sketch_plan *out)
+{
+    if (!job || !out) return fail(FPM_EINVAL, "null argument");
+    static_assert(FPM_TILE_CLASSES == kTileClasses, "fpmash.h states the tile classes");
+    *out = fpm_sketch_plan{};
+    for (int c = 0; c < kTileClasses; c++) {
+        out->tiles[c] = job->class_begin[c + 1] - job->class_begin[c];
+        out->sample_tiles[c] = job->sclass_begin[c + 1] - job->sclass_begin[c];
+    }
+    out->thr4 = job->thr4 ? 1 : 0;
+    out->n_slots = job->n_slots;
+    out->tight = job->tight ? 1 : 0;
+    out->n_ssel = job->n_ssel;
+    out->n_sel = job->n_sel;
+    // as merge_pass (fpm_sketch_run) routes each round
+    auto rounds = [](const std::vector<uint32_t> &begin, const std::vector<uint8_t> &small,
+                     uint32_t *n, uint32_t *n_small) {
+        *n = begin.empty() ? 0 : (uint32_t)begin.size() - 1;
+        for (size_t r = 0; r < *n; r++)
+            if (g_merge_small_env == 2 || (g_merge_small_env != 0 && r < small.size() && small[r]))
+                ++*n_small;
+    };
+    rounds(job->round_begin, job->round_small, &out->rounds, &out->rounds_small);
+    rounds(job->sround_begin, job->sround_small, &out->sample_rounds, &out->sample_rounds_small);
+    out->merge_kernel = job->kp.s <= kMergeLdsKeys ? FPM_MK_LDS : FPM_MK_GLOBAL;
+    return FPM_OK;
+}
+
 int fpm_merge_small_spills(fpm_ctx *ctx, uint64_t *count)
 {
     if (!count) return fail(FPM_EINVAL, "null argument");

@@ -1684,7 +1684,7 @@ hipError_t launch_merge(const MergeDesc *d_desc, uint32_t n, uint32_t s, bool sm
         return hipGetLastError();
     }
     // up to 128 KiB of staged list (s <= 16,384); beyond, the global-memory searches
-    constexpr size_t kMaxLds = 128 * 1024;
+    constexpr size_t kMaxLds = kMergeLdsKeys * sizeof(uint64_t);
     const size_t lds = (size_t)s * sizeof(uint64_t);
     if (lds <= kMaxLds &&
         hipFuncSetAttribute((const void *)merge_lds_kernel,

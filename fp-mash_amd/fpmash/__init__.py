@@ -99,6 +99,7 @@ SYMBOLS = [
     ("fpm_sketch_job_redo_tiles", C.c_int, [vp, C.POINTER(C.c_int32)]),
     ("fpm_sketch_job_short_groups", C.c_int, [vp, C.POINTER(C.c_int32)]),
     ("fpm_sketch_job_sample_short", C.c_int, [vp, C.POINTER(C.c_int32)]),
+    ("fpm_sketch_job_plan", C.c_int, [vp, vp]),
     ("fpm_sketch_job_free", None, [vp]),
     ("fpm_fp_hash_lines", C.c_int, [vp, u64p, u64p, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
     ("fpm_fp_hash_lines_dev", C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp,
@@ -181,6 +182,20 @@ class CellListStruct(C.Structure):
     """fpm_cell_list (include/fpmash.h): device arrays of the compact dist output's list"""
     _fields_ = [("qry", vp), ("ref", vp), ("dist", vp), ("pvalue", vp), ("pass_", vp),
                 ("cap", C.c_uint64), ("count", vp)]
+
+
+TILE_CLASSES = 6                                  # FPM_TILE_CLASSES: class c = 256 << c starts
+MK_LDS, MK_GLOBAL = range(2)                      # fpm_sketch_plan.merge_kernel (FPM_MK_*)
+
+
+class SketchPlan(C.Structure):
+    """fpm_sketch_plan (include/fpmash.h): the routes staging chose for a sketch job"""
+    _fields_ = [("tiles", C.c_uint32 * TILE_CLASSES), ("sample_tiles", C.c_uint32 * TILE_CLASSES),
+                ("thr4", C.c_uint32), ("n_slots", C.c_uint32), ("tight", C.c_uint32),
+                ("n_ssel", C.c_uint32), ("n_sel", C.c_uint32),
+                ("rounds", C.c_uint32), ("rounds_small", C.c_uint32),
+                ("sample_rounds", C.c_uint32), ("sample_rounds_small", C.c_uint32),
+                ("merge_kernel", C.c_uint32)]
 
 
 class FpmError(RuntimeError):
@@ -465,6 +480,16 @@ class SketchJob:
         _check(lib().fpm_sketch_job_sample_short(self.h, C.byref(n)))
         return n.value
 
+    def plan(self):
+        """fpm_sketch_job_plan: the routes staging chose (a test hook) -> dict: tiles and
+        sample_tiles per class (lists), thr4, n_slots, tight, n_ssel, n_sel, rounds,
+        rounds_small, sample_rounds, sample_rounds_small, merge_kernel (MK_*)"""
+        p = SketchPlan()
+        _check(lib().fpm_sketch_job_plan(self.h, C.byref(p)))
+        out = {n: getattr(p, n) for n, _ in SketchPlan._fields_}
+        out["tiles"], out["sample_tiles"] = list(p.tiles), list(p.sample_tiles)
+        return out
+
     def device_output(self):
         dh, dc = vp(), vp()
         ng, st = C.c_uint32(), C.c_uint32()
@@ -705,10 +730,9 @@ class Context:
         return job.value, {"seg": seg[:n], "hdr_off": ho[:n], "hdr_len": hl[:n],
                            "seq_len": sl[:n]}, bool(q.value)
 
-    def sketch_seq(self, params, seq_job, groups, n_groups, counts=False, min_copies=1):
-        """fpm_sketch_stage_seq + run + fetch over parsed records (the job takes the packed
-        records; free the parse handle with seq_free afterwards).  min_copies > 1: reads mode,
-        only hashes seen at least min_copies times."""
+    def sketch_seq_job(self, params, seq_job, groups, n_groups):
+        """fpm_sketch_stage_seq: the staged SketchJob over parsed records (it takes the packed
+        records; free it, and the parse handle with seq_free, afterwards)."""
         g = np.ascontiguousarray(groups, dtype=np.uint32)
         if g.size == 0:
             g = np.zeros(1, np.uint32)
@@ -717,6 +741,13 @@ class Context:
                                           n_groups, C.byref(h)))
         job = SketchJob.__new__(SketchJob)
         job.ctx, job.params, job.n_groups, job.h, job._keep = self, params, n_groups, h.value, None
+        return job
+
+    def sketch_seq(self, params, seq_job, groups, n_groups, counts=False, min_copies=1):
+        """fpm_sketch_stage_seq + run + fetch over parsed records (the job takes the packed
+        records; free the parse handle with seq_free afterwards).  min_copies > 1: reads mode,
+        only hashes seen at least min_copies times."""
+        job = self.sketch_seq_job(params, seq_job, groups, n_groups)
         if min_copies != 1:
             try:
                 job.set_min_copies(min_copies)

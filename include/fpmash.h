@@ -251,6 +251,28 @@ int fpm_sketch_job_short_groups(fpm_sketch_job *job, int32_t *n_short);
  * unbounded (a test hook, like the two above; every run starts from the staged bounds).  -1
  * when the job's samples carry no a-priori bound. */
 int fpm_sketch_job_sample_short(fpm_sketch_job *job, int32_t *n_short);
+/* The routes staging chose for a job (a test hook like fpm_ctx_last_dist_kernel, the result
+ * does not depend on it): what fpm_sketch_run will launch, as decided on the host when the job
+ * was staged: no synchronisation.  Tile class c holds the tiles of at most 256 << c k-mer
+ * starts (one sketch_tiles_kernel instance per class).  A merge plan's rounds are one launch
+ * each: `small` of them go to the small-list kernel (merge_small_kernel, by the estimated list
+ * lengths and FPM_MERGE_SMALL), the others to `merge_kernel`, which depends on sketch_size
+ * only (lists staged in LDS up to 16,384 hashes, searched in global memory beyond). */
+#define FPM_TILE_CLASSES 6
+#define FPM_MK_LDS 0
+#define FPM_MK_GLOBAL 1
+typedef struct fpm_sketch_plan {
+    uint32_t tiles[FPM_TILE_CLASSES];         /* main pass: tiles per class */
+    uint32_t sample_tiles[FPM_TILE_CLASSES];  /* sample pass of the long groups */
+    uint32_t thr4;            /* the class-4 tiles take the survivors-only kernel (+ its redo) */
+    uint32_t n_slots;         /* sampled (long) groups */
+    uint32_t tight;           /* their bounds are the tight ones (short_groups() >= 0) */
+    uint32_t n_ssel, n_sel;   /* one-workgroup selections: of the samples, of the groups */
+    uint32_t rounds, rounds_small;                /* main merge plan */
+    uint32_t sample_rounds, sample_rounds_small;  /* sample merge plan */
+    uint32_t merge_kernel;    /* FPM_MK_*: the kernel of the rounds that are not small */
+} fpm_sketch_plan;
+int fpm_sketch_job_plan(fpm_sketch_job *job, fpm_sketch_plan *out);
 void fpm_sketch_job_free(fpm_sketch_job *job);
 
 /* Bottom-s of the union of n_lists sketches (device rows of stride s, ascending and
