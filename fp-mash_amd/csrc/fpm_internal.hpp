@@ -1,7 +1,7 @@
 // fpm_internal.hpp — what the files implementing the C ABI of include/fpmash.h share:
 // the context, its pool / ring / copy helpers, the device scratch slots and the counter block.
-// fpm_ctx.cpp defines the helpers; fpm_sketch_api.cpp, fpm_text_api.cpp, fpm_dist_api.cpp and
-// fpm_comm.cpp use them.  Nothing declared here is exported from the library.
+// fpm_ctx.cpp defines the helpers; fpm_sketch_api.cpp, fpm_text_api.cpp, fpm_dist_api.cpp,
+// fpm_contain_api.cpp and fpm_comm.cpp use them.  Nothing declared here is exported from the library.
 #pragma once
 
 #include "fpm_kernels.hpp"
@@ -149,6 +149,7 @@ enum CtrWord : uint32_t {
     kCtrKmax = 68,         // the largest indexed key (the bucket scale)
     kCtrCandOver = 69,     // flag: a probe ran past its candidate buffer (only a speculated one can)
     kCtrKmaxAcc = 72,      // ..73: idx_kmax_kernel's accumulator, kept at zero between calls
+    kCtrContain = 74,      // contain: low u32 the not-ascending flag, high u32 the longest query row
     kCtrWords = 80,
     kCtrProbeWords = kCtrOverflow,   // [0, 67): cleared before, and read after, a probe count
     kCtrBuildWords = kCtrKmax,       // [0, 68): published after an index build
@@ -173,6 +174,8 @@ struct fpm_ctx {
     int last_kernel = FPM_DK_NONE;   // fpm_ctx_last_dist_kernel
     bool probe_half = true;          // fpm_ctx_set_probe_half (FPM_PROBE_HALF=0 starts it off)
     int last_probe = FPM_PROBE_NONE; // fpm_ctx_last_dist_probe
+    int contain_mode = FPM_CONTAIN_AUTO;        // fpm_ctx_set_contain_mode
+    int last_contain_kernel = FPM_CK_NONE;      // fpm_ctx_last_contain_kernel
     uint64_t last_events = 0, last_cand = 0;
     const unsigned long long *last_cand_dev = nullptr;   // the last sparse call's counter
     hipStream_t last_cand_stream = nullptr;

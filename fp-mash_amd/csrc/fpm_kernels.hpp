@@ -1,5 +1,6 @@
 // fpm_kernels.hpp — launch interface between the C-ABI (fpm_*_api.cpp) and the
-// gfx950 kernels (sketch.hip, dist.hip, fingerprint.hip).  Host-only types.
+// gfx950 kernels (sketch.hip, dist.hip, dist_index.hip, fingerprint.hip, seqparse.hip,
+// contain.hip).  Host-only types.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -336,6 +337,32 @@ hipError_t launch_positional_grid(const void *d_ref, const uint32_t *d_ref_len,
                                   uint32_t hash_bytes, double max_dist, double max_pvalue,
                                   uint32_t *d_numer, uint32_t *d_denom, double *d_dist,
                                   double *d_pvalue, uint8_t *d_pass, hipStream_t st);
+
+// contain (contain.hip): per pair the (common, steps) of containSketches
+// (CommandContain.cpp:368-412), query-major cells q * n_ref + r.
+// flag[0..1] (zeroed by the caller): flag[0] = 1 when some row of either set is not strictly
+// ascending within its length (plain stores), flag[1] = the longest query row (atomic max);
+// the caller reads them back (one stream synchronisation)
+hipError_t launch_rows_ascending(const void *d_ref, const uint32_t *d_ref_len, uint64_t ref_stride,
+                                 uint32_t n_ref, const void *d_qry, const uint32_t *d_qry_len,
+                                 uint64_t qry_stride, uint32_t n_qry, uint32_t hash_bytes,
+                                 uint32_t *flag, hipStream_t st);
+// the longest query row contain_rows_kernel stages in LDS on the current device (the dynamic
+// LDS limit is raised above 64 KB when the device grants it)
+uint32_t contain_lds_cap(uint32_t hash_bytes);
+// closed form, for strictly ascending rows only; max_qry_len = the longest query row, which
+// picks the LDS-staged or the global-memory instance (*lds)
+hipError_t launch_contain_rows(const void *d_ref, const uint32_t *d_ref_len, uint64_t ref_stride,
+                               uint32_t n_ref, const void *d_qry, const uint32_t *d_qry_len,
+                               uint64_t qry_stride, uint32_t n_qry, uint32_t hash_bytes,
+                               uint32_t max_qry_len, uint32_t *d_common, uint32_t *d_steps,
+                               hipStream_t st, bool *lds);
+// the literal walk, one lane per pair: exact for any lists
+hipError_t launch_contain_literal(const void *d_ref, const uint32_t *d_ref_len,
+                                  uint64_t ref_stride, uint32_t n_ref, const void *d_qry,
+                                  const uint32_t *d_qry_len, uint64_t qry_stride, uint32_t n_qry,
+                                  uint32_t hash_bytes, uint32_t *d_common, uint32_t *d_steps,
+                                  hipStream_t st);
 
 // The transposed grid of a rectangular compare (fpm_refset_dist_mirror_dev): cell (r, q) at
 // r * n_qry + q holds the pair "query r of the ref set against ref q of the query set".  For

@@ -4,6 +4,7 @@ A ctypes mirror of the reference's engine calls for this path:
   Sketch sketching (addMinHashes/MinHashHeap, Sketch.cpp:664-735, 1490-1517) -> Context.sketch
   -fp line hashing (getHashFingerPrint, hash.cpp:45-73)                    -> Context.fp_hash_lines
   compare/compareSketches/pValue (CommandDistance.cpp:335-450)             -> Context.dist
+  contain/containSketches (CommandContain.cpp:314-412)                     -> Context.contain
 The shared library is built in-tree (fp-mash_amd/lib/libfpmash.so).  There is no
 CPU fallback: if the library is missing this import fails, and without a gfx950
 device Context() raises FpmError(FPM_ENODEV).
@@ -25,7 +26,8 @@ FPM_OK, FPM_EINVAL, FPM_ENODEV, FPM_EHIP, FPM_ENOMEM = 0, -1, -2, -3, -4
  K_SEQPARSE) = range(10)
 NO_GROUP = 0xFFFFFFFF
 KERNEL_NAMES = {K_SKETCH: "sketch_tiles_kernel", K_MERGE: "merge_kernel",
-                K_FPHASH: "fp_hash_kernel", K_COMPARE: "candidate compare (rank_rows/walk_cand/compare_grid)",
+                K_FPHASH: "fp_hash_kernel",
+                K_COMPARE: "candidate compare (rank_rows/walk_cand/compare_grid), contain_rows/contain_literal",
                 K_FINALIZE: "dist finalize (dense / candidate cells)", K_INDEX: "dist index build",
                 K_PROBE: "probe_rows_kernel", K_FPTEXT: "fp text parse (nl index + fp_line)",
                 K_FILL: "dist_fill_kernel", K_SEQPARSE: "FASTA parse (seq chunk scan + emit)"}
@@ -40,6 +42,12 @@ DIST_KERNELS = ["none", "compare_grid_kernel", "compare_grid_lds_kernel",
                 "rank_rows_kernel<2048>"]
 # fpm_ctx_last_dist_probe codes (FPM_PROBE_*)
 PROBE_NONE, PROBE_FULL, PROBE_HALF = range(3)
+# fpm_ctx_set_contain_mode (FPM_CONTAIN_*) and fpm_ctx_last_contain_kernel (FPM_CK_*) codes
+CONTAIN_AUTO, CONTAIN_LITERAL = range(2)
+CK_NONE, CK_ROWS_LDS, CK_ROWS_GLOBAL, CK_LITERAL = range(4)
+CONTAIN_KERNELS = ["none", "contain_rows_kernel<lds>", "contain_rows_kernel<global>",
+                   "contain_literal_kernel"]
+CONTAIN_BLOCK_REFS = 64                          # FPM_CONTAIN_BLOCK_REFS
 
 ALPHABET_NUCLEOTIDE = "ACGT"                     # Sketch.h alphabetNucleotide
 ALPHABET_PROTEIN = "ACDEFGHIKLMNPQRSTVWY"         # Sketch.h alphabetProtein
@@ -133,6 +141,13 @@ SYMBOLS = [
     ("fpm_dist", C.c_int, [vp, vp, u32p, u64p, C.c_uint64, C.c_uint32, vp, u32p, u64p,
                            C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                            C.c_double, C.c_double, C.c_double, u32p, u32p, f64p, f64p, u8p]),
+    ("fpm_contain", C.c_int, [vp, vp, u32p, C.c_uint64, C.c_uint32, vp, u32p, C.c_uint64,
+                              C.c_uint32, C.c_uint32, u32p, u32p]),
+    ("fpm_contain_dev", C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64,
+                                  C.c_uint32, C.c_uint32, vp, vp, vp]),
+    ("fpm_ctx_set_contain_mode", C.c_int, [vp, C.c_int]),
+    ("fpm_ctx_last_contain_kernel", C.c_int, [vp, C.POINTER(C.c_int)]),
+    ("fpm_contain_lds_cap", C.c_int, [vp, C.c_uint32, u32p]),
     ("fpm_refset_create", C.c_int, [vp, vp, u32p, u64p, C.c_uint64, C.c_uint32, C.c_uint32,
                                     C.c_uint32, C.POINTER(vp)]),
     ("fpm_refset_create_dev", C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32,
@@ -824,6 +839,57 @@ class Context:
                               _p(pv, f64p), _p(pa, u8p)))
         return {"numer": nu[:n], "denom": de[:n], "distance": di[:n], "pvalue": pv[:n],
                 "pass": pa[:n].astype(bool)}
+
+    # --- contain ------------------------------------------------------------
+    def set_contain_mode(self, mode):
+        """fpm_ctx_set_contain_mode: CONTAIN_AUTO, or CONTAIN_LITERAL to force the literal walk
+        (same results)"""
+        _check(lib().fpm_ctx_set_contain_mode(self.h, mode))
+
+    def last_contain_kernel(self):
+        """fpm_ctx_last_contain_kernel: the kernel of the last contain call (a CK_* code; a
+        test hook)"""
+        k = C.c_int()
+        _check(lib().fpm_ctx_last_contain_kernel(self.h, C.byref(k)))
+        return k.value
+
+    def contain_lds_cap(self, use64=True):
+        """fpm_contain_lds_cap: the longest query row contain_rows_kernel stages in LDS"""
+        v = np.zeros(1, np.uint32)
+        _check(lib().fpm_contain_lds_cap(self.h, 8 if use64 else 4, _p(v, u32p)))
+        return int(v[0])
+
+    def contain_rows(self, R, ref_len, Q, qry_len):
+        """fpm_contain on dense row matrices (2-D u64 or u32 arrays, row stride = their width)
+        -> dict of flat query-major u32 arrays (index q*n_ref + r): common, steps"""
+        R, Q = np.ascontiguousarray(R), np.ascontiguousarray(Q)
+        if R.dtype != Q.dtype or R.dtype not in (np.uint64, np.uint32):
+            raise ValueError("contain_rows: both matrices u64 or both u32")
+        rl = np.ascontiguousarray(ref_len, dtype=np.uint32)
+        ql = np.ascontiguousarray(qry_len, dtype=np.uint32)
+        nr, nq = len(rl), len(ql)
+        n = nr * nq
+        co = np.zeros(max(n, 1), np.uint32)
+        stp = np.zeros(max(n, 1), np.uint32)
+        _check(lib().fpm_contain(self.h, R.ctypes.data, _p(rl, u32p), R.shape[1] if R.ndim == 2 else 0,
+                                 nr, Q.ctypes.data, _p(ql, u32p), Q.shape[1] if Q.ndim == 2 else 0,
+                                 nq, R.dtype.itemsize, _p(co, u32p), _p(stp, u32p)))
+        return {"common": co[:n], "steps": stp[:n]}
+
+    def contain(self, ref_lists, qry_lists, use64=True):
+        """All pairs of containSketches (CommandContain.cpp:368-412), query-major: common and
+        steps (the walk's final j); score = common / steps, error bound = 1 / sqrt(steps)."""
+        dt = np.uint64 if use64 else np.uint32
+        R, rl = _dense(ref_lists, max([len(x) for x in ref_lists] + [1]), dt)
+        Q, ql = _dense(qry_lists, max([len(x) for x in qry_lists] + [1]), dt)
+        return self.contain_rows(R, rl[:len(ref_lists)], Q, ql[:len(qry_lists)])
+
+    def contain_dev(self, d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len, qry_stride,
+                    n_qry, use64, d_common, d_steps, stream=None):
+        """fpm_contain_dev on device pointers (stream-ordered after its one read-back)"""
+        _check(lib().fpm_contain_dev(self.h, d_ref, d_ref_len, ref_stride, n_ref, d_qry,
+                                     d_qry_len, qry_stride, n_qry, 8 if use64 else 4, d_common,
+                                     d_steps, stream))
 
     def dist16(self, ref_lists, qry_lists, sketch_size, use64=True, k=21, kmer_space=None,
                ref_lengths=None, qry_lengths=None, max_dist=-1.0, max_pvalue=-1.0):

@@ -541,6 +541,50 @@ int fpm_fp_positional_grid(fpm_ctx *ctx, const void *ref, const uint32_t *ref_le
                            uint32_t *out_numer, uint32_t *out_denom, double *out_dist,
                            double *out_pvalue, uint8_t *out_pass);
 
+/* ---- contain ------------------------------------------------------------------------
+ * Replaces contain()/containSketches() (CommandContain.cpp:314-412) over the whole ref x query
+ * grid.  Per pair, with R / Q the lists as stored (lengths lr / lq, no cut to a sketch size):
+ *     common = 0; denom = min(lr, lq); i = j = 0
+ *     for (steps = 0; steps < denom && i < lr; steps++)
+ *         if      R[i] < Q[j]  { i++; steps--; }
+ *         else if Q[j] < R[i]  { j++; }
+ *         else                 { i++; j++; common++; }
+ * and the cell gets (common, j); compares are unsigned at hash_bytes.  The caller computes
+ * score = common / j and error = 1 / sqrt(j) in double (:408-411), so the device holds integers
+ * only.  Rows, strides, lengths and the query-major output (index q*n_ref + r) are those of
+ * fpm_compare_grid.
+ * When every row of both sets is strictly ascending the walk has an order-free form
+ * (jf = min(lr, lq, #{q in Q : q <= R[lr-1]}), common = |Q[0..jf) n R|, (0, 0) when a list is
+ * empty), which contain_rows_kernel computes with the query row staged in LDS, or read from
+ * global memory when the longest query row exceeds fpm_contain_lds_cap entries.  Otherwise,
+ * or in FPM_CONTAIN_LITERAL mode, contain_literal_kernel walks each pair as written above.
+ * The rows are tested on the device and the host reads the one flag: both calls synchronise
+ * `stream` once before the compare is launched (LITERAL mode skips the test and does not).
+ * No CPU fallback. */
+int fpm_contain_dev(fpm_ctx *ctx, const void *d_ref, const uint32_t *d_ref_len,
+                    uint64_t ref_stride, uint32_t n_ref, const void *d_qry,
+                    const uint32_t *d_qry_len, uint64_t qry_stride, uint32_t n_qry,
+                    uint32_t hash_bytes, uint32_t *d_common, uint32_t *d_steps, void *stream);
+/* host buffers, copied through the pinned staging ring */
+int fpm_contain(fpm_ctx *ctx, const void *ref, const uint32_t *ref_len, uint64_t ref_stride,
+                uint32_t n_ref, const void *qry, const uint32_t *qry_len, uint64_t qry_stride,
+                uint32_t n_qry, uint32_t hash_bytes, uint32_t *out_common, uint32_t *out_steps);
+#define FPM_CONTAIN_AUTO 0
+#define FPM_CONTAIN_LITERAL 1
+int fpm_ctx_set_contain_mode(fpm_ctx *ctx, int mode);
+/* The kernel the last contain call launched (a test hook like fpm_ctx_last_dist_kernel).
+ * NONE: an empty grid. */
+#define FPM_CK_NONE 0
+#define FPM_CK_ROWS_LDS 1
+#define FPM_CK_ROWS_GLOBAL 2
+#define FPM_CK_LITERAL 3
+int fpm_ctx_last_contain_kernel(fpm_ctx *ctx, int *kernel);
+/* the longest query row (entries of hash_bytes) contain_rows_kernel stages in LDS on this
+ * context's device */
+int fpm_contain_lds_cap(fpm_ctx *ctx, uint32_t hash_bytes, uint32_t *cap);
+/* ref rows one contain_rows_kernel workgroup takes (one wave per row at a time) */
+#define FPM_CONTAIN_BLOCK_REFS 64
+
 /* ---- communicator: RCCL over xGMI for the cross-GPU min-merge ------------------------
  * north_star reserves the collective for "the final min-merge only where the reference set
  * exceeds one GPU's HBM" (or one sketch is split over GPUs).  The reference has no collective:
