@@ -14,7 +14,9 @@
 //      so this is a two-level counting sort with no global atomics: per-tile LDS histograms
 //      of the top 10 bucket bits + one exclusive scan place every entry in its partition,
 //      then one workgroup per partition counting-sorts it by the next l2 bits in LDS and
-//      writes its slice of the directory;
+//      writes its slice of the directory.  An index that only the half probe (2) will read
+//      leaves out every hash above V*, the largest value any row looks up (IdxGeom::vcut):
+//      the indexed range is then [0, V*];
 //   2. one workgroup per query row looks up the bucket of each of its hashes; each wave
 //      flattens the buckets of 64 hashes into one event range and reads it coalesced,
 //      ORing the ref id of every entry whose fingerprint matches into a row bitmap in LDS
@@ -106,21 +108,26 @@ __device__ __forceinline__ uint32_t row_of(uint32_t e, uint32_t stride, uint64_t
 
 // ---- 0. the largest normalized key among the rows' last entries (the maximum for sorted
 // rows; unsorted rows may hold larger keys, which bucket_of clamps into the last bucket).
+// With the value cut (vcut: S, else 0) the last entry of each row's visited prefix instead,
+// row[H_r - 1] with H_r = len_r >= S ? ceil(S / 2) : len_r: the largest value V* any row of the
+// half probe looks up, so the level-1 kernels drop what lies above it.  Also sums the rows'
+// lengths (n_entries[1]: the entries an uncut index holds).
 // A few workgroups (8 rows per thread in flight); each folds its maximum into acc[0] and the
 // last one to finish (acc[1] counts them) zeroes the call's counters (zero[0 .. nzero), which
 // may hold kmax itself), writes kmax and resets acc for the next call: no memset launch, and
-// not the 14 us of one workgroup walking 10k rows.  acc[0..1] start at zero (scratch()).
+// not the 14 us of one workgroup walking 10k rows.  acc[0..2] start at zero (scratch()).
 constexpr int kKmaxThreads = 256;
 constexpr int kKmaxU = 8;
 __global__ __launch_bounds__(kKmaxThreads) void idx_kmax_kernel(
     const void *__restrict__ ref, const uint32_t *__restrict__ ref_len, uint64_t stride,
     uint32_t n_ref, uint32_t hash_bytes, unsigned long long *__restrict__ kmax,
     unsigned long long *__restrict__ zero, uint32_t nzero, unsigned long long *acc,
-    uint32_t *__restrict__ zero32, uint32_t nzero32, unsigned long long *__restrict__ zero_x)
+    uint32_t *__restrict__ zero32, uint32_t nzero32, unsigned long long *__restrict__ zero_x,
+    uint32_t vcut, unsigned long long *__restrict__ n_entries)
 {
-    __shared__ unsigned long long wmax[kKmaxThreads / 64];
+    __shared__ unsigned long long wmax[kKmaxThreads / 64], wlen[kKmaxThreads / 64];
     __shared__ uint32_t s_last;
-    uint64_t mx = 0;
+    uint64_t mx = 0, nl = 0;
     const uint32_t step = gridDim.x * kKmaxThreads;
     for (uint32_t r0 = blockIdx.x * kKmaxThreads + threadIdx.x; r0 < n_ref; r0 += kKmaxU * step) {
         uint32_t l[kKmaxU];
@@ -128,6 +135,8 @@ __global__ __launch_bounds__(kKmaxThreads) void idx_kmax_kernel(
         for (int u = 0; u < kKmaxU; u++) {
             const uint32_t r = r0 + u * step;
             l[u] = r < n_ref ? ref_len[r] : 0u;
+            nl += min((uint64_t)l[u], stride);
+            if (vcut && l[u] >= vcut) l[u] = (vcut + 1) / 2;
         }
         uint64_t k[kKmaxU];
 #pragma unroll
@@ -139,12 +148,22 @@ __global__ __launch_bounds__(kKmaxThreads) void idx_kmax_kernel(
         for (int u = 0; u < kKmaxU; u++) mx = max(mx, k[u]);
     }
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) mx = max(mx, (uint64_t)__shfl_xor((unsigned long long)mx, d, 64));
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = mx;
+    for (int d = 32; d > 0; d >>= 1) {
+        mx = max(mx, (uint64_t)__shfl_xor((unsigned long long)mx, d, 64));
+        nl += (uint64_t)__shfl_xor((unsigned long long)nl, d, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        wmax[threadIdx.x >> 6] = mx;
+        wlen[threadIdx.x >> 6] = nl;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int w = 1; w < kKmaxThreads / 64; w++) mx = max(mx, (uint64_t)wmax[w]);
+        for (int w = 1; w < kKmaxThreads / 64; w++) {
+            mx = max(mx, (uint64_t)wmax[w]);
+            nl += wlen[w];
+        }
         atomicMax(&acc[0], (unsigned long long)mx);
+        if (nl) atomicAdd(&acc[2], (unsigned long long)nl);
         __threadfence();
         s_last = atomicAdd(&acc[1], 1ULL) == gridDim.x - 1 ? 1u : 0u;
     }
@@ -158,9 +177,20 @@ __global__ __launch_bounds__(kKmaxThreads) void idx_kmax_kernel(
     __syncthreads();
     if (threadIdx.x == 0) {
         *kmax = atomicMax(&acc[0], 0ULL);
+        const unsigned long long all = atomicAdd(&acc[2], 0ULL);
+        if (n_entries) n_entries[1] = all;
         acc[0] = 0;
         acc[1] = 0;
+        acc[2] = 0;
     }
+}
+
+// The value cut (g.vcut): a cell whose normalized key exceeds *g.kmax (then V*, idx_kmax_kernel)
+// is neither counted nor emitted by any level-1 kernel; a key equal to it is kept.  The
+// sortedness test still covers every cell of every row.
+__device__ __forceinline__ uint64_t idx_vmax(const IdxGeom &g)
+{
+    return g.vcut ? (uint64_t)*g.kmax : ~0ULL;
 }
 
 // ---- 1a. level-1 histogram: LDS counters per partition; also flags unsorted /
@@ -171,7 +201,7 @@ __global__ __launch_bounds__(kIdxThreads) void idx_part_hist_kernel(
     uint32_t *__restrict__ tile_hist, uint32_t *__restrict__ unsorted, IdxGeom g)
 {
     __shared__ uint32_t hist[kParts];
-    const uint64_t mult = idx_mult(g);
+    const uint64_t mult = idx_mult(g), vmax = idx_vmax(g);
     for (uint32_t p = threadIdx.x; p < kParts; p += kIdxThreads) hist[p] = 0;
     __syncthreads();
     const uint32_t e0 = blockIdx.x * g.tile, lane = threadIdx.x & 63;
@@ -195,7 +225,8 @@ __global__ __launch_bounds__(kIdxThreads) void idx_part_hist_kernel(
             if (lane == 63 && nx[u])
                 nk = load_key(ref, hash_bytes, (uint64_t)e0 + c0 + u * kIdxThreads + threadIdx.x + 1);
             uns |= nx[u] && !(key[u] < nk);
-            if (v[u]) atomicAdd(&hist[bucket_of(norm_key(key[u], hash_bytes), g, mult) >> g.l2], 1u);
+            const uint64_t K = norm_key(key[u], hash_bytes);
+            if (v[u] && K <= vmax) atomicAdd(&hist[bucket_of(K, g, mult) >> g.l2], 1u);
         }
     }
     if (__any(uns) && lane == 0) atomicOr(unsorted, 1u);
@@ -231,7 +262,7 @@ __global__ __launch_bounds__(kIdxThreads) void idx_part_scatter_kernel(
     extern __shared__ __attribute__((aligned(16))) uint64_t stage[];   // kIdxTile words
     __shared__ uint32_t gbase[kParts], lbase[kParts], lcur[kParts];
     __shared__ uint32_t wsum[kIdxThreads / 64];
-    const uint64_t mult = idx_mult(g);
+    const uint64_t mult = idx_mult(g), vmax = idx_vmax(g);
     // per-partition: global base of this tile's run, and its local base (block exscan of the
     // tile's counts)
     static_assert(kParts == kIdxThreads, "one partition per thread");
@@ -266,6 +297,7 @@ __global__ __launch_bounds__(kIdxThreads) void idx_part_scatter_kernel(
             rr[u] = r;
             fl[u] = entry_flag(i, la, g);
             K[u] = v[u] ? norm_key(load_key(ref, hash_bytes, e), hash_bytes) : 0;
+            v[u] = v[u] && K[u] <= vmax;                // (the histogram pass counted the same cells)
         }
 #pragma unroll
         for (int u = 0; u < kIdxU; u++)
@@ -302,6 +334,8 @@ __global__ __launch_bounds__(kIdxThreads) void idx_part_scatter1_kernel(
     __shared__ uint32_t wsum[kIdxThreads / 64];
     static_assert(kParts == kIdxThreads, "one partition per thread");
     const uint64_t mult = idx_mult(g);
+    // the cut against the raw keys (norm_key is monotone: a shift)
+    const uint64_t vraw = hash_bytes == 8 ? idx_vmax(g) : idx_vmax(g) >> 32;
     lcur[threadIdx.x] = 0;
     const uint32_t e0 = blockIdx.x * g.tile, lane = threadIdx.x & 63;
     const uint32_t n = min(n_ref * stride, e0 + g.tile);     // this tile's cells end here
@@ -336,7 +370,7 @@ __global__ __launch_bounds__(kIdxThreads) void idx_part_scatter1_kernel(
     }
     __syncthreads();                                          // lcur cleared, first[] written
     bool uns = false;
-    uint32_t vbits = 0;                                       // bit u: cell u is a list entry
+    uint32_t vbits = 0;                                       // bit u: cell u is an indexed list entry
     uint32_t fbits = 0;                                       // bit u: and carries the entry flag
     // pass 1: the tile's partition counts (and the sortedness flags)
 #pragma unroll
@@ -348,7 +382,7 @@ __global__ __launch_bounds__(kIdxThreads) void idx_part_scatter1_kernel(
         uint64_t nk = __shfl_down((unsigned long long)key[u], 1, 64);
         if (lane == 63) nk = wave_id + 1 < kW ? first[u][wave_id + 1] : first[u + 1][0];
         uns |= nx && !(key[u] < nk);
-        if (v) {
+        if (v && key[u] <= vraw) {
             vbits |= 1u << u;
             fbits |= entry_flag(i, la[u], g) ? 1u << u : 0u;
             atomicAdd(&lcur[bucket_of(norm_key(key[u], hash_bytes), g, mult) >> g.l2], 1u);
@@ -416,7 +450,8 @@ __global__ __launch_bounds__(kBucketThreads) void idx_bucket_kernel(
     const uint64_t *__restrict__ tent_all, uint32_t ntiles,
     const uint32_t *__restrict__ tile_off, IdxGeom g, uint32_t cap, uint32_t *__restrict__ dir,
     uint32_t *__restrict__ entries_all, unsigned long long *__restrict__ sqsum,
-    const uint32_t *__restrict__ part_fill, uint32_t lsplit)
+    const uint32_t *__restrict__ part_fill, uint32_t lsplit,
+    unsigned long long *__restrict__ n_entries)
 {
     extern __shared__ uint32_t sh[];             // the range's counters, then cursors; then cap entries
     __shared__ uint32_t wsum[kBucketThreads / 64];
@@ -529,7 +564,12 @@ __global__ __launch_bounds__(kBucketThreads) void idx_bucket_kernel(
         for (int d = 32; d > 0; d >>= 1) sq += __shfl_down(sq, d, 64);
         if (lane == 0) wsq[wave] = sq;
     }
-    if (p == kParts - 1 && j == ns - 1 && threadIdx.x == 0) dir[(uint64_t)kParts << g.l2] = s1;
+    // the last partition ends at the number of indexed entries (the sum of every partition's
+    // fill): also the call's indexed-entries counter, no atomics
+    if (p == kParts - 1 && j == ns - 1 && threadIdx.x == 0) {
+        dir[(uint64_t)kParts << g.l2] = s1;
+        if (n_entries) n_entries[0] = s1;
+    }
     __syncthreads();
     if (sqsum && threadIdx.x == 0) {
         unsigned long long t = 0;
@@ -732,6 +772,9 @@ __global__ void sum64_kernel(unsigned long long *events)
 // in q are unvisited, say c'; q holds c inside its prefix and c' outside, so c <= c'; r holds
 // c' inside and c outside, so c' <= c; then c = c' has a visited member on both sides, which
 // sets both.
+// The index may hold only the values <= V* (IdxGeom::vcut): every entry the argument names sits
+// inside its own row's visited prefix, hence is <= V* and indexed; the entries left out are
+// unvisited ones, which could only add seen bits through a collision (the index cut).
 template <typename C, bool HALF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8)))
 void probe_rows_kernel(
@@ -1173,8 +1216,10 @@ hipError_t launch_idx_build(const void *d_ref, const uint32_t *d_ref_len, uint64
                             uint32_t *dir, uint32_t *entries, uint32_t *unsorted,
                             unsigned long long *self_events, unsigned long long *zero,
                             uint32_t nzero, unsigned long long *acc, uint32_t *part_fill,
-                            uint32_t *overflow, hipStream_t st, unsigned long long *zero_x)
+                            uint32_t *overflow, hipStream_t st, unsigned long long *zero_x,
+                            unsigned long long *n_entries)
 {
+    if (g.vcut && !g.cut) return hipErrorInvalidValue;
     const uint32_t ntiles = g.ntiles;
     const uint64_t magic = stride > 1 ? ~0ULL / stride + 1 : 0;   // row_of's multiplier
     const uint32_t kg = std::max<uint32_t>(1, std::min<uint32_t>(
@@ -1182,7 +1227,8 @@ hipError_t launch_idx_build(const void *d_ref, const uint32_t *d_ref_len, uint64
     const bool one_pass = g.cap != 0 && part_fill && overflow;
     hipLaunchKernelGGL(idx_kmax_kernel, dim3(kg), dim3(kKmaxThreads), 0, st, d_ref, d_ref_len,
                        stride, n_ref, hash_bytes, (unsigned long long *)g.kmax, zero, nzero, acc,
-                       one_pass ? part_fill : nullptr, one_pass ? kParts : 0u, zero_x);
+                       one_pass ? part_fill : nullptr, one_pass ? kParts : 0u, zero_x,
+                       g.vcut ? g.cut : 0u, n_entries);
     // level 2: the sub-bucket range split over 2^lsplit workgroups until its counters fit
     // 32 KB and a range's mean entries 24k (C4, E = 5e7: 2 per partition).  The LDS copy: 16k
     // entries (80 KB with the counters, two workgroups per CU) when the ranges' mean fits 12k
@@ -1211,7 +1257,7 @@ hipError_t launch_idx_build(const void *d_ref, const uint32_t *d_ref_len, uint64
         hipLaunchKernelGGL(idx_bucket_kernel, bgrid, dim3(kBucketThreads),
                            (size_t)(cnt_bytes0 + (uint64_t)lds_cap * 4), st, (const uint64_t *)tent,
                            ntiles, (const uint32_t *)nullptr, g, lds_cap, dir, entries, self_events,
-                           (const uint32_t *)part_fill, lsplit);
+                           (const uint32_t *)part_fill, lsplit, n_entries);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(idx_part_hist_kernel, dim3(ntiles), dim3(kIdxThreads), 0, st, d_ref,
@@ -1231,7 +1277,7 @@ hipError_t launch_idx_build(const void *d_ref, const uint32_t *d_ref_len, uint64
     hipLaunchKernelGGL(idx_bucket_kernel, bgrid, dim3(kBucketThreads),
                        (size_t)(cnt_bytes0 + (uint64_t)lds_cap * 4), st, (const uint64_t *)tent,
                        ntiles, (const uint32_t *)tile_off, g, lds_cap, dir, entries, self_events,
-                       (const uint32_t *)nullptr, lsplit);
+                       (const uint32_t *)nullptr, lsplit, n_entries);
     return hipGetLastError();
 }
 

@@ -310,6 +310,7 @@ int fpm_ctx_create(int device, fpm_ctx **out)
     ctx->device = device;
     if (const char *v = getenv("FPM_FILL_COUNTS")) ctx->fill_counts = atoi(v) != 0 ? 1 : 0;
     if (const char *v = getenv("FPM_PROBE_HALF")) ctx->probe_half = atoi(v) != 0;
+    if (const char *v = getenv("FPM_INDEX_CUT")) ctx->index_cut = atoi(v) != 0;
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
@@ -523,6 +524,22 @@ int fpm_ctx_last_dist_probe(fpm_ctx *ctx, int *form)
 {
     if (!ctx || !form) return fail(FPM_EINVAL, "null argument");
     *form = ctx->last_probe;
+    return FPM_OK;
+}
+
+int fpm_ctx_set_index_cut(fpm_ctx *ctx, int on)
+{
+    if (!ctx) return fail(FPM_EINVAL, "null context");
+    ctx->index_cut = on != 0;
+    return FPM_OK;
+}
+
+int fpm_ctx_last_index_cut(fpm_ctx *ctx, int *cut, uint64_t *indexed, uint64_t *entries)
+{
+    if (!ctx) return fail(FPM_EINVAL, "null context");
+    if (cut) *cut = ctx->last_index_cut ? 1 : 0;
+    if (indexed) *indexed = ctx->last_indexed;
+    if (entries) *entries = ctx->last_entries;
     return FPM_OK;
 }
 

@@ -128,7 +128,8 @@ static int build_index(fpm_ctx *ctx, const RowSet &R, uint32_t hash_bytes, IdxGe
                                      (uint32_t *)scan_s, (uint64_t *)tent, dir, entries, unsorted,
                                      self_events ? ctr : nullptr, ctr, kCtrZeroWords,
                                      ctr + kCtrKmaxAcc, (uint32_t *)part_fill, overflow, st,
-                                     zero_x));
+                                     zero_x, ctr + kCtrIndexed));
+            static_assert(kCtrEntries == kCtrIndexed + 1, "launch_idx_build's n_entries[0..1]");
             if (int rc = then()) return rc;
             tl.done();
         }
@@ -168,6 +169,7 @@ struct fpm_refset {
     bool recorded = false;        // the index holds launch_record_rows copies
     uint64_t mr = 0;              // their row stride
     uint64_t self_events = 0;     // sum_b |b|^2: the posting events of the set against itself
+    uint64_t n_indexed = 0;       // the index's entries (never cut: other blocks probe it in full)
     // per-query-block device buffers (fpm_refset_dist, fpm_refset_dist_list): the uploaded
     // block, its result grids, and the six arrays of the device cell list
     enum { kQRows, kQLen, kQLength, kQNumer, kQDenom, kQDist, kQPval, kQPass, kQList,
@@ -205,7 +207,8 @@ static int refset_build_index(fpm_refset *rs, hipStream_t st)
     if (int rc = build(R, geom, true)) return rc;
     rs->ref_unsorted = host_unsorted(ctx);
     rs->self_events = host_events(ctx);
-    rs->mr = std::min<uint64_t>(R.stride, rs->sketch_size);
+    rs->n_indexed = host_indexed(ctx);
+    rs->mr =std::min<uint64_t>(R.stride, rs->sketch_size);
     rs->recorded = rs->ref_unsorted;
     if (rs->recorded) {
         void *dref, *dref_len, *dref_pos;
@@ -224,6 +227,7 @@ static int refset_build_index(fpm_refset *rs, hipStream_t st)
         if (int rc = build(RowSet{dref, (const uint32_t *)dref_len, nullptr, rs->mr, R.n}, geom,
                            false))
             return rc;
+        rs->n_indexed = host_indexed(ctx);
     }
     rs->geom = geom;
     return FPM_OK;
@@ -292,6 +296,39 @@ static bool probe_half(const Compare &c, const SparsePlan &p, bool sym)
     // (sym already excludes record rows and the skip-count path: neither is a sorted set
     // against itself; the launcher refuses the half form with either)
     return sym && c.ctx->probe_half && p.geom.cut == c.S && !p.p_len && !p.skip_count;
+}
+
+// The transient index of one set against itself leaves out every value above V*, the largest
+// value a half probe looks up (IdxGeom::vcut), for exactly the calls that end in the half probe
+// when they go sparse: probe_half's conditions and the rank kernel's (compare_impl's
+// rows_merge), as far as the host knows them before the build.  What it learns afterwards
+// leads elsewhere without a probe of this index: unsorted rows to the record index (rebuilt,
+// uncut), a dense result to the dense walk.  Resident sets stay whole (other blocks probe them
+// in full), and so do record indexes.
+static bool index_cut_ok(const Compare &c)
+{
+    return c.ctx->index_cut && c.ctx->probe_half && !c.rs && c.self_set && c.hash_bytes == 8 &&
+           c.S > 0 && c.R.n <= (1u << 19) && std::max(c.R.stride, c.Q.stride) <= 2048;
+}
+
+// The sparse / dense rule, the candidate capacity and the speculation profile are stated in the
+// posting events of the whole index.  A cut index counts those of its indexed values only:
+// scaled by entries / indexed entries, rounded up (exact when the sharing is spread evenly
+// over the rows' range, never below the cut count; candidates <= cut events still holds).
+static uint64_t whole_index_events(uint64_t ev, uint64_t entries, uint64_t indexed)
+{
+    if (!indexed || indexed >= entries) return ev;
+    const unsigned __int128 x = (unsigned __int128)ev * entries + (indexed - 1);
+    const unsigned __int128 q = x / indexed;
+    return q > (unsigned __int128)UINT64_MAX ? UINT64_MAX : (uint64_t)q;
+}
+
+// what fpm_ctx_last_index_cut reports, after an index build's counters were read
+static void note_index(fpm_ctx *ctx, const IdxGeom &g)
+{
+    ctx->last_index_cut = g.vcut != 0;
+    ctx->last_indexed = host_indexed(ctx);
+    ctx->last_entries = host_entries(ctx);
 }
 
 static int zero_list(Compare &c)
@@ -421,6 +458,7 @@ static int index_transient(Compare &c, SparsePlan &p)
         c.list_zeroed = true;
         p.all_sorted = false;
         p.ev = host_events(ctx);
+        note_index(ctx, p.geom);
         return FPM_OK;
     };
     if (hash_bytes == 4) {
@@ -433,6 +471,7 @@ static int index_transient(Compare &c, SparsePlan &p)
         if (host_unsorted(ctx)) return record_index();
     }
     p.geom.kmax = events + kCtrKmax;
+    p.geom.vcut = index_cut_ok(c) ? 1u : 0u;
     // A call of the last sparse rank-kernel call's shape (the bench's steps, a
     // pipeline's batches) enqueues its probe behind the index build before the
     // host reads the build's counters, so the GPU is not idle while the host
@@ -471,8 +510,9 @@ static int index_transient(Compare &c, SparsePlan &p)
                              c.list_zeroed ? nullptr : c.list_cnt))
         return rc;
     c.list_zeroed = true;
-    p.ev = host_events(ctx);
+    p.ev = whole_index_events(host_events(ctx), host_entries(ctx), host_indexed(ctx));
     p.all_sorted = !host_unsorted(ctx);
+    note_index(ctx, p.geom);
     if (p.all_sorted) return FPM_OK;
     if (hash_bytes != 4)
         if (int rc = records(nullptr)) return rc;
@@ -490,6 +530,7 @@ static int index_phase(Compare &c, SparsePlan &p)
     hipStream_t st = c.st;
     const RowSet &Q = c.Q;
     if (!rs) return index_transient(c, p);
+    ctx->last_indexed = ctx->last_entries = rs->n_indexed;
     // A resident sorted set against another block of sorted rows (the C4 block pairs, the
     // CLI's query blocks): no probe count.  The count pass reads every query hash's
     // bucket bounds at random (~0.27 ms for 2.2e7 hashes at N = 8, as long as the index
@@ -574,9 +615,6 @@ static int candidate_phase(Compare &c, SparsePlan &p, bool rows_merge, uint64_t 
     hipStream_t st = c.st;
     const RowSet &R = c.R, &Q = c.Q;
     const DistFinal *fin = c.fin;
-    void *cand, *row_seg;
-    HIP_TRY(scratch(ctx, kSlotCand, cap * 8, &cand));
-    HIP_TRY(scratch(ctx, kSlotRowSeg, (size_t)Q.n * 8, &row_seg));
     // one sorted set against itself: (numer, denom) of sorted distinct lists is
     // symmetric in the two sets, so each unordered pair is ranked once (by the row the
     // probe gives it: pair parity) and each result is written to both cells (q, r) and
@@ -584,6 +622,25 @@ static int candidate_phase(Compare &c, SparsePlan &p, bool rows_merge, uint64_t 
     const bool sym = rows_merge && c.self_set;
     const bool half = p.spec_probe ? p.spec_half : probe_half(c, p, sym);
     ctx->last_probe = half ? FPM_PROBE_HALF : FPM_PROBE_FULL;
+    // A cut index holds only the values a half probe looks up: no other form may run on it.
+    // index_cut_ok admits only calls that take the half form here, so this is a guard, not a
+    // path: should the two ever disagree, the index is rebuilt whole (any speculated probe
+    // dropped with it) and the call goes on as without the cut.
+    if (p.geom.vcut && !half) {
+        p.geom.vcut = 0;
+        p.spec_probe = false;
+        if (int rc = build_index(ctx, R, c.hash_bytes, p.geom, const_cast<uint32_t *>(p.dir),
+                                 const_cast<uint32_t *>(p.entries), p.ctr, c.self_set, st,
+                                 [] { return FPM_OK; }))
+            return rc;
+        p.ev = host_events(ctx);
+        note_index(ctx, p.geom);
+        ctx->last_events = p.ev;
+        cap = std::max<uint64_t>(1, std::min<uint64_t>(p.ev, c.n_pairs));
+    }
+    void *cand, *row_seg;
+    HIP_TRY(scratch(ctx, kSlotCand, cap * 8, &cand));
+    HIP_TRY(scratch(ctx, kSlotRowSeg, (size_t)Q.n * 8, &row_seg));
     if (!p.spec_probe) {
         TimedLaunch tl(ctx, FPM_K_PROBE, st);
         HIP_TRY(launch_probe_rows(p.p_rows, Q.len, p.p_stride, Q.n, R.n, c.hash_bytes, p.geom,
@@ -761,6 +818,8 @@ static int compare_impl(fpm_ctx *ctx, const RowSet &R, const RowSet &Q, uint32_t
     ctx->last_sparse = 0;
     ctx->last_kernel = FPM_DK_NONE;
     ctx->last_probe = FPM_PROBE_NONE;
+    ctx->last_index_cut = false;
+    ctx->last_indexed = ctx->last_entries = 0;
     ctx->last_events = 0;
     ctx->last_cand = 0;
     if (n_pairs == 0) {

@@ -146,13 +146,15 @@ enum CtrWord : uint32_t {
     kCtrCand = 65,         // candidates the probe appended
     kCtrUnsorted = 66,     // flag: some row is unsorted / carries duplicates
     kCtrOverflow = 67,     // flag: a one-pass index build overflowed a partition slot
-    kCtrKmax = 68,         // the largest indexed key (the bucket scale)
-    kCtrCandOver = 69,     // flag: a probe ran past its candidate buffer (only a speculated one can)
-    kCtrKmaxAcc = 72,      // ..73: idx_kmax_kernel's accumulator, kept at zero between calls
-    kCtrContain = 74,      // contain: low u32 the not-ascending flag, high u32 the longest query row
+    kCtrIndexed = 68,      // entries the index build indexed (fewer than kCtrEntries when cut)
+    kCtrEntries = 69,      // entries the indexed rows hold
+    kCtrKmax = 70,         // the largest indexed key (the bucket scale)
+    kCtrCandOver = 71,     // flag: a probe ran past its candidate buffer (only a speculated one can)
+    kCtrKmaxAcc = 72,      // ..74: idx_kmax_kernel's accumulators, kept at zero between calls
+    kCtrContain = 75,      // contain: low u32 the not-ascending flag, high u32 the longest query row
     kCtrWords = 80,
     kCtrProbeWords = kCtrOverflow,   // [0, 67): cleared before, and read after, a probe count
-    kCtrBuildWords = kCtrKmax,       // [0, 68): published after an index build
+    kCtrBuildWords = kCtrKmax,       // [0, 70): published after an index build
     kCtrZeroWords = kCtrKmaxAcc      // [0, 72): cleared by the index build's first kernel
 };
 
@@ -174,6 +176,11 @@ struct fpm_ctx {
     int last_kernel = FPM_DK_NONE;   // fpm_ctx_last_dist_kernel
     bool probe_half = true;          // fpm_ctx_set_probe_half (FPM_PROBE_HALF=0 starts it off)
     int last_probe = FPM_PROBE_NONE; // fpm_ctx_last_dist_probe
+    bool index_cut = true;           // fpm_ctx_set_index_cut (FPM_INDEX_CUT=0 starts it off)
+    // fpm_ctx_last_index_cut: the last compare's index left out the values no half probe can
+    // reach, the entries it holds and the entries its rows hold (0 / 0: no index was built)
+    bool last_index_cut = false;
+    uint64_t last_indexed = 0, last_entries = 0;
     int contain_mode = FPM_CONTAIN_AUTO;        // fpm_ctx_set_contain_mode
     int last_contain_kernel = FPM_CK_NONE;      // fpm_ctx_last_contain_kernel
     uint64_t last_events = 0, last_cand = 0;
@@ -278,6 +285,8 @@ inline bool host_flag(const fpm_ctx *ctx, CtrWord w)
 }
 inline bool host_unsorted(const fpm_ctx *ctx) { return host_flag(ctx, kCtrUnsorted); }
 inline bool host_overflow(const fpm_ctx *ctx) { return host_flag(ctx, kCtrOverflow); }
+inline uint64_t host_indexed(const fpm_ctx *ctx) { return ctx->host_counters[kCtrIndexed]; }
+inline uint64_t host_entries(const fpm_ctx *ctx) { return ctx->host_counters[kCtrEntries]; }
 
 #pragma GCC visibility pop
 

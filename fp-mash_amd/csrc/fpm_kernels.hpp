@@ -190,6 +190,11 @@ struct IdxGeom {
     // position is inside its own row's visited prefix, pos < (len >= S ? (S + 1) / 2 : len);
     // 0 = no cut, every entry flagged (record-row indexes)
     uint32_t cut;
+    // value cut (needs cut != 0; an index probed by the half form only): *kmax is V*, the
+    // largest value any row's visited prefix holds, max over rows of row[H_r - 1], and cells
+    // whose key exceeds it are left out of the index (no probed hash can equal them).  0 = every
+    // entry indexed, *kmax from the rows' last entries
+    uint32_t vcut;
 };
 // entries of the level-1 staging buffer `tent` the build needs
 uint64_t idx_tent_words(const IdxGeom &g, uint64_t E);
@@ -200,9 +205,12 @@ hipError_t launch_idx_build(const void *d_ref, const uint32_t *d_ref_len, uint64
                             unsigned long long *self_events, unsigned long long *zero,
                             uint32_t nzero, unsigned long long *acc, uint32_t *part_fill,
                             uint32_t *overflow, hipStream_t st,
-                            unsigned long long *zero_x = nullptr);
-// zero[0..nzero) (and *zero_x when given) is cleared first; acc[0..1]: two words that start at
+                            unsigned long long *zero_x = nullptr,
+                            unsigned long long *n_entries = nullptr);
+// zero[0..nzero) (and *zero_x when given) is cleared first; acc[0..2]: three words that start at
 // zero and are left at zero.
+// n_entries (may be null, may lie inside zero[]): [0] = the entries indexed (fewer than the
+// rows hold with g.vcut), [1] = the entries the rows hold (sum of the lengths)
 // One-pass build (g.cap != 0): part_fill holds 2^kIdxL1 u32 (cleared by the build), *overflow
 // (inside zero[]) is set when a partition exceeded cap: the index is then unusable and the
 // caller rebuilds with g.cap = 0

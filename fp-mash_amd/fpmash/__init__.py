@@ -89,6 +89,8 @@ SYMBOLS = [
     ("fpm_ctx_last_dist_kernel", C.c_int, [vp, C.POINTER(C.c_int)]),
     ("fpm_ctx_set_probe_half", C.c_int, [vp, C.c_int]),
     ("fpm_ctx_last_dist_probe", C.c_int, [vp, C.POINTER(C.c_int)]),
+    ("fpm_ctx_set_index_cut", C.c_int, [vp, C.c_int]),
+    ("fpm_ctx_last_index_cut", C.c_int, [vp, C.POINTER(C.c_int), u64p, u64p]),
     ("fpm_sketch_batch", C.c_int, [vp, vp, C.c_char_p, u64p, C.c_uint32, u32p, C.c_uint32,
                                    u64p, u32p]),
     ("fpm_sketch_stage", C.c_int, [vp, vp, C.c_char_p, u64p, C.c_uint32, u32p, C.c_uint32,
@@ -679,6 +681,18 @@ class Context:
         f = C.c_int()
         _check(lib().fpm_ctx_last_dist_probe(self.h, C.byref(f)))
         return f.value
+
+    def set_index_cut(self, on=True):
+        """fpm_ctx_set_index_cut: the index of one sorted set against itself leaves out the
+        hashes no half probe can reach (default on; same results)"""
+        _check(lib().fpm_ctx_set_index_cut(self.h, int(on)))
+
+    def last_index_cut(self):
+        """fpm_ctx_last_index_cut: {"cut": whether the last compare's index was cut, "indexed":
+        the entries it holds, "entries": the entries its rows hold} (a test hook)"""
+        c, i, e = C.c_int(), C.c_uint64(), C.c_uint64()
+        _check(lib().fpm_ctx_last_index_cut(self.h, C.byref(c), C.byref(i), C.byref(e)))
+        return {"cut": bool(c.value), "indexed": i.value, "entries": e.value}
 
     # --- sketch -----------------------------------------------------------
     def sketch(self, params, seqs, groups=None, n_groups=None, counts=False, min_copies=1):

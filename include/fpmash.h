@@ -159,6 +159,17 @@ int fpm_ctx_set_probe_half(fpm_ctx *ctx, int on);
 #define FPM_PROBE_FULL 1
 #define FPM_PROBE_HALF 2
 int fpm_ctx_last_dist_probe(fpm_ctx *ctx, int *form);
+/* The index a compare builds for one sorted set against itself, when the half probe will read
+ * it, leaves out every hash above the largest value any row's probed half holds: no probed
+ * hash can equal one.  Resident sets and the record index of unsorted lists are never cut.  On
+ * by default; a context created with FPM_INDEX_CUT=0 in the environment starts with it off.
+ * Same results either way. */
+int fpm_ctx_set_index_cut(fpm_ctx *ctx, int on);
+/* The index of the last compare (a test hook): *cut whether it was cut, *indexed the entries
+ * it holds, *entries the entries its rows hold (equal without a cut; both 0 when the compare
+ * used no index).  Any pointer may be NULL.  From counters the compare already read: no
+ * synchronisation. */
+int fpm_ctx_last_index_cut(fpm_ctx *ctx, int *cut, uint64_t *indexed, uint64_t *entries);
 
 /* ---- k-mer sketch ------------------------------------------------------------
  * Replaces addMinHashes (Sketch.cpp:664-735) + MinHashHeap::tryInsert
