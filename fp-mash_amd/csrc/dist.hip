@@ -2036,4 +2036,32 @@ hipError_t launch_dist_finalize(Counts cnt, const uint64_t *d_ref_length, const 
     return hipGetLastError();
 }
 
+// screen's pValueWithin (CommandScreen.cpp:386-406) for n references, r = setSize / kmerSpace
+// clamped by the caller: 1 at shared = 0, else gsl_cdf_binomial_Q(shared - 1, r, size) =
+// 0 when shared - 1 >= size, else I_r(shared, size - shared + 1)
+__global__ __launch_bounds__(256) void screen_pvalue_kernel(const uint32_t *__restrict__ shared,
+                                                          const uint32_t *__restrict__ size,
+                                                          uint32_t n, double r,
+                                                          double *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t x = shared[i], m = size[i];
+    double p = 1.0;
+    if (x) {
+        const uint32_t k = x - 1;
+        p = k >= m ? 0.0 : beta_P(r, (double)k + 1.0, (double)m - (double)k);
+    }
+    out[i] = p;
+}
+
+hipError_t launch_screen_pvalues(const uint32_t *d_shared, const uint32_t *d_size, uint32_t n,
+                                 double r, double *d_p, hipStream_t st)
+{
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(screen_pvalue_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_shared,
+                       d_size, n, r, d_p);
+    return hipGetLastError();
+}
+
 }  // namespace fpm

@@ -1,7 +1,7 @@
 // fpm_internal.hpp — what the files implementing the C ABI of include/fpmash.h share:
 // the context, its pool / ring / copy helpers, the device scratch slots and the counter block.
 // fpm_ctx.cpp defines the helpers; fpm_sketch_api.cpp, fpm_text_api.cpp, fpm_dist_api.cpp,
-// fpm_contain_api.cpp and fpm_comm.cpp use them.  Nothing declared here is exported from the library.
+// fpm_contain_api.cpp, fpm_screen_api.cpp and fpm_comm.cpp use them.  Nothing declared here is exported from the library.
 #pragma once
 
 #include "fpm_kernels.hpp"
@@ -183,6 +183,7 @@ struct fpm_ctx {
     uint64_t last_indexed = 0, last_entries = 0;
     int contain_mode = FPM_CONTAIN_AUTO;        // fpm_ctx_set_contain_mode
     int last_contain_kernel = FPM_CK_NONE;      // fpm_ctx_last_contain_kernel
+    int last_screen_kernel = FPM_SK_NONE;       // fpm_ctx_last_screen_kernel
     uint64_t last_events = 0, last_cand = 0;
     const unsigned long long *last_cand_dev = nullptr;   // the last sparse call's counter
     hipStream_t last_cand_stream = nullptr;
@@ -308,3 +309,17 @@ struct StageRecords {
 // fpm_sketch_api.cpp: the staging behind fpm_sketch_stage and fpm_sketch_stage_seq
 FPM_HIDDEN int stage_core(fpm_ctx *ctx, const fpm_sketch_params *p, StageRecords &R,
                           fpm_sketch_job **job_out);
+
+// fpm_sketch_api.cpp: what fpm_screen_add_job reads of a staged job (its tiles by class cover
+// every window of its records exactly once; row 0 / count 0 are its first group's sketch)
+struct JobView {
+    fpm_ctx *ctx;
+    SketchKParams kp;
+    uint32_t n_groups;
+    const uint8_t *d_seq;
+    const TileDesc *d_tiles;
+    const uint32_t *class_begin;   // kTileClasses + 1
+    const uint64_t *d_rows;
+    const uint32_t *d_count;
+};
+FPM_HIDDEN void job_view(const fpm_sketch_job *job, JobView *out);

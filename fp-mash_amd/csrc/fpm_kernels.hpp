@@ -372,6 +372,53 @@ hipError_t launch_contain_literal(const void *d_ref, const uint32_t *d_ref_len,
                                   uint32_t hash_bytes, uint32_t *d_common, uint32_t *d_steps,
                                   hipStream_t st);
 
+// screen (screen.hip, screen_table.hpp; the pool pass in sketch.hip; the p-values in dist.hip)
+struct ScreenTable;
+// longest reference row (cells) screen_rows_kernel holds in LDS (48 KB of u32 counters)
+constexpr uint32_t kScreenRowsLdsCap = 12288;
+// table build, part 1: every cell of the database (rows strictly ascending, E cells in all,
+// cell index row * stride + i < 2^32) sorted by key into okey / ocell (E entries each; skey /
+// scell: E entries of staging).  kmax: one u64; hist, start: 2^sbits u32; scan_s:
+// scan_scratch_words(max(2^sbits, E)) u32
+hipError_t launch_screen_sort(const void *d_db, const uint32_t *d_len, uint64_t stride,
+                              uint32_t n_db, uint32_t hash_bytes, uint32_t E, uint32_t sbits,
+                              unsigned long long *kmax, uint32_t *hist, uint32_t *start,
+                              uint32_t *scan_s, uint64_t *skey, uint32_t *scell, uint64_t *okey,
+                              uint32_t *ocell, hipStream_t st);
+// part 2: head[p] = 1 where sorted key p starts a run of equal keys, hx = its exclusive scan,
+// *n_distinct (device) = |U|; the caller reads it and kmax back to size part 3
+hipError_t launch_screen_heads(const uint64_t *okey, uint32_t E, uint32_t *head, uint32_t *hx,
+                               uint32_t *scan_s, uint32_t *n_distinct, hipStream_t st);
+// part 3: U (n entries), ustart (n + 1: the sorted cells [ustart[u], ustart[u + 1]) hold U[u]),
+// slot (per database cell, the layout of the rows: its entry of U), post (per sorted cell: its
+// row) and the directory (2^dbits + 1 entries, shift = clz of the largest key)
+hipError_t launch_screen_compact(const uint64_t *okey, const uint32_t *ocell, const uint32_t *head,
+                                 const uint32_t *hx, uint32_t E, uint64_t stride, uint32_t n,
+                                 uint32_t dbits, uint32_t shift, uint64_t *U, uint32_t *ustart,
+                                 uint32_t *slot, uint32_t *post, uint32_t *dir, hipStream_t st);
+// pool pass: every valid window of the tiles adds 1 to the counter of its key's entry of U
+// (hashSequence, CommandScreen.cpp:280-384); sketch.hip
+hipError_t launch_screen_count(int cls, const uint8_t *d_seq, const TileDesc *d_tiles,
+                               uint32_t n_tiles, const SketchKParams &p, const ScreenTable &t,
+                               hipStream_t st);
+// the same for a plain device array of n keys (no hashing)
+hipError_t launch_screen_hashes(const uint64_t *d_keys, uint64_t n, const ScreenTable &t,
+                                hipStream_t st);
+// per reference: shared and median (d_owner null: every cell; else the cells whose entry the
+// row owns); *lds: the LDS-held instance ran (max_len <= kScreenRowsLdsCap)
+hipError_t launch_screen_rows(const uint32_t *d_slot, const uint32_t *d_len, uint64_t stride,
+                              uint32_t n_db, uint32_t max_len, const uint32_t *d_count,
+                              const uint32_t *d_owner, uint32_t *d_shared, uint32_t *d_median,
+                              hipStream_t st, bool *lds);
+// -w: owner[u] = the holder of entry u that keeps it (0xFFFFFFFF when its counter is 0)
+hipError_t launch_screen_winner(const uint32_t *d_count, const uint32_t *d_ustart,
+                                const uint32_t *d_post, uint32_t n, const double *d_scores,
+                                const uint64_t *d_lengths, uint32_t *d_owner, hipStream_t st);
+// pValueWithin (CommandScreen.cpp:386-406) of n references: 1 when shared is 0, else
+// gsl_cdf_binomial_Q(shared - 1, r, size) by dist.hip's binomial tail
+hipError_t launch_screen_pvalues(const uint32_t *d_shared, const uint32_t *d_size, uint32_t n,
+                                 double r, double *d_p, hipStream_t st);
+
 // The transposed grid of a rectangular compare (fpm_refset_dist_mirror_dev): cell (r, q) at
 // r * n_qry + q holds the pair "query r of the ref set against ref q of the query set".  For
 // sorted distinct lists (numer, denom) is symmetric, and so are distance and p-value.

@@ -1,0 +1,350 @@
+// fpm_screen_api.cpp — the screen part of the C ABI (include/fpmash.h): the table of a sketch
+// database, the pool passes that fill its counters and the pool's bottom-s row, and the
+// per-reference sums, -w and p-values read from them.  The kernels are in screen.hip, the
+// pool pass in sketch.hip (screen_count_kernel), the binomial tail in dist.hip.
+#include "fpm_internal.hpp"
+#include "screen_table.hpp"
+
+struct fpm_screen {
+    fpm_ctx *ctx = nullptr;
+    uint32_t n_db = 0, s = 0, hash_bytes = 8;
+    uint64_t stride = 0;
+    uint32_t E = 0, max_len = 0;          // cells of the database, its longest row
+    std::vector<uint32_t> h_len;
+    ScreenTable tab;                      // U, dir, count (owned)
+    uint32_t *d_len = nullptr, *d_slot = nullptr, *d_ustart = nullptr, *d_post = nullptr;
+    uint32_t *d_owner = nullptr, *d_shared = nullptr, *d_median = nullptr;
+    // the pool's running bottom-s row: pair[0] (count pcnt[0]); pair[1] takes a job's row and
+    // pair[2] (pcnt[2]) their merge
+    uint64_t *d_pair = nullptr;
+    uint32_t *d_pcnt = nullptr;
+};
+
+namespace {
+
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t get(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+    template <typename T> T *as() { return (T *)p; }
+};
+
+void screen_release(fpm_screen *sc)
+{
+    if (!sc) return;
+    (void)hipSetDevice(sc->ctx->device);
+    for (void *p : {(void *)sc->tab.U, (void *)sc->tab.dir, (void *)sc->tab.count, (void *)sc->d_len,
+                    (void *)sc->d_slot, (void *)sc->d_ustart, (void *)sc->d_post,
+                    (void *)sc->d_owner, (void *)sc->d_shared, (void *)sc->d_median,
+                    (void *)sc->d_pair, (void *)sc->d_pcnt})
+        (void)hipFree(p);
+    delete sc;
+}
+
+int screen_build(fpm_ctx *ctx, const void *d_db, const uint32_t *d_db_len, uint64_t stride,
+                 uint32_t n_db, uint32_t hash_bytes, uint32_t sketch_size, fpm_screen **out)
+{
+    if (!out) return fail(FPM_EINVAL, "fpm_screen_create: null argument");
+    *out = nullptr;
+    if (hash_bytes != 4 && hash_bytes != 8) return fail(FPM_EINVAL, "hash_bytes must be 4 or 8");
+    if (sketch_size < 1) return fail(FPM_EINVAL, "sketch_size must be >= 1");
+    if (n_db && (!d_db || !d_db_len)) return fail(FPM_EINVAL, "fpm_screen_create: null buffer");
+    if ((uint64_t)n_db * stride >= (1ull << 32) || n_db > 0x7FFFFFFFu)
+        return fail(FPM_EINVAL, "fpm_screen_create: n_db * stride must be below 2^32");
+    hipStream_t st = ctx->stream;
+    fpm_screen *sc = new fpm_screen;
+    sc->ctx = ctx;
+    sc->n_db = n_db;
+    sc->s = sketch_size;
+    sc->hash_bytes = hash_bytes;
+    sc->stride = stride;
+    sc->h_len.assign(n_db, 0);
+    auto body = [&]() -> int {
+        const size_t cells = (size_t)n_db * stride;
+        HIP_TRY(hipMalloc((void **)&sc->d_len, std::max<size_t>(n_db, 1) * 4));
+        HIP_TRY(hipMalloc((void **)&sc->d_shared, std::max<size_t>(n_db, 1) * 4));
+        HIP_TRY(hipMalloc((void **)&sc->d_median, std::max<size_t>(n_db, 1) * 4));
+        HIP_TRY(hipMalloc((void **)&sc->d_slot, std::max<size_t>(cells, 1) * 4));
+        HIP_TRY(hipMalloc((void **)&sc->d_pair, (size_t)3 * sketch_size * 8));
+        HIP_TRY(hipMalloc((void **)&sc->d_pcnt, 16));
+        HIP_TRY(hipMemsetAsync(sc->d_pcnt, 0, 16, st));
+        uint64_t E = 0;
+        if (n_db) {
+            HIP_TRY(hipMemcpyAsync(sc->d_len, d_db_len, (size_t)n_db * 4, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(sc->h_len.data(), d_db_len, (size_t)n_db * 4,
+                                   hipMemcpyDeviceToHost, st));
+            // strictly ascending rows (the lookup and the postings rest on it)
+            void *ctr;
+            HIP_TRY(scratch(ctx, kSlotCounters, kCtrWords * 8, &ctr));
+            uint32_t *flag = (uint32_t *)((unsigned long long *)ctr + kCtrContain);
+            HIP_TRY(hipMemsetAsync(flag, 0, 8, st));
+            HIP_TRY(launch_rows_ascending(d_db, d_db_len, stride, n_db, nullptr, nullptr, 0, 0,
+                                          hash_bytes, flag, st));
+            uint32_t host[2] = {0, 0};
+            HIP_TRY(hipMemcpyAsync(host, flag, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            for (uint32_t l : sc->h_len) {
+                if (l > stride) return fail(FPM_EINVAL, "fpm_screen_create: a row is longer than the stride");
+                E += l;
+                sc->max_len = std::max(sc->max_len, l);
+            }
+            if (host[0])
+                return fail(FPM_EINVAL, "fpm_screen_create: a row is not strictly ascending");
+        }
+        sc->E = (uint32_t)E;
+        uint32_t nU = 0;
+        unsigned long long kmax = 0;
+        DevBuf okey, ocell, head, hx, scan_s;
+        if (E) {
+            // ~2 cells per sort bucket
+            uint32_t sbits = 1;
+            while (sbits < 22 && (2ull << sbits) < E) sbits++;
+            const uint64_t nb = 1ull << sbits;
+            DevBuf km, hist, start, skey;
+            HIP_TRY(km.get(16));
+            HIP_TRY(hist.get(nb * 4));
+            HIP_TRY(start.get(nb * 4));
+            HIP_TRY(scan_s.get(scan_scratch_words(std::max<uint64_t>(nb, E)) * 4));
+            HIP_TRY(skey.get(E * 8));
+            HIP_TRY(okey.get(E * 8));
+            HIP_TRY(ocell.get(E * 4));
+            HIP_TRY(head.get(E * 4));
+            HIP_TRY(hx.get(E * 4));
+            HIP_TRY(hipMalloc((void **)&sc->d_post, E * 4));   // the scatter's cells, then the postings
+            HIP_TRY(launch_screen_sort(d_db, d_db_len, stride, n_db, hash_bytes, (uint32_t)E, sbits,
+                                       km.as<unsigned long long>(), hist.as<uint32_t>(),
+                                       start.as<uint32_t>(), scan_s.as<uint32_t>(),
+                                       skey.as<uint64_t>(), sc->d_post, okey.as<uint64_t>(),
+                                       ocell.as<uint32_t>(), st));
+            uint32_t *d_n = km.as<uint32_t>() + 2;
+            HIP_TRY(launch_screen_heads(okey.as<uint64_t>(), (uint32_t)E, head.as<uint32_t>(),
+                                        hx.as<uint32_t>(), scan_s.as<uint32_t>(), d_n, st));
+            HIP_TRY(hipMemcpyAsync(&kmax, km.p, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(&nU, d_n, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        // directory: 2^dbits >= 2 |U| where 24 bits allow
+        uint32_t dbits = 4;
+        while (dbits < 24 && (1ull << dbits) < 2ull * nU) dbits++;
+        sc->tab.n = nU;
+        sc->tab.dbits = dbits;
+        sc->tab.umax = kmax;
+        sc->tab.shift = kmax ? (uint32_t)__builtin_clzll(kmax) : 63u;
+        HIP_TRY(hipMalloc((void **)&sc->tab.U, std::max<size_t>(nU, 1) * 8));
+        HIP_TRY(hipMalloc((void **)&sc->tab.count, std::max<size_t>(nU, 1) * 4));
+        HIP_TRY(hipMalloc((void **)&sc->d_owner, std::max<size_t>(nU, 1) * 4));
+        HIP_TRY(hipMalloc((void **)&sc->d_ustart, ((size_t)nU + 1) * 4));
+        HIP_TRY(hipMalloc((void **)&sc->tab.dir, ((size_t)(1u << dbits) + 1) * 4));
+        HIP_TRY(hipMemsetAsync(sc->tab.count, 0, std::max<size_t>(nU, 1) * 4, st));
+        HIP_TRY(hipMemsetAsync(sc->d_ustart, 0, ((size_t)nU + 1) * 4, st));
+        HIP_TRY(hipMemsetAsync((void *)sc->tab.dir, 0, ((size_t)(1u << dbits) + 1) * 4, st));
+        HIP_TRY(launch_screen_compact(okey.as<uint64_t>(), ocell.as<uint32_t>(), head.as<uint32_t>(),
+                                      hx.as<uint32_t>(), (uint32_t)E, stride, nU, dbits,
+                                      sc->tab.shift, (uint64_t *)sc->tab.U, sc->d_ustart,
+                                      sc->d_slot, sc->d_post, (uint32_t *)sc->tab.dir, st));
+        HIP_TRY(hipStreamSynchronize(st));   // the build's buffers are released on return
+        return FPM_OK;
+    };
+    const int rc = body();
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        screen_release(sc);
+        return rc;
+    }
+    *out = sc;
+    return FPM_OK;
+}
+
+// shared / median of every reference from the counters (owner: the -w pass's, or null)
+int screen_rows(fpm_screen *sc, const uint32_t *d_owner, uint32_t *out_shared, uint32_t *out_median)
+{
+    fpm_ctx *ctx = sc->ctx;
+    hipStream_t st = ctx->stream;
+    ctx->last_screen_kernel = FPM_SK_NONE;
+    if (!sc->n_db) return FPM_OK;
+    bool lds = false;
+    {
+        TimedLaunch tl(ctx, FPM_K_COMPARE, st);
+        HIP_TRY(launch_screen_rows(sc->d_slot, sc->d_len, sc->stride, sc->n_db, sc->max_len,
+                                   sc->tab.count, d_owner, sc->d_shared, sc->d_median, st, &lds));
+        tl.done();
+    }
+    ctx->last_screen_kernel = lds ? FPM_SK_ROWS_LDS : FPM_SK_ROWS_GLOBAL;
+    HIP_TRY(hipStreamSynchronize(st));
+    if (out_shared) HIP_TRY(copy_out(ctx, out_shared, sc->d_shared, (size_t)sc->n_db * 4));
+    if (out_median) HIP_TRY(copy_out(ctx, out_median, sc->d_median, (size_t)sc->n_db * 4));
+    return FPM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fpm_screen_create_dev(fpm_ctx *ctx, const void *d_db, const uint32_t *d_db_len,
+                          uint64_t stride, uint32_t n_db, uint32_t hash_bytes,
+                          uint32_t sketch_size, fpm_screen **out)
+{
+    if (int rc = set_device(ctx)) return rc;
+    return screen_build(ctx, d_db, d_db_len, stride, n_db, hash_bytes, sketch_size, out);
+}
+
+int fpm_screen_create(fpm_ctx *ctx, const void *db, const uint32_t *db_len, uint64_t stride,
+                      uint32_t n_db, uint32_t hash_bytes, uint32_t sketch_size, fpm_screen **out)
+{
+    if (int rc = set_device(ctx)) return rc;
+    if (hash_bytes != 4 && hash_bytes != 8) return fail(FPM_EINVAL, "hash_bytes must be 4 or 8");
+    if (n_db && (!db || !db_len)) return fail(FPM_EINVAL, "fpm_screen_create: null buffer");
+    DevBuf rows, len;
+    const size_t bytes = (size_t)n_db * stride * hash_bytes;
+    hipError_t e = rows.get(bytes);
+    if (e == hipSuccess) e = len.get((size_t)n_db * 4);
+    if (e == hipSuccess && bytes) e = copy_in(ctx, rows.p, db, bytes);
+    if (e == hipSuccess && n_db) e = copy_in(ctx, len.p, db_len, (size_t)n_db * 4);
+    if (e != hipSuccess) return fail(FPM_ENOMEM, std::string("screen staging: ") + hipGetErrorString(e));
+    return screen_build(ctx, rows.p, len.as<uint32_t>(), stride, n_db, hash_bytes, sketch_size, out);
+}
+
+void fpm_screen_free(fpm_screen *sc) { screen_release(sc); }
+
+int fpm_screen_add_job(fpm_screen *sc, fpm_sketch_job *job, void *stream)
+{
+    if (!sc || !job) return fail(FPM_EINVAL, "fpm_screen_add_job: null argument");
+    fpm_ctx *ctx = sc->ctx;
+    if (int rc = set_device(ctx)) return rc;
+    JobView v;
+    job_view(job, &v);
+    if (v.ctx != ctx) return fail(FPM_EINVAL, "fpm_screen_add_job: the job belongs to another context");
+    if (v.n_groups != 1) return fail(FPM_EINVAL, "fpm_screen_add_job: the job must be staged as one group");
+    if (v.kp.s != sc->s) return fail(FPM_EINVAL, "fpm_screen_add_job: the job's sketch size is not the screen's");
+    if ((v.kp.use64 ? 8u : 4u) != sc->hash_bytes)
+        return fail(FPM_EINVAL, "fpm_screen_add_job: the job's hash width is not the database's");
+    hipStream_t st = pick_stream(ctx, stream);
+    if (int rc = fpm_sketch_run(job, st)) return rc;
+    // running row <- bottom-s of (running row, the job's row)
+    const size_t rb = (size_t)sc->s * 8;
+    HIP_TRY(hipMemcpyAsync(sc->d_pair + sc->s, v.d_rows, rb, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(sc->d_pcnt + 1, v.d_count, 4, hipMemcpyDeviceToDevice, st));
+    if (int rc = fpm_sketch_merge_dev(ctx, sc->d_pair, sc->d_pcnt, 2, sc->s, sc->d_pair + 2 * (size_t)sc->s,
+                                      sc->d_pcnt + 2, st))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(sc->d_pair, sc->d_pair + 2 * (size_t)sc->s, rb, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(sc->d_pcnt, sc->d_pcnt + 2, 4, hipMemcpyDeviceToDevice, st));
+    for (int c = 0; c < kTileClasses; c++) {
+        const uint32_t b = v.class_begin[c], n = v.class_begin[c + 1] - b;
+        if (!n) continue;
+        TimedLaunch tl(ctx, FPM_K_SCREEN, st);
+        HIP_TRY(launch_screen_count(c, v.d_seq, v.d_tiles + b, n, v.kp, sc->tab, st));
+        tl.done();
+    }
+    return FPM_OK;
+}
+
+int fpm_screen_add_hashes_dev(fpm_screen *sc, const uint64_t *d_keys, uint64_t n, void *stream)
+{
+    if (!sc || (n && !d_keys)) return fail(FPM_EINVAL, "fpm_screen_add_hashes_dev: null argument");
+    if (int rc = set_device(sc->ctx)) return rc;
+    HIP_TRY(launch_screen_hashes(d_keys, n, sc->tab, pick_stream(sc->ctx, stream)));
+    return FPM_OK;
+}
+
+int fpm_screen_set_size(fpm_screen *sc, uint64_t *set_size)
+{
+    if (!sc || !set_size) return fail(FPM_EINVAL, "fpm_screen_set_size: null argument");
+    fpm_ctx *ctx = sc->ctx;
+    if (int rc = set_device(ctx)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    uint32_t len = 0;
+    HIP_TRY(copy_out(ctx, &len, sc->d_pcnt, 4));
+    *set_size = 0;
+    if (!len) return FPM_OK;
+    uint64_t top = 0;
+    HIP_TRY(copy_out(ctx, &top, sc->d_pair + (len - 1), 8));
+    // MinHashHeap::estimateSetSize (MinHashHeap.h:45), truncated as CommandTaxScreen.cpp:370 stores it
+    const double range = sc->hash_bytes == 8 ? 18446744073709551616.0 : 4294967296.0;
+    const double e = range * (double)len / (double)top;
+    *set_size = e < 18446744073709551616.0 ? (uint64_t)e : ~0ULL;
+    return FPM_OK;
+}
+
+int fpm_screen_counts(fpm_screen *sc, uint64_t *out_keys, uint32_t *out_counts, uint64_t *n_distinct)
+{
+    if (!sc || !n_distinct) return fail(FPM_EINVAL, "fpm_screen_counts: null argument");
+    fpm_ctx *ctx = sc->ctx;
+    if (int rc = set_device(ctx)) return rc;
+    *n_distinct = sc->tab.n;
+    if (!sc->tab.n) return FPM_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    if (out_keys) HIP_TRY(copy_out(ctx, out_keys, sc->tab.U, (size_t)sc->tab.n * 8));
+    if (out_counts) HIP_TRY(copy_out(ctx, out_counts, sc->tab.count, (size_t)sc->tab.n * 4));
+    return FPM_OK;
+}
+
+int fpm_screen_rows(fpm_screen *sc, uint32_t *out_shared, uint32_t *out_median)
+{
+    if (!sc) return fail(FPM_EINVAL, "fpm_screen_rows: null argument");
+    if (int rc = set_device(sc->ctx)) return rc;
+    HIP_TRY(hipDeviceSynchronize());   // pool passes may have run on other streams
+    return screen_rows(sc, nullptr, out_shared, out_median);
+}
+
+int fpm_screen_rows_winner(fpm_screen *sc, const double *scores, const uint64_t *lengths,
+                           uint32_t *out_shared, uint32_t *out_median)
+{
+    if (!sc || (sc->n_db && (!scores || !lengths)))
+        return fail(FPM_EINVAL, "fpm_screen_rows_winner: null argument");
+    fpm_ctx *ctx = sc->ctx;
+    if (int rc = set_device(ctx)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (!sc->n_db) return screen_rows(sc, nullptr, out_shared, out_median);
+    DevBuf ds, dl;
+    hipError_t e = ds.get((size_t)sc->n_db * 8);
+    if (e == hipSuccess) e = dl.get((size_t)sc->n_db * 8);
+    if (e == hipSuccess) e = copy_in(ctx, ds.p, scores, (size_t)sc->n_db * 8);
+    if (e == hipSuccess) e = copy_in(ctx, dl.p, lengths, (size_t)sc->n_db * 8);
+    if (e != hipSuccess) return fail(FPM_ENOMEM, std::string("screen -w staging: ") + hipGetErrorString(e));
+    HIP_TRY(launch_screen_winner(sc->tab.count, sc->d_ustart, sc->d_post, sc->tab.n, ds.as<double>(),
+                                 dl.as<uint64_t>(), sc->d_owner, ctx->stream));
+    return screen_rows(sc, sc->d_owner, out_shared, out_median);
+}
+
+int fpm_screen_pvalues(fpm_screen *sc, const uint32_t *shared, double kmer_space, double *out_p)
+{
+    if (!sc || (sc->n_db && (!shared || !out_p)))
+        return fail(FPM_EINVAL, "fpm_screen_pvalues: null argument");
+    fpm_ctx *ctx = sc->ctx;
+    uint64_t set_size = 0;
+    if (int rc = fpm_screen_set_size(sc, &set_size)) return rc;
+    if (!sc->n_db) return FPM_OK;
+    double r = (double)set_size / kmer_space;
+    r = std::max(0.0, std::min(1.0, r));
+    DevBuf dsh, dp;
+    hipError_t e = dsh.get((size_t)sc->n_db * 4);
+    if (e == hipSuccess) e = dp.get((size_t)sc->n_db * 8);
+    if (e == hipSuccess) e = copy_in(ctx, dsh.p, shared, (size_t)sc->n_db * 4);
+    if (e != hipSuccess) return fail(FPM_ENOMEM, std::string("screen p-value staging: ") + hipGetErrorString(e));
+    {
+        TimedLaunch tl(ctx, FPM_K_FINALIZE, ctx->stream);
+        HIP_TRY(launch_screen_pvalues(dsh.as<uint32_t>(), sc->d_len, sc->n_db, r, dp.as<double>(),
+                                      ctx->stream));
+        tl.done();
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(copy_out(ctx, out_p, dp.p, (size_t)sc->n_db * 8));
+    return FPM_OK;
+}
+
+int fpm_ctx_last_screen_kernel(fpm_ctx *ctx, int *kernel)
+{
+    if (!ctx || !kernel) return fail(FPM_EINVAL, "null argument");
+    *kernel = ctx->last_screen_kernel;
+    return FPM_OK;
+}
+
+int fpm_screen_lds_cap(fpm_ctx *ctx, uint32_t *cap)
+{
+    if (!ctx || !cap) return fail(FPM_EINVAL, "null argument");
+    *cap = kScreenRowsLdsCap;
+    return FPM_OK;
+}
+
+}  // extern "C"

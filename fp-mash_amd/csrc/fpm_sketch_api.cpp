@@ -154,6 +154,12 @@ static void job_release(fpm_sketch_job *j)
     if (j->h_sel_failed) (void)hipHostFree(j->h_sel_failed);
 }
 
+void job_view(const fpm_sketch_job *j, JobView *out)
+{
+    *out = JobView{j->ctx, j->kp, j->n_groups, j->d_seq, j->d_tiles, j->class_begin, j->d_rows,
+                   j->d_count};
+}
+
 extern "C" {
 
 int fpm_sketch_stage(fpm_ctx *ctx, const fpm_sketch_params *p, const char *seq,

@@ -11,6 +11,7 @@
 // reference heap holds at the end of the stream.
 #include "fpm_device.hpp"
 #include "fpm_kernels.hpp"
+#include "screen_table.hpp"
 
 namespace fpm {
 
@@ -1155,6 +1156,65 @@ hipError_t launch_reads_maxcount(int cls, const uint8_t *d_seq, const TileDesc *
     default: return hipErrorInvalidValue;
     }
 #undef FPM_READS_CASE
+    return hipGetLastError();
+}
+
+// ---- screen: the pool pass (hashSequence, CommandScreen.cpp:280-384).  reads_count_kernel
+// with the group's row replaced by the table over the whole sketch database
+// (screen_table.hpp): every valid window's key that the table holds adds 1 to its entry's
+// counter.  A key above the table's maximum is dropped by one compare as it is hashed (with
+// bottom-s sketches of genomes that is nearly every key, the same cut as hmax above), so no
+// thread holds its E keys in registers.
+template <int P, int K>
+__global__ __launch_bounds__(kBlock) void screen_count_kernel(
+    const uint8_t *__restrict__ seq, const TileDesc *__restrict__ tiles, SketchKParams p,
+    ScreenTable t)
+{
+    using I = TileImg<P>;
+    __shared__ __attribute__((aligned(16))) uint32_t img[I::kBytes / 4];
+    uint8_t *const alpha = reinterpret_cast<uint8_t *>(img + (I::kFBytes + I::kRBytes) / 4 +
+                                                       I::kMaskWords);
+    uint8_t *const compl_tab = alpha + 256;
+    const TileDesc td = tiles[blockIdx.x];
+    const int tid = threadIdx.x;
+    alpha[tid] = p.alphabet[tid];
+    compl_tab[tid] = p.complement[tid];
+    __syncthreads();
+    tile_stage<P>(seq, td, p, img, tid);
+    __syncthreads();
+    const uint64_t umax = t.umax;
+    tile_hash<P, K>(td, p, img, tid, [&](int, uint64_t h) {
+        if (h <= umax) {
+            const uint32_t u = screen_lookup(t, h);
+            if (u != kScreenMiss) atomicAdd(&t.count[u], 1u);
+        }
+    });
+}
+
+hipError_t launch_screen_count(int cls, const uint8_t *d_seq, const TileDesc *d_tiles,
+                               uint32_t n_tiles, const SketchKParams &p, const ScreenTable &t,
+                               hipStream_t st)
+{
+    if (n_tiles == 0 || t.n == 0) return hipSuccess;
+#define FPM_SCREEN_CASE(c, P)                                                                  \
+    case c:                                                                                    \
+        if (p.k == 21)                                                                         \
+            hipLaunchKernelGGL((screen_count_kernel<P, 21>), dim3(n_tiles), dim3(kBlock), 0,    \
+                               st, d_seq, d_tiles, p, t);                                       \
+        else                                                                                   \
+            hipLaunchKernelGGL((screen_count_kernel<P, 0>), dim3(n_tiles), dim3(kBlock), 0, st, \
+                               d_seq, d_tiles, p, t);                                           \
+        break;
+    switch (cls) {
+        FPM_SCREEN_CASE(0, 256)
+        FPM_SCREEN_CASE(1, 512)
+        FPM_SCREEN_CASE(2, 1024)
+        FPM_SCREEN_CASE(3, 2048)
+        FPM_SCREEN_CASE(4, 4096)
+        FPM_SCREEN_CASE(5, 8192)
+    default: return hipErrorInvalidValue;
+    }
+#undef FPM_SCREEN_CASE
     return hipGetLastError();
 }
 

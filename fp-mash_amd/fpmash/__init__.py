@@ -5,6 +5,7 @@ A ctypes mirror of the reference's engine calls for this path:
   -fp line hashing (getHashFingerPrint, hash.cpp:45-73)                    -> Context.fp_hash_lines
   compare/compareSketches/pValue (CommandDistance.cpp:335-450)             -> Context.dist
   contain/containSketches (CommandContain.cpp:314-412)                     -> Context.contain
+  screen: hashSequence, sums, -w, pValueWithin (CommandScreen.cpp:133-406) -> Context.screen
 The shared library is built in-tree (fp-mash_amd/lib/libfpmash.so).  There is no
 CPU fallback: if the library is missing this import fails, and without a gfx950
 device Context() raises FpmError(FPM_ENODEV).
@@ -23,14 +24,15 @@ BIN_PATH = os.path.join(PKG_ROOT, "bin", "fpmash")
 
 FPM_OK, FPM_EINVAL, FPM_ENODEV, FPM_EHIP, FPM_ENOMEM = 0, -1, -2, -3, -4
 (K_SKETCH, K_MERGE, K_FPHASH, K_COMPARE, K_FINALIZE, K_INDEX, K_PROBE, K_FPTEXT, K_FILL,
- K_SEQPARSE) = range(10)
+ K_SEQPARSE, K_SCREEN) = range(11)
 NO_GROUP = 0xFFFFFFFF
 KERNEL_NAMES = {K_SKETCH: "sketch_tiles_kernel", K_MERGE: "merge_kernel",
                 K_FPHASH: "fp_hash_kernel",
                 K_COMPARE: "candidate compare (rank_rows/walk_cand/compare_grid), contain_rows/contain_literal",
                 K_FINALIZE: "dist finalize (dense / candidate cells)", K_INDEX: "dist index build",
                 K_PROBE: "probe_rows_kernel", K_FPTEXT: "fp text parse (nl index + fp_line)",
-                K_FILL: "dist_fill_kernel", K_SEQPARSE: "FASTA parse (seq chunk scan + emit)"}
+                K_FILL: "dist_fill_kernel", K_SEQPARSE: "FASTA parse (seq chunk scan + emit)",
+                K_SCREEN: "screen_count_kernel"}
 DIST_AUTO, DIST_DENSE, DIST_SPARSE = 0, 1, 2
 # fpm_ctx_last_dist_stats path codes
 DIST_PATHS = ["dense walk", "bucket index + literal walk", "bucket index + bucketed rank"]
@@ -48,6 +50,9 @@ CK_NONE, CK_ROWS_LDS, CK_ROWS_GLOBAL, CK_LITERAL = range(4)
 CONTAIN_KERNELS = ["none", "contain_rows_kernel<lds>", "contain_rows_kernel<global>",
                    "contain_literal_kernel"]
 CONTAIN_BLOCK_REFS = 64                          # FPM_CONTAIN_BLOCK_REFS
+# fpm_ctx_last_screen_kernel codes (FPM_SK_*)
+SK_NONE, SK_ROWS_LDS, SK_ROWS_GLOBAL = range(3)
+SCREEN_KERNELS = ["none", "screen_rows_kernel<lds>", "screen_rows_kernel<global>"]
 
 ALPHABET_NUCLEOTIDE = "ACGT"                     # Sketch.h alphabetNucleotide
 ALPHABET_PROTEIN = "ACDEFGHIKLMNPQRSTVWY"         # Sketch.h alphabetProtein
@@ -150,6 +155,20 @@ SYMBOLS = [
     ("fpm_ctx_set_contain_mode", C.c_int, [vp, C.c_int]),
     ("fpm_ctx_last_contain_kernel", C.c_int, [vp, C.POINTER(C.c_int)]),
     ("fpm_contain_lds_cap", C.c_int, [vp, C.c_uint32, u32p]),
+    ("fpm_screen_create", C.c_int, [vp, vp, u32p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                    C.c_uint32, C.POINTER(vp)]),
+    ("fpm_screen_create_dev", C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32,
+                                        C.c_uint32, C.POINTER(vp)]),
+    ("fpm_screen_free", None, [vp]),
+    ("fpm_screen_add_job", C.c_int, [vp, vp, vp]),
+    ("fpm_screen_add_hashes_dev", C.c_int, [vp, vp, C.c_uint64, vp]),
+    ("fpm_screen_set_size", C.c_int, [vp, u64p]),
+    ("fpm_screen_counts", C.c_int, [vp, u64p, u32p, u64p]),
+    ("fpm_screen_rows", C.c_int, [vp, u32p, u32p]),
+    ("fpm_screen_rows_winner", C.c_int, [vp, f64p, u64p, u32p, u32p]),
+    ("fpm_screen_pvalues", C.c_int, [vp, u32p, C.c_double, f64p]),
+    ("fpm_ctx_last_screen_kernel", C.c_int, [vp, C.POINTER(C.c_int)]),
+    ("fpm_screen_lds_cap", C.c_int, [vp, u32p]),
     ("fpm_refset_create", C.c_int, [vp, vp, u32p, u64p, C.c_uint64, C.c_uint32, C.c_uint32,
                                     C.c_uint32, C.POINTER(vp)]),
     ("fpm_refset_create_dev", C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32,
@@ -575,6 +594,113 @@ class Comm:
             self.h = None
 
 
+def estimate_identity(common, denom, k):
+    """estimateIdentity (CommandScreen.cpp:259-278), in double as the reference computes it"""
+    if common == denom:
+        return 1.0
+    if common == 0:
+        return 0.0
+    return (float(common) / float(denom)) ** (1.0 / k)
+
+
+class Screen:
+    """fpm_screen: the table of one sketch database (rows: a 2-D u64 or u32 matrix, lens: the
+    valid entries per row) with its pool counters and the pool's running bottom-s row."""
+
+    def __init__(self, ctx, rows, lens, sketch_size):
+        rows = np.ascontiguousarray(rows)
+        if rows.dtype not in (np.uint64, np.uint32):
+            raise ValueError("Screen: rows must be u64 or u32")
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        self.ctx, self.n, self.s = ctx, len(lens), int(sketch_size)
+        self.use64 = rows.dtype == np.uint64
+        self.sizes = lens.copy()
+        stride = rows.shape[1] if rows.ndim == 2 else 0
+        h = vp()
+        _check(lib().fpm_screen_create(ctx.h, rows.ctypes.data, _p(lens, u32p), stride, self.n,
+                                       rows.dtype.itemsize, self.s, C.byref(h)))
+        self.h = h.value
+
+    @classmethod
+    def from_lists(cls, ctx, lists, sketch_size, use64=True):
+        R, rl = _dense(lists, max([len(x) for x in lists] + [1]), np.uint64 if use64 else np.uint32)
+        return cls(ctx, R[:len(lists)], rl[:len(lists)], sketch_size)
+
+    def add_job(self, job, stream=None):
+        """fpm_screen_add_job: one slice of the pool, a SketchJob staged as one group"""
+        _check(lib().fpm_screen_add_job(self.h, job.h, stream))
+
+    def add_records(self, params, recs):
+        """one slice of the pool given as records: staged as one group, added, released"""
+        job = SketchJob(self.ctx, params, recs, groups=[0] * len(recs), n_groups=1)
+        try:
+            self.add_job(job)
+            self.ctx.synchronize()
+        finally:
+            job.free()
+
+    def add_hashes(self, keys):
+        """fpm_screen_add_hashes_dev over a host array of u64 keys"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        if not len(keys):
+            return
+        b = DeviceBuffer.from_array(self.ctx, keys)
+        try:
+            _check(lib().fpm_screen_add_hashes_dev(self.h, b.ptr, len(keys), None))
+            self.ctx.synchronize()
+        finally:
+            b.free()
+
+    def set_size(self):
+        v = np.zeros(1, np.uint64)
+        _check(lib().fpm_screen_set_size(self.h, _p(v, u64p)))
+        return int(v[0])
+
+    def counts(self):
+        """-> (U, the sorted distinct union of the rows as u64; its u32 counters)"""
+        n = np.zeros(1, np.uint64)
+        _check(lib().fpm_screen_counts(self.h, None, None, _p(n, u64p)))
+        n = int(n[0])
+        U, c = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint32)
+        nn = np.zeros(1, np.uint64)
+        _check(lib().fpm_screen_counts(self.h, _p(U, u64p), _p(c, u32p), _p(nn, u64p)))
+        return U[:n], c[:n]
+
+    def rows(self):
+        """-> (shared, median) per reference, u32"""
+        sh, me = np.zeros(max(self.n, 1), np.uint32), np.zeros(max(self.n, 1), np.uint32)
+        _check(lib().fpm_screen_rows(self.h, _p(sh, u32p), _p(me, u32p)))
+        return sh[:self.n], me[:self.n]
+
+    def rows_winner(self, scores, lengths):
+        """-w -> (shared, median) over the entries each reference won"""
+        sc = np.ascontiguousarray(scores, dtype=np.float64)
+        le = np.ascontiguousarray(lengths, dtype=np.uint64)
+        if len(sc) != self.n or len(le) != self.n:
+            raise ValueError("rows_winner: one score and one length per reference")
+        sh, me = np.zeros(max(self.n, 1), np.uint32), np.zeros(max(self.n, 1), np.uint32)
+        _check(lib().fpm_screen_rows_winner(self.h, _p(sc, f64p), _p(le, u64p), _p(sh, u32p),
+                                            _p(me, u32p)))
+        return sh[:self.n], me[:self.n]
+
+    def pvalues(self, shared, kmer_space):
+        sh = np.ascontiguousarray(shared, dtype=np.uint32)
+        out = np.zeros(max(self.n, 1), np.float64)
+        _check(lib().fpm_screen_pvalues(self.h, _p(sh, u32p), float(kmer_space), _p(out, f64p)))
+        return out[:self.n]
+
+    def free(self):
+        if self.h:
+            lib().fpm_screen_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Context:
     """One gfx950 device (fpm_ctx)."""
 
@@ -904,6 +1030,45 @@ class Context:
         _check(lib().fpm_contain_dev(self.h, d_ref, d_ref_len, ref_stride, n_ref, d_qry,
                                      d_qry_len, qry_stride, n_qry, 8 if use64 else 4, d_common,
                                      d_steps, stream))
+
+    # --- screen -------------------------------------------------------------
+    def last_screen_kernel(self):
+        """fpm_ctx_last_screen_kernel: the screen_rows_kernel instance of the last rows call (an
+        SK_* code; a test hook)"""
+        k = C.c_int()
+        _check(lib().fpm_ctx_last_screen_kernel(self.h, C.byref(k)))
+        return k.value
+
+    def screen_lds_cap(self):
+        """fpm_screen_lds_cap: the longest reference row screen_rows_kernel holds in LDS"""
+        v = np.zeros(1, np.uint32)
+        _check(lib().fpm_screen_lds_cap(self.h, _p(v, u32p)))
+        return int(v[0])
+
+    def screen(self, params, db_lists, pool, lengths=None, winner=False, slices=1):
+        """The documented `mash screen` over a database (lists of ascending hashes, cut to the
+        sketch size) and a pool of records, given to the device in `slices` parts -> dict:
+        shared, median, size (u32 per reference), identity, pvalue (float64), set_size.
+        winner: -w, with lengths the references' Reference::length."""
+        k, s = int(params.kmer_size), int(params.sketch_size)
+        n_alpha = int(sum(params.alphabet))
+        sc = Screen.from_lists(self, [l[:s] for l in db_lists], s, use64=bool(params.use64))
+        try:
+            step = max(1, -(-len(pool) // max(slices, 1)))
+            for at in range(0, len(pool), step):
+                sc.add_records(params, pool[at:at + step])
+            shared, median = sc.rows()
+            if winner:
+                scores = [estimate_identity(int(c), int(d), k) for c, d in zip(shared, sc.sizes)]
+                shared, median = sc.rows_winner(scores, lengths if lengths is not None
+                                                else [0] * sc.n)
+            pv = sc.pvalues(shared, float(n_alpha) ** k)
+            ident = np.array([estimate_identity(int(c), int(d), k)
+                              for c, d in zip(shared, sc.sizes)], np.float64)
+            return {"shared": shared, "median": median, "size": sc.sizes.copy(),
+                    "identity": ident, "pvalue": pv, "set_size": sc.set_size()}
+        finally:
+            sc.free()
 
     def dist16(self, ref_lists, qry_lists, sketch_size, use64=True, k=21, kmer_space=None,
                ref_lengths=None, qry_lengths=None, max_dist=-1.0, max_pvalue=-1.0):

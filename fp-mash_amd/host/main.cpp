@@ -1,8 +1,9 @@
 // main.cpp — `fpmash`: the reference's CLI entry (mash.cpp:19-40) for the hot-path
-// verbs.  `fpmash sketch|dist|info|paste|triangle|contain [-fp] ...` is a drop-in for the same
+// verbs.  `fpmash sketch|dist|info|paste|triangle|contain|screen [-fp] ...` is a drop-in for the same
 // `mash` verbs.
 #include "Command.h"
 #include "CommandContain.h"
+#include "CommandScreen.h"
 #include "Timing.h"
 
 #include <cstdio>
@@ -27,6 +28,7 @@ int main(int argc, const char **argv)
     commandList.addCommand(new fpmhost::CommandPaste());
     commandList.addCommand(new fpmhost::CommandTriangle());
     commandList.addCommand(new fpmhost::CommandContain());
+    commandList.addCommand(new fpmhost::CommandScreen());
     const int rc = commandList.run(argc, argv);
     fpmhost::phaseMark("command done");
     // Every output is written and the device work is complete (results were fetched): leave

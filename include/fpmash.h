@@ -107,7 +107,8 @@ int fpm_memset(fpm_ctx *ctx, void *dptr, int value, size_t bytes);
 #define FPM_K_FPTEXT 7
 #define FPM_K_FILL 8
 #define FPM_K_SEQPARSE 9
-#define FPM_K_COUNT 10
+#define FPM_K_SCREEN 10   /* screen: the pool count pass (screen_count_kernel) */
+#define FPM_K_COUNT 11
 /* one-pass bucket-index builds (dist_index.hip) that overflowed a level-1 slot and were
  * redone by the exact two-pass build, since the context was created */
 int fpm_ctx_index_rebuilds(fpm_ctx *ctx, uint64_t *count);
@@ -595,6 +596,70 @@ int fpm_ctx_last_contain_kernel(fpm_ctx *ctx, int *kernel);
 int fpm_contain_lds_cap(fpm_ctx *ctx, uint32_t hash_bytes, uint32_t *cap);
 /* ref rows one contain_rows_kernel workgroup takes (one wave per row at a time) */
 #define FPM_CONTAIN_BLOCK_REFS 64
+
+/* ---- screen -------------------------------------------------------------------------
+ * The documented `mash screen` (doc/man/mash-screen.1): how much of each sketch of a database
+ * is in a pool of sequences, and at what depth.  The fork's CommandScreen::run no longer
+ * streams the pool; these calls replace the parts of the verb that are intact in the tree:
+ *   the hashTable / hashCounts maps over the database    CommandScreen.cpp:87-102
+ *   hashSequence, every window's key counted             CommandScreen.cpp:280-384
+ *   the pool's one MinHashHeap and its set size          CommandTaxScreen.cpp:347-370,
+ *                                                        MinHashHeap.h:45
+ *   shared counts, depths, medians                       CommandScreen.cpp:133-151, 208-211, 235
+ *   -w                                                   CommandScreen.cpp:153-202
+ *   pValueWithin                                         CommandScreen.cpp:386-406
+ * estimateIdentity (:259-278) stays with the caller, in double.
+ *
+ * A screen holds the table of one database: U, the sorted distinct union of its rows (rows
+ * as in fpm_compare_grid, cut by the caller to the sketch size), a u32 counter per entry of U
+ * (the reference's atomic<uint32_t>: it wraps at 2^32) and the running bottom-sketch_size row
+ * of the pool.  Every row must be strictly ascending within its length, else FPM_EINVAL (-fp
+ * made sketches).  n_db * stride must be below 2^32.  _create copies host rows, _create_dev
+ * reads device rows; neither keeps them.  Both synchronise.  No CPU fallback. */
+typedef struct fpm_screen fpm_screen;
+int fpm_screen_create(fpm_ctx *ctx, const void *db, const uint32_t *db_len, uint64_t stride,
+                      uint32_t n_db, uint32_t hash_bytes, uint32_t sketch_size, fpm_screen **out);
+int fpm_screen_create_dev(fpm_ctx *ctx, const void *d_db, const uint32_t *d_db_len,
+                          uint64_t stride, uint32_t n_db, uint32_t hash_bytes,
+                          uint32_t sketch_size, fpm_screen **out);
+void fpm_screen_free(fpm_screen *sc);
+/* One slice of the pool (CommandTaxScreen.cpp:262-329 hands hashSequence 1 MB at a time): `job`
+ * is a sketch job staged as ONE group with the database's parameters and sketch size
+ * (fpm_sketch_stage / fpm_sketch_stage_seq).  Runs the job, min-merges its row into the
+ * screen's running row (:347-361) and counts every valid window of its tiles.  Counts add and
+ * bottom-s rows merge, so any slicing of a pool into whole records gives the same result. */
+int fpm_screen_add_job(fpm_screen *sc, fpm_sketch_job *job, void *stream);
+/* n keys hashed elsewhere (device u64, u32 hashes zero-extended): counted like window keys;
+ * the set-size row is not touched. */
+int fpm_screen_add_hashes_dev(fpm_screen *sc, const uint64_t *d_keys, uint64_t n, void *stream);
+/* MinHashHeap::estimateSetSize of the pool so far (MinHashHeap.h:45: 2^64, or 2^32 for u32
+ * hashes, x len / max, truncated; 0 for an empty row).  Synchronises. */
+int fpm_screen_set_size(fpm_screen *sc, uint64_t *set_size);
+/* U and its counters (either array may be NULL; *n_distinct is always set).  Synchronises. */
+int fpm_screen_counts(fpm_screen *sc, uint64_t *out_keys, uint32_t *out_counts,
+                      uint64_t *n_distinct);
+/* Per reference i: shared = #{h in row i : count[h] >= 1}, median = the counts of those
+ * hashes in ascending order, at position shared / 2 (0 when shared is 0).  Host outputs. */
+int fpm_screen_rows(fpm_screen *sc, uint32_t *out_shared, uint32_t *out_median);
+/* -w: every entry of U with count >= 1 goes to one of the references that hold it: the
+ * greatest scores[i] (the caller's estimateIdentity of the plain shared counts, compared as
+ * doubles, never recomputed), then the greatest lengths[i] (Reference::length), then the
+ * lowest i.  The reference breaks that last tie by the visiting order of an unordered set;
+ * the lowest index replaces it.  shared / median as above over the entries each reference won. */
+int fpm_screen_rows_winner(fpm_screen *sc, const double *scores, const uint64_t *lengths,
+                           uint32_t *out_shared, uint32_t *out_median);
+/* pValueWithin(shared[i], setSize, kmer_space, size_i) with the screen's current set size; r =
+ * setSize / kmer_space is clamped to [0, 1] without the reference's message (:395-399). */
+int fpm_screen_pvalues(fpm_screen *sc, const uint32_t *shared, double kmer_space, double *out_p);
+/* The instance of screen_rows_kernel the last fpm_screen_rows / _rows_winner launched (a
+ * test hook like fpm_ctx_last_contain_kernel): the reference's counters held in LDS, or
+ * gathered from global memory in every selection pass when the longest row exceeds
+ * fpm_screen_lds_cap cells.  NONE: no reference. */
+#define FPM_SK_NONE 0
+#define FPM_SK_ROWS_LDS 1
+#define FPM_SK_ROWS_GLOBAL 2
+int fpm_ctx_last_screen_kernel(fpm_ctx *ctx, int *kernel);
+int fpm_screen_lds_cap(fpm_ctx *ctx, uint32_t *cap);
 
 /* ---- communicator: RCCL over xGMI for the cross-GPU min-merge ------------------------
  * north_star reserves the collective for "the final min-merge only where the reference set
