@@ -462,6 +462,23 @@ int fpm_seq_records(fpm_seqtext *j, uint32_t *seg_of_rec, uint64_t *hdr_off, uin
     return FPM_OK;
 }
 
+int fpm_seq_packed(fpm_seqtext *j, uint64_t *seq_off, uint8_t *out, uint64_t cap,
+                   uint64_t *n_bytes)
+{
+    if (!j || !n_bytes) return fail(FPM_EINVAL, "seq_packed: null argument");
+    if (int rc = set_device(j->ctx)) return rc;
+    if (!j->d_out) return fail(FPM_EINVAL, "seq_packed: records already staged");
+    const uint64_t n = j->n_rec, bytes = j->total_kept + n;
+    *n_bytes = bytes;
+    if (!out) return FPM_OK;                              // sized by this call
+    if (cap < bytes) return fail(FPM_EINVAL, "seq_packed: buffer too small");
+    // seq_off is the fourth of d_rec's five arrays in both layouts (the FASTA emit strides
+    // them by max(n_rec, 1), the FASTQ emit by n_rec: the same wherever a record exists)
+    if (seq_off) HIP_TRY(d2h_staged(j->ctx, seq_off, j->d_rec + 3 * n, n * 8));
+    HIP_TRY(d2h_staged(j->ctx, out, j->d_out, bytes));
+    return FPM_OK;
+}
+
 void fpm_seq_free(fpm_seqtext *j)
 {
     seqtext_release(j);

@@ -201,6 +201,7 @@ SYMBOLS = [
     ("fpm_seq_parse", C.c_int, [vp, C.POINTER(C.c_char_p), u64p, C.c_uint32, C.POINTER(vp),
                                 u64p, C.POINTER(C.c_int)]),
     ("fpm_seq_records", C.c_int, [vp, u32p, u64p, u64p, u64p]),
+    ("fpm_seq_packed", C.c_int, [vp, u64p, u8p, C.c_uint64, u64p]),
     ("fpm_sketch_stage_seq", C.c_int, [vp, vp, vp, u32p, C.c_uint32, C.POINTER(vp)]),
     ("fpm_seq_free", None, [vp]),
     ("fpm_host_alloc", C.c_int, [vp, C.POINTER(vp), C.c_size_t]),
@@ -884,6 +885,23 @@ class Context:
             raise
         return job.value, {"seg": seg[:n], "hdr_off": ho[:n], "hdr_len": hl[:n],
                            "seq_len": sl[:n]}, bool(q.value)
+
+    def seq_packed(self, seq_job, n_rec=None, cap=None):
+        """fpm_seq_packed: the packed records of a parse handle that has not been staged (a
+        test hook) -> (bytes, seq_off): every record's sequence bytes and one 0x00, and each
+        record's offset.  n_rec: the record count seq_parse returned (default: the 0x00 bytes
+        of the buffer, sequence bytes being isgraph); cap: the buffer size handed over
+        (default: the size the call reports)."""
+        nb = C.c_uint64()
+        _check(lib().fpm_seq_packed(seq_job, None, None, 0, C.byref(nb)))
+        size = nb.value if cap is None else cap
+        out = np.zeros(max(size, 1), np.uint8)
+        # one offset per record; the packed size bounds the record count (a 0x00 each)
+        off = np.zeros(max(nb.value, 1), np.uint64)
+        _check(lib().fpm_seq_packed(seq_job, _p(off, u64p), _p(out, u8p), size, C.byref(nb)))
+        if n_rec is None:
+            n_rec = int(np.count_nonzero(out[:nb.value] == 0))
+        return out[:nb.value].tobytes(), off[:n_rec].copy()
 
     def sketch_seq_job(self, params, seq_job, groups, n_groups):
         """fpm_sketch_stage_seq: the staged SketchJob over parsed records (it takes the packed

@@ -309,13 +309,20 @@ int fpm_sketch_merge_dev(fpm_ctx *ctx, const uint64_t *d_lists, const uint32_t *
  * the header line's length (to its '\n' or the end of the file) and the sequence length.
  * fpm_sketch_stage_seq: a sketch job over the parsed records (group_of_rec[r] as in
  * fpm_sketch_stage, FPM_NO_GROUP = not sketched, e.g. records shorter than k); the job
- * takes over the packed records (stage once per parse). */
+ * takes over the packed records (stage once per parse).
+ * fpm_seq_packed: the packed records themselves, read back (a test hook like
+ * fpm_sketch_job_plan: it launches nothing and leaves the job as it was).  The buffer holds
+ * each record's sequence bytes followed by one 0x00, *n_bytes = the sequence lengths' sum +
+ * the record count in all; seq_off[r] = record r's offset in it.  out == NULL only reports
+ * *n_bytes; FPM_EINVAL where cap < *n_bytes or the job's records were staged already. */
 typedef struct fpm_seqtext fpm_seqtext;
 #define FPM_NO_GROUP 0xFFFFFFFFu
 int fpm_seq_parse(fpm_ctx *ctx, const char *const *seg_text, const uint64_t *seg_len,
                   uint32_t n_seg, fpm_seqtext **job, uint64_t *n_records, int *quality_lines);
 int fpm_seq_records(fpm_seqtext *job, uint32_t *seg_of_rec, uint64_t *hdr_off, uint64_t *hdr_len,
                     uint64_t *seq_len);
+int fpm_seq_packed(fpm_seqtext *job, uint64_t *seq_off, uint8_t *out, uint64_t cap,
+                   uint64_t *n_bytes);
 int fpm_sketch_stage_seq(fpm_ctx *ctx, const fpm_sketch_params *p, fpm_seqtext *seq,
                          const uint32_t *group_of_rec, uint32_t n_groups, fpm_sketch_job **job);
 void fpm_seq_free(fpm_seqtext *job);
