@@ -239,6 +239,8 @@ __global__ __launch_bounds__(256) void fp_line_kernel(
 }
 
 uint32_t text_blocks(uint64_t len) { return (uint32_t)((len + kTextChunk - 1) / kTextChunk); }
+uint32_t fp_text_chunk() { return kTextChunk; }
+uint32_t fp_span_bytes() { return kFpSpan; }
 
 hipError_t launch_fp_nl_count(const uint8_t *d_text, uint64_t len, uint32_t *blk_cnt,
                               uint32_t *blk_off, uint32_t *scan_s, hipStream_t st)
@@ -345,6 +347,7 @@ __global__ __launch_bounds__(256) void fp_ref_len_kernel(
 }
 
 uint32_t fp_head_blocks(uint64_t n_lines) { return (uint32_t)((n_lines + kHeadLines - 1) / kHeadLines); }
+uint32_t fp_head_lines() { return kHeadLines; }
 
 hipError_t launch_fp_heads(const uint8_t *d_new_id, uint64_t n_lines, uint32_t *blk_cnt,
                            uint32_t *blk_off, uint32_t *scan_s, hipStream_t st)

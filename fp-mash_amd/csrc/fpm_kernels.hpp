@@ -290,6 +290,9 @@ hipError_t launch_merge_rows(const uint64_t *d_cand, const uint64_t *row_seg, ui
 
 // -fp CFL text: newline index, then one lane per line (fingerprint.hip)
 uint32_t text_blocks(uint64_t len);
+uint32_t fp_text_chunk();   // text bytes per newline-index workgroup
+uint32_t fp_span_bytes();   // largest wave span fp_line_kernel stages in LDS
+uint32_t fp_head_lines();   // lines per head-count workgroup
 hipError_t launch_fp_nl_count(const uint8_t *d_text, uint64_t len, uint32_t *blk_cnt,
                               uint32_t *blk_off, uint32_t *scan_s, hipStream_t st);
 hipError_t launch_fp_nl_scatter(const uint8_t *d_text, uint64_t len, const uint32_t *blk_off,

@@ -235,6 +235,13 @@ void fpm_fp_text_free(fpm_fptext *j)
     delete j;
 }
 
+void fpm_fp_text_limits(uint32_t *text_chunk, uint32_t *span_bytes, uint32_t *head_lines)
+{
+    if (text_chunk) *text_chunk = fp_text_chunk();
+    if (span_bytes) *span_bytes = fp_span_bytes();
+    if (head_lines) *head_lines = fp_head_lines();
+}
+
 }  // extern "C"
 
 // ----------------------------------------------------------------------------

@@ -124,6 +124,7 @@ SYMBOLS = [
     ("fpm_fp_text_fetch", C.c_int, [vp, u64p, u32p, u32p, vp, u8p]),
     ("fpm_fp_text_refs", C.c_int, [vp, C.c_uint64, u64p, u64p, u64p, u32p, u64p]),
     ("fpm_fp_text_free", None, [vp]),
+    ("fpm_fp_text_limits", None, [u32p, u32p, u32p]),
     ("fpm_compare_grid", C.c_int, [vp, vp, u32p, C.c_uint64, C.c_uint32, vp, u32p, C.c_uint64,
                                    C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p]),
     ("fpm_compare_grid_dev", C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64,
@@ -324,6 +325,14 @@ def device_count():
     n = C.c_int(0)
     _check(lib().fpm_device_count(C.byref(n)))
     return n.value
+
+
+def fp_text_limits():
+    """(text bytes per newline-index workgroup, largest wave span fp_line_kernel stages in
+    LDS, lines per head-count workgroup) of the -fp text kernels (fpm_fp_text_limits)."""
+    c, s, h = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    lib().fpm_fp_text_limits(C.byref(c), C.byref(s), C.byref(h))
+    return c.value, s.value, h.value
 
 
 def _p(a, t):

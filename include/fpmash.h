@@ -364,6 +364,11 @@ int fpm_fp_text_fetch(fpm_fptext *job, uint64_t *id_off, uint32_t *id_len, uint3
 int fpm_fp_text_refs(fpm_fptext *job, uint64_t cap, uint64_t *n_refs, uint64_t *first_line,
                      uint64_t *id_off, uint32_t *id_len, uint64_t *length);
 void fpm_fp_text_free(fpm_fptext *job);
+/* The sizes the -fp text kernels switch paths at, for tests that build inputs on them (no
+ * device needed; any output may be NULL): text bytes per newline-index workgroup, the largest
+ * wave span (64 lines, from the 16-byte block of the line before them) the line kernel stages
+ * in LDS before it reads global memory instead, and lines per head-count workgroup. */
+void fpm_fp_text_limits(uint32_t *text_chunk, uint32_t *span_bytes, uint32_t *head_lines);
 
 /* ---- dist ---------------------------------------------------------------------
  * Replaces compare()/compareSketches()/pValue() (CommandDistance.cpp:335-450) over

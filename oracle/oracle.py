@@ -33,8 +33,11 @@ class Params(C.Structure):
     ]
 
 
-def build():
+def build(force=False):
+    """make in oracle/; force: liboracle.so again whatever the file times say"""
     import subprocess
+    if force:
+        subprocess.run(["make", "-s", "-B", "-C", HERE, "liboracle.so"], check=True)
     subprocess.run(["make", "-s", "-C", HERE], check=True)
 
 
@@ -44,7 +47,16 @@ def lib():
         path = os.path.join(HERE, "liboracle.so")
         if not os.path.exists(path):
             build()
+        else:
+            # a library from before fp_istream.cpp is rebuilt; its symbol names are looked for
+            # in the file, since a second dlopen of one path returns the image already loaded
+            with open(path, "rb") as f:
+                if b"orc_fp_parse_istream" not in f.read():
+                    build(force=True)
         L = C.CDLL(path)
+        L.orc_fp_parse_istream.restype = C.c_uint64
+        L.orc_fp_parse_istream.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, u64p, C.c_uint64,
+                                           C.c_uint64, u64p, u32p, u64p, u64p]
         L.orc_get_hash.restype = C.c_uint64
         L.orc_get_hash.argtypes = [C.c_char_p, C.c_int, C.c_uint32, C.c_int]
         L.orc_get_hash_fp.restype = C.c_uint64
@@ -253,6 +265,27 @@ def sketch_batch(P, seqs, groups=None, n_groups=None, threads=1, counts=False):
 
 def fp_parse(text: bytes, limit=1_000_000, lines_used=0):
     """-> (ids list[bytes], values list[np.uint64 array], lines_used)."""
+    id_off, id_len, vals, lvo, used = fp_parse_arrays(text, limit, lines_used)
+    return _fp_ids(text, id_off, id_len), \
+        [vals[int(lvo[i]):int(lvo[i + 1])].copy() for i in range(len(id_off))], used
+
+
+def fp_parse_istream(text: bytes, limit=1_000_000, lines_used=0):
+    """fp_parse through libstdc++'s own getline / `ss >> id` / `while (ss >> v)`
+    (fp_istream.cpp): the statements fp_parse restates."""
+    id_off, id_len, vals, lvo, used = fp_parse_arrays(text, limit, lines_used, istream=True)
+    return _fp_ids(text, id_off, id_len), \
+        [vals[int(lvo[i]):int(lvo[i + 1])].copy() for i in range(len(id_off))], used
+
+
+def _fp_ids(text, id_off, id_len):
+    return [text[int(o):int(o) + int(n)] for o, n in zip(id_off, id_len)]
+
+
+def fp_parse_arrays(text: bytes, limit=1_000_000, lines_used=0, istream=False):
+    """The parse as arrays: (ID offset u64[n], ID length u32[n], values u64[], line l's values
+    at [lvo[l], lvo[l + 1]), lines_used); istream: through fp_istream.cpp."""
+    fn = lib().orc_fp_parse_istream if istream else lib().orc_fp_parse
     n_max = text.count(b"\n") + 1
     v_max = len(text) // 2 + 1
     id_off = np.zeros(n_max, dtype=np.uint64)
@@ -260,11 +293,10 @@ def fp_parse(text: bytes, limit=1_000_000, lines_used=0):
     vals = np.zeros(v_max, dtype=np.uint64)
     lvo = np.zeros(n_max + 1, dtype=np.uint64)
     used = C.c_uint64(lines_used)
-    n = lib().orc_fp_parse(text, len(text), limit, C.byref(used), n_max, v_max,
-                           _p(id_off, u64p), _p(id_len, u32p), _p(vals, u64p), _p(lvo, u64p))
-    ids = [text[int(id_off[i]):int(id_off[i]) + int(id_len[i])] for i in range(n)]
-    vl = [vals[int(lvo[i]):int(lvo[i + 1])].copy() for i in range(n)]
-    return ids, vl, used.value
+    n = fn(text, len(text), limit, C.byref(used), n_max, v_max,
+           _p(id_off, u64p), _p(id_len, u32p), _p(vals, u64p), _p(lvo, u64p))
+    assert n <= n_max, "the ID the stream read is not the line's first non-space run"
+    return id_off[:n], id_len[:n], vals[:int(lvo[n])], lvo[:n + 1], used.value
 
 
 def fp_references(text: bytes, seed=42, limit=1_000_000, lines_used=0, last_id=b""):

@@ -409,6 +409,37 @@ def test_dist_fp_msh_and_table(tmp_path, oracle):
             assert c == "%g" % oracle.distance(nu, de, 1)
 
 
+@pytest.mark.gpu
+def test_sketch_fp_line_cap_across_files(tmp_path, oracle):
+    """`sketch -fp a.txt b.txt`: the 1,000,000-line cap runs over the files together.  a has
+    999,998 lines without values, so b gives its first two lines and its third is absent."""
+    (tmp_path / "a.txt").write_bytes(b"a\n" * 999_998)
+    (tmp_path / "b.txt").write_bytes(b"b 1\nb 2\nb 3\nc 4\nc 5\n")
+    run(["sketch", "-fp", "a.txt", "b.txt", "-o", "ab"], cwd=tmp_path)
+    refs = mshfmt.read_msh(str(tmp_path / "ab.msh"))["references"]
+    h = [oracle.get_hash_fp(v, 42, False) for v in ([], [1], [2], [3])]
+    assert len({*h}) == 4
+    assert [r["name"] for r in refs] == [b"a", b"b"]
+    assert sum(len(r["hashes32"]) for r in refs) == 1_000_000
+    assert len(refs[0]["hashes32"]) == 999_998 and (refs[0]["hashes32"] == h[0]).all()
+    assert list(refs[1]["hashes32"]) == h[1:3]
+    assert [r["length"] for r in refs] == [0, 3]
+
+
+@pytest.mark.gpu
+def test_sketch_fp_id_continued_across_files(tmp_path):
+    """a second file whose first ID is the first file's last: the reference dereferences a null
+    Reference there; the CLI says so and exits non-zero"""
+    (tmp_path / "a.txt").write_bytes(b"x 1\ny 2\ny 3\n")
+    (tmp_path / "b.txt").write_bytes(b"y 4\nz 5\n")
+    p = run(["sketch", "-fp", "a.txt", "b.txt", "-o", "ab"], cwd=tmp_path, check=False)
+    assert p.returncode != 0
+    assert b'fingerprint line 1 of b.txt continues ID "y" from a previous file.' in p.stderr
+    assert not (tmp_path / "ab.msh").exists()
+    p = run(["sketch", "-fp", "b.txt", "a.txt", "-o", "ba"], cwd=tmp_path)
+    assert (tmp_path / "ba.msh").exists()
+
+
 # ----------------------------------------------------------------------------- paste
 
 
