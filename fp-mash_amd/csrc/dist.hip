@@ -25,6 +25,7 @@
 #include <float.h>
 
 #include <algorithm>
+#include <type_traits>
 
 namespace fpm {
 
@@ -389,14 +390,22 @@ __device__ __forceinline__ uint64_t rank_chunk(const uint64_t *Bs, const uint32_
     }
 }
 
-template <int CAP, typename C>
+// CMP (one set against itself whose half probe wrote the compacted rows, CmpRows): candidate
+// r is streamed from its compacted copy, which leaves out the values of its probed prefix that
+// no other row holds.  Such a value is not in B, so it shares nothing; all it did was to raise
+// the position i of the values behind it, and those carry their original position: the union
+// rank of a kept value stays pos + j - k, exact, and still increases with the value, so the
+// early exit holds as it is while a chunk of 128 kept values spans more of the row.  The
+// diagonal (r == q) cannot be ranked that way, its dropped values are all in B, and needs no
+// ranking: numer = min(S, lb), every value shared.
+template <int CAP, typename C, bool CMP = false>
 __global__ __launch_bounds__(64 * kRankWaves) void rank_rows_kernel(
     const uint64_t *__restrict__ cand, const uint64_t *__restrict__ row_seg, uint32_t n_qry,
     uint32_t q_lo, const uint64_t *__restrict__ ref, const uint32_t *__restrict__ ref_len,
     uint64_t ref_stride, uint32_t n_ref, const uint64_t *__restrict__ qry,
     const uint32_t *__restrict__ qry_len, uint64_t qry_stride, uint32_t S, uint32_t sym,
     C *__restrict__ numer, C *__restrict__ denom, uint32_t *__restrict__ cnum,
-    uint32_t *__restrict__ cden)
+    uint32_t *__restrict__ cden, CmpRows cm)
 {
     constexpr uint32_t kLogBuckets = (CAP <= 1024) ? kRankLogB : kRankLogB + 1;
     constexpr uint32_t kBuckets = 1u << kLogBuckets;
@@ -515,21 +524,29 @@ __global__ __launch_bounds__(64 * kRankWaves) void rank_rows_kernel(
     // a candidate starts); the groups after an early exit are never loaded.
     constexpr int kGroup = 1;      // chunks per load group (2 and 4 measured slower)
     constexpr uint32_t kChunk = 128;
-    struct Row { __amdgpu_buffer_rsrc_t rsrc; uint32_t la; uint64_t o; };
+    // CMP: the row's block of the compacted rows, values then positions, under one descriptor
+    // (the positions of chunk t: one dword per lane at byte ld * 8 + (64 t + lane) * 4, the
+    // block's own stride being ref_stride = ld); lc = the entries to stream, none on the diagonal
+    struct Row { __amdgpu_buffer_rsrc_t rsrc; uint32_t la, lc; uint64_t o; };
+    const uint32_t row_bytes = CMP ? (uint32_t)cmp_row_bytes(ref_stride) : ld * 8u;
     auto open_row = [&](uint64_t o) -> Row {
         const uint32_t rr = __builtin_amdgcn_readfirstlane((uint32_t)(o - pair_row));
-        const uintptr_t Ar = (uintptr_t)(ref + (uint64_t)rr * ref_stride);
+        const uintptr_t Ar = CMP ? (uintptr_t)cm.rows + (uint64_t)rr * row_bytes
+                                 : (uintptr_t)(ref + (uint64_t)rr * ref_stride);
         const uint32_t plo = __builtin_amdgcn_readfirstlane((uint32_t)Ar);
         const uint32_t phi = __builtin_amdgcn_readfirstlane((uint32_t)(Ar >> 32));
         Row R;
         R.rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(((uintptr_t)phi << 32) | plo), 0,
-                                                   (int)__builtin_amdgcn_readfirstlane(ld * 8u),
+                                                   (int)__builtin_amdgcn_readfirstlane(row_bytes),
                                                    0x00020000);
         R.la = ref_len[rr];
+        R.lc = CMP ? (rr == q ? 0u : cm.len[rr]) : R.la;
         R.o = o;
         return R;
     };
-    struct Pair { uint64_t e0, e1; };
+    struct PairV { uint64_t e0, e1; };
+    struct PairP { uint64_t e0, e1; uint32_t pp; };      // pp: the positions of e0 | e1 << 16
+    using Pair = std::conditional_t<CMP, PairP, PairV>;
     auto load_group = [&](const Row &R, uint32_t gi, Pair (&dst)[kGroup]) {
 #pragma unroll
         for (int u = 0; u < kGroup; u++) {
@@ -539,6 +556,9 @@ __global__ __launch_bounds__(64 * kRankWaves) void rank_rows_kernel(
                                                                  0, 0);
             dst[u].e0 = ((uint64_t)v0[1] << 32) | v0[0];
             dst[u].e1 = ((uint64_t)v1[1] << 32) | v1[0];
+            if constexpr (CMP)
+                dst[u].pp = __builtin_amdgcn_raw_buffer_load_b32(R.rsrc, (t * 64 + lane) * 4u,
+                                                                 (int)(ld * 8u), 0);
         }
     };
     auto cand_at = [&](uint32_t cc) -> uint64_t {
@@ -558,13 +578,23 @@ __global__ __launch_bounds__(64 * kRankWaves) void rank_rows_kernel(
         uint32_t j0, j1;
         const uint64_t m0 = probe(cur[0].e0, j0);
         const uint64_t m1 = probe(cur[0].e1, j1);
-        const uint32_t i0 = g0 * kChunk;
+        // the positions of the lane's two values in the row (CMP: as stored beside them)
+        uint32_t i0l, i1l, i_last;
+        if constexpr (CMP) {
+            i0l = cur[0].pp & 0xFFFFu;
+            i1l = cur[0].pp >> 16;
+            i_last = last ? 0u : (uint32_t)__builtin_amdgcn_readlane((int)cur[0].pp, 63) >> 16;
+        } else {
+            i0l = g0 * kChunk + lane;
+            i1l = i0l + 64;
+            i_last = g0 * kChunk + (kChunk - 1);
+        }
         const uint64_t a0 = m0 & vm0, a1 = m1 & vm1;
         const uint32_t p0 = (uint32_t)__popcll(a0), p1 = (uint32_t)__popcll(a1);
         uint32_t u_last = 0;
         if (!last) {
             const uint32_t jl = (uint32_t)__builtin_amdgcn_readlane((int)j1, 63);
-            u_last = i0 + (kChunk - 1) + jl -
+            u_last = i_last + jl -
                      (shared_below + p0 + (uint32_t)__popcll(a1 & 0x7FFFFFFFFFFFFFFFULL));
         }
         if (!last && u_last < S) {
@@ -576,7 +606,7 @@ __global__ __launch_bounds__(64 * kRankWaves) void rank_rows_kernel(
                 (uint32_t)(a1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)a1, 0u));
             const uint32_t k0 = shared_below + b0;
             const uint32_t k1 = shared_below + p0 + b1;
-            const uint32_t u0 = i0 + lane + j0 - k0, u1 = i0 + 64 + lane + j1 - k1;
+            const uint32_t u0 = i0l + j0 - k0, u1 = i1l + j1 - k1;
             cnt += __popcll(a0 & __builtin_amdgcn_ballot_w64(u0 < S)) +
                    __popcll(a1 & __builtin_amdgcn_ballot_w64(u1 < S));
         }
@@ -595,14 +625,15 @@ __global__ __launch_bounds__(64 * kRankWaves) void rank_rows_kernel(
             const uint32_t la = R.la;
             const uint64_t o = R.o;
             const bool need_all = la < S && lb < S;       // denom depends on #shared
-            const uint32_t nch = (la + kChunk - 1) / kChunk;
+            const uint32_t ls = R.lc;                     // the entries streamed
+            const uint32_t nch = (ls + kChunk - 1) / kChunk;
             const uint32_t ngr = (nch + kGroup - 1) / kGroup;
             static_assert(kGroup == 1, "the last-chunk masks assume one chunk per group");
             // values past la (row padding) count nothing: in the last chunk (lane l holds
             // A[i0 + l], A[i0 + 64 + l]) the lanes below r0 / r1 hold row values.  Computed once
             // per candidate, selected per chunk (computed in the chunk loop they cost ~20 scalar
             // instructions per chunk: the compiler turns a branch around them into selects)
-            const int rl = (int)la - (int)(nch - 1) * (int)kChunk;          // 1 .. 128
+            const int rl = (int)ls - (int)(nch - 1) * (int)kChunk;          // 1 .. 128
             const int r0 = min(rl, 64), r1 = rl - 64;
             const uint64_t vl0 = r0 >= 64 ? ~0ULL : r0 > 0 ? (1ULL << r0) - 1 : 0ULL;
             const uint64_t vl1 = r1 >= 64 ? ~0ULL : r1 > 0 ? (1ULL << r1) - 1 : 0ULL;
@@ -629,6 +660,10 @@ __global__ __launch_bounds__(64 * kRankWaves) void rank_rows_kernel(
                 const uint64_t x0 = fast ? __builtin_amdgcn_ballot_w64(cur[0].e0 == ~0ULL) : 0;
                 const uint64_t x1 = fast ? __builtin_amdgcn_ballot_w64(cur[0].e1 == ~0ULL) : 0;
                 rank_group(probe, gi * kGroup, true, vl0 & ~x0, vl1 & ~x1, cur, shared_below, cnt);
+            }
+            if constexpr (CMP) {
+                // the diagonal (nothing streamed: lc = 0): every value is shared
+                if ((uint32_t)(o - pair_row) == q) { shared_below = lb; cnt = lb < S ? lb : S; }
             }
             if (lane == 0) {
                 const uint64_t un = (uint64_t)la + lb - shared_below;
@@ -673,19 +708,34 @@ static hipError_t merge_rows_c(const uint64_t *d_cand, const uint64_t *row_seg, 
                                const uint32_t *d_qry_len, uint64_t qry_stride, uint32_t S,
                                bool sym, C *d_numer, C *d_denom, uint32_t *d_cnum,
                                uint32_t *d_cden, hipStream_t st, uint32_t q_lo,
-                               uint32_t *rank_cap)
+                               uint32_t *rank_cap, CmpRows cmp)
 {
     const dim3 g(xcd_grid(n_qry)), b(64 * kRankWaves);
     const uint64_t cap = std::max(ref_stride, qry_stride);
     if (rank_cap) *rank_cap = cap <= 1024 ? 1024u : 2048u;
+    if (cmp.rows) {
+        // the compacted rows of one set against itself, every row's probe behind us
+        if (!cmp.len || !sym || d_ref != d_qry || ref_stride != qry_stride || q_lo != 0 ||
+            n_qry != n_ref || cap > 2048)
+            return hipErrorInvalidValue;
+        if (cap <= 1024)
+            hipLaunchKernelGGL((rank_rows_kernel<1024, C, true>), g, b, 0, st, d_cand, row_seg,
+                               n_qry, q_lo, d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len,
+                               qry_stride, S, (uint32_t)sym, d_numer, d_denom, d_cnum, d_cden, cmp);
+        else
+            hipLaunchKernelGGL((rank_rows_kernel<2048, C, true>), g, b, 0, st, d_cand, row_seg,
+                               n_qry, q_lo, d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len,
+                               qry_stride, S, (uint32_t)sym, d_numer, d_denom, d_cnum, d_cden, cmp);
+        return hipGetLastError();
+    }
     if (cap <= 1024)
         hipLaunchKernelGGL((rank_rows_kernel<1024, C>), g, b, 0, st, d_cand, row_seg, n_qry, q_lo,
                            d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len, qry_stride, S,
-                           (uint32_t)sym, d_numer, d_denom, d_cnum, d_cden);
+                           (uint32_t)sym, d_numer, d_denom, d_cnum, d_cden, cmp);
     else if (cap <= 2048)
         hipLaunchKernelGGL((rank_rows_kernel<2048, C>), g, b, 0, st, d_cand, row_seg, n_qry, q_lo,
                            d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len, qry_stride, S,
-                           (uint32_t)sym, d_numer, d_denom, d_cnum, d_cden);
+                           (uint32_t)sym, d_numer, d_denom, d_cnum, d_cden, cmp);
     else
         return hipErrorInvalidValue;
     return hipGetLastError();
@@ -696,16 +746,16 @@ hipError_t launch_merge_rows(const uint64_t *d_cand, const uint64_t *row_seg, ui
                              uint32_t n_ref, const uint64_t *d_qry, const uint32_t *d_qry_len,
                              uint64_t qry_stride, uint32_t S, bool sym, Counts cnt,
                              uint32_t *d_cnum, uint32_t *d_cden, hipStream_t st, uint32_t q_lo,
-                             uint32_t *rank_cap)
+                             uint32_t *rank_cap, CmpRows cmp)
 {
     if (!n_qry) return hipSuccess;
     if (cnt.c16)
         return merge_rows_c(d_cand, row_seg, n_qry, d_ref, d_ref_len, ref_stride, n_ref, d_qry,
                             d_qry_len, qry_stride, S, sym, (uint16_t *)cnt.numer,
-                            (uint16_t *)cnt.denom, d_cnum, d_cden, st, q_lo, rank_cap);
+                            (uint16_t *)cnt.denom, d_cnum, d_cden, st, q_lo, rank_cap, cmp);
     return merge_rows_c(d_cand, row_seg, n_qry, d_ref, d_ref_len, ref_stride, n_ref, d_qry,
                         d_qry_len, qry_stride, S, sym, (uint32_t *)cnt.numer,
-                        (uint32_t *)cnt.denom, d_cnum, d_cden, st, q_lo, rank_cap);
+                        (uint32_t *)cnt.denom, d_cnum, d_cden, st, q_lo, rank_cap, cmp);
 }
 
 // ---- FP64 p-value (same algorithm as the oracle restatement)

@@ -775,7 +775,17 @@ __global__ void sum64_kernel(unsigned long long *events)
 // The index may hold only the values <= V* (IdxGeom::vcut): every entry the argument names sits
 // inside its own row's visited prefix, hence is <= V* and indexed; the entries left out are
 // unvisited ones, which could only add seen bits through a collision (the index cut).
-template <typename C, bool HALF>
+//
+// CMP (with HALF, u64 rows, every ref in this workgroup: gridDim.y == 1): the row also writes its
+// compacted copy for the rank kernel (CmpRows).  A probed hash is kept iff one of its
+// events hit an entry of another row with its fingerprint: one bit per probed hash in s_keep,
+// gathered per event window from the hits' ballots.  A hash without such an event is held by no
+// other row: every row
+// holding it would hold an indexed entry of it (the value is <= V*, inside the index with or
+// without the cut), in its bucket and with its fingerprint.  That covers the buckets of one
+// entry (not read), the row's own entry and the entries of other fingerprints.  A collision
+// only keeps a value that could have gone.
+template <typename C, bool HALF, bool CMP = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8)))
 void probe_rows_kernel(
     const void *__restrict__ qry, const uint32_t *__restrict__ qry_len, uint64_t stride,
@@ -786,16 +796,25 @@ void probe_rows_kernel(
     C *__restrict__ denom, uint64_t *__restrict__ cand,
     unsigned long long *__restrict__ n_cand, uint64_t *__restrict__ row_seg,
     const uint32_t *__restrict__ qry_it_len, uint32_t *__restrict__ q_unsorted,
-    unsigned long long *__restrict__ events, uint64_t cap, uint32_t *__restrict__ cand_over)
+    unsigned long long *__restrict__ events, uint64_t cap, uint32_t *__restrict__ cand_over,
+    CmpRows cm)
 {
+    static_assert(!CMP || HALF, "the compacted rows are the half probe's");
     extern __shared__ __attribute__((aligned(16))) uint32_t rowbits[];
     __shared__ uint32_t wsum[4];
     __shared__ unsigned long long row_base;
+    // CMP: bit i = probed hash i is kept; per 64 hashes the kept hashes before them; their total
+    constexpr uint32_t kKeepWords = CMP ? kCmpMaxRow / 32 : 1;
+    __shared__ __attribute__((aligned(8))) uint32_t s_keep[kKeepWords];
+    __shared__ uint32_t s_kpre[CMP ? 64 : 1];
+    __shared__ uint32_t s_kept;
     // per wave: (entry base, fingerprint) of its 64 hashes, and the owner map of an event
     // window (which of the 64 hashes each event belongs to)
     constexpr uint32_t kWin = 1024;
     __shared__ uint64_t w_tab[4][64];
     __shared__ uint8_t w_own[4][kWin];
+    // CMP: per wave, bit e of the window = event e hit another row's entry with its fingerprint
+    __shared__ uint64_t w_hit[4][CMP ? kWin / 64 : 1];
     // XCD-contiguous rows (shared buckets in L2) of rows [q_lo, q_lo + n_qry)
     const uint32_t qr = xcd_row(blockIdx.x, n_qry);
     if (qr >= n_qry) return;
@@ -822,6 +841,8 @@ void probe_rows_kernel(
     // second bitmap of nwords words behind the first
     const uint32_t both0 = nwords * 32;
     for (uint32_t w = threadIdx.x; w < nwords * (HALF ? 2 : 1); w += 256) rowbits[w] = 0;
+    if constexpr (CMP)
+        if (threadIdx.x < kKeepWords) s_keep[threadIdx.x] = 0;
     __syncthreads();
     // lq: the row's list length (the defaults); lit: the hashes probed, which differ from lq
     // when the probed rows are the record rows of unsorted lists (record_rows_kernel), and
@@ -879,6 +900,7 @@ void probe_rows_kernel(
         // arithmetic wraps consistently).
         const uint32_t pre = inc - cnt;
         w_tab[wave][lane] = ((uint64_t)tgt << 32) | (uint32_t)(st - pre);
+        bool keptl = false;     // CMP: this lane's hash of the batch is kept
         for (uint32_t wb = 0; wb < total; wb += kWin) {
             // owner map of events [wb, wb + kWin): each lane marks its own hash's events
             // (4 per dword store inside a lane's range: 3 spilled VGPRs under the 8-wave cap,
@@ -911,6 +933,15 @@ void probe_rows_kernel(
                 // HALF: still one read per event.  A both bit is only ever set together with its
                 // seen bit, so an event of a flagged entry reads (and sets) the ref's both bit,
                 // at bit index both0 + ref, and any other event its seen bit
+                // CMP: which events hit another row's entry goes into the wave's window image
+                // w_hit, one ballot per 64 events (every lane stores the same word), and the
+                // owners read their own ranges of it after the window.  (Per event through the
+                // owner byte, a kept bit read first and set by a rare atomic like the ref bits:
+                // the owner bytes held over the loads spilled 23 VGPRs under the 8-wave cap, 11
+                // packed four to a register, 26 read again from w_own.  The store by lane 0 alone:
+                // probe 0.222 -> 0.230 ms; the owners testing each ballot in registers, no
+                // image: the same time.  The ref range test is dropped, every ref being in this
+                // workgroup: 0.219 -> 0.213 ms.)
                 uint32_t wi[kU], need = 0;
 #pragma unroll
                 for (int u = 0; u < kU; u++) {
@@ -918,11 +949,14 @@ void probe_rows_kernel(
                     const uint32_t r = en[u] & rmask;
                     const bool hit = e < wn &&
                                      ((en[u] & ~kEntryFlag) >> g.rbits) == (uint32_t)(tab[u] >> 32) &&
-                                     r >= r0 && r < r1;
+                                     (CMP || (r >= r0 && r < r1));   // CMP: every ref is here
                     wi[u] = hit ? r - r0 : 0u;
                     if (HALF) wi[u] += hit && (en[u] & kEntryFlag) ? both0 : 0u;
                     const uint32_t word = rowbits[wi[u] >> 5];
                     need |= (hit && !(word & (1u << (wi[u] & 31)))) ? (1u << u) : 0u;
+                    if constexpr (CMP)
+                        w_hit[wave][__builtin_amdgcn_readfirstlane(e0 - lane) / 64 + u] =
+                            __builtin_amdgcn_ballot_w64(hit && r != q);
                 }
                 if (__any(need != 0)) {
 #pragma unroll
@@ -935,6 +969,22 @@ void probe_rows_kernel(
                 }
             }
             __builtin_amdgcn_wave_barrier();   // before the next window's owner map
+            if constexpr (CMP) {
+                // this lane's hash is kept when one of its events [a0, a1) of the window hit
+                // another row's entry.  (Every 64-event group below wn was stored: its first
+                // event's lane ran that step of the loop.)
+                for (uint32_t lo = a0 - wb, hi = a1 - wb; a0 < a1 && lo < hi;
+                     lo = (lo | 63u) + 1) {
+                    const uint32_t n = min(hi, (lo | 63u) + 1) - lo;      // 1 .. 64 bits from lo
+                    keptl |= ((w_hit[wave][lo >> 6] >> (lo & 63u)) << (64 - n)) != 0;
+                }
+                __builtin_amdgcn_wave_barrier();   // before the next window's image
+            }
+        }
+        if constexpr (CMP) {
+            // the batch's kept bits: its two words of s_keep belong to this wave alone
+            const uint64_t kb = __builtin_amdgcn_ballot_w64(keptl);
+            if (lane == 0) *(uint64_t *)&s_keep[(jb + 256 * bi) >> 5] = kb;
         }
         __builtin_amdgcn_wave_barrier();
       }
@@ -943,6 +993,31 @@ void probe_rows_kernel(
     if (!HALF && events && blockIdx.y == 0 && lane == 0 && ev_w)
         atomicAdd(&events[1 + (blockIdx.x & 63)], ev_w);
     __syncthreads();
+    // CMP: the row's first kCp x 256 values, for its compacted copy below: loaded here, so that
+    // they arrive while the candidates are counted and their place in the list is fetched
+    constexpr int kCp = 4;
+    uint64_t cv[CMP ? kCp : 1];
+    if constexpr (CMP) {
+#pragma unroll
+        for (int u = 0; u < kCp; u++) {
+            const uint32_t i = threadIdx.x + 256 * u;
+            cv[u] = i < lq ? ((const uint64_t *)qry)[rowoff + i] : 0;
+        }
+        // the kept hashes before each of the (up to 32) batches of 64, and their total: one
+        // wave's scan, published by the barrier of the candidate count
+        if (wave == 3) {
+            const uint32_t c = 2 * lane + 1 < kKeepWords
+                                   ? __popc(s_keep[2 * lane]) + __popc(s_keep[2 * lane + 1]) : 0u;
+            uint32_t inc = c;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t y = __shfl_up(inc, d, 64);
+                if ((int)lane >= d) inc += y;
+            }
+            s_kpre[lane] = inc - c;
+            if (lane == 63) s_kept = inc;
+        }
+    }
     // candidates of this row: popcount per word -> block scan -> append
     // the row's candidates among the refs of word w
     auto taken = [&](uint32_t w) -> uint32_t {
@@ -981,6 +1056,38 @@ void probe_rows_kernel(
             int t = __builtin_ctz(b);
             b &= b - 1;
             cand[pos++] = bit0 + t;
+        }
+    }
+    if constexpr (CMP) {
+        // the compacted row: the kept hashes of the probed prefix [0, lit) in order, then the
+        // tail [lit, lq) as it is, each with its position in the row; every thread places its
+        // entries
+        const uint32_t kept = s_kept;
+        const uint64_t rb = cmp_row_bytes(stride);
+        uint64_t *crow = (uint64_t *)((uint8_t *)cm.rows + (uint64_t)q * rb);
+        uint16_t *cpos = (uint16_t *)((uint8_t *)crow + stride * 8);
+        auto place = [&](uint32_t i, uint64_t v) {
+            uint32_t d = kept + (i - lit);
+            bool keep = true;
+            if (i < lit) {
+                const uint32_t word = s_keep[i >> 5], bit = i & 31;
+                keep = word >> bit & 1u;
+                d = s_kpre[i >> 6] + ((i & 32) ? __popc(s_keep[(i >> 5) - 1]) : 0u) +
+                    __popc(word & ((1u << bit) - 1u));
+            }
+            if (keep) {
+                crow[d] = v;
+                cpos[(d >> 7) * 128 + (d & 63) * 2 + ((d >> 6) & 1)] = (uint16_t)i;
+            }
+        };
+#pragma unroll
+        for (int u = 0; u < kCp; u++)
+            if (threadIdx.x + 256 * u < lq) place(threadIdx.x + 256 * u, cv[u]);
+        for (uint32_t i = threadIdx.x + 256 * kCp; i < lq; i += 256)
+            place(i, ((const uint64_t *)qry)[rowoff + i]);
+        if (threadIdx.x == 0) {
+            cm.len[q] = kept + (lq - lit);
+            cm.len[n_ref + q] = lq;
         }
     }
     // every pair of the row starts as "no shared value": (0, min(S, la+lb)) (the candidate
@@ -1195,7 +1302,7 @@ hipError_t launch_exscan(const uint32_t *in, uint32_t *out, uint32_t *out2, uint
 static hipError_t dyn_lds_attr(int slot, const void *fn, int bytes)
 {
     constexpr int kMaxDev = 64;
-    static std::atomic<int> done[5][kMaxDev];
+    static std::atomic<int> done[7][kMaxDev];
     int dev = 0;
     if (hipError_t e = hipGetDevice(&dev)) return e;
     if (dev < 0 || dev >= kMaxDev) return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
@@ -1301,9 +1408,14 @@ hipError_t launch_probe_rows(const void *d_qry, const uint32_t *d_qry_len, uint6
                              unsigned long long *n_cand, uint64_t *row_seg,
                              const uint32_t *d_qry_it_len, uint32_t *q_unsorted,
                              unsigned long long *events, uint64_t cap, uint32_t *cand_over,
-                             hipStream_t st, uint32_t q_lo, bool half)
+                             hipStream_t st, uint32_t q_lo, bool half, CmpRows cmp)
 {
     if (!n_qry || !n_ref) return hipSuccess;
+    // the compacted rows are the half probe's, of u64 rows its kept bits cover, with every ref
+    // of a row in one workgroup (all foreign hits of a hash seen in one place)
+    if (cmp.rows && (!half || !cmp.len || hash_bytes != 8 || stride > kCmpMaxRow ||
+                     n_ref > (1u << 19) || q_lo != 0 || n_qry != n_ref))
+        return hipErrorInvalidValue;
     // the half form is the symmetric probe's, over an index whose flags were cut at this S
     // (and never the skip-count path's: no record rows, no order test, no event count)
     if (half && (!sym || !self_set || g.cut != S || d_qry_it_len || q_unsorted || events))
@@ -1314,23 +1426,29 @@ hipError_t launch_probe_rows(const void *d_qry, const uint32_t *d_qry_len, uint6
     // (half: the seen and both bitmaps, up to 128 KiB, past the default dynamic-LDS limit)
     const size_t lds = ((cref + 31) / 32) * 4 * (half ? 2 : 1);
     if (lds > 64 * 1024) {
-        const void *fn = cnt.c16 ? (const void *)probe_rows_kernel<uint16_t, true>
-                                 : (const void *)probe_rows_kernel<uint32_t, true>;
-        if (hipError_t e = dyn_lds_attr(cnt.c16 ? 3 : 4, fn, 128 * 1024)) return e;
+        const void *fn = cmp.rows ? (cnt.c16 ? (const void *)probe_rows_kernel<uint16_t, true, true>
+                                             : (const void *)probe_rows_kernel<uint32_t, true, true>)
+                                  : (cnt.c16 ? (const void *)probe_rows_kernel<uint16_t, true>
+                                             : (const void *)probe_rows_kernel<uint32_t, true>);
+        if (hipError_t e = dyn_lds_attr((cnt.c16 ? 3 : 4) + (cmp.rows ? 2 : 0), fn, 128 * 1024))
+            return e;
     }
     // vector default stores (4 cells): every row and chunk start 4-cell aligned, buffers
     // 16-B aligned
     const auto al = [](const void *p) { return ((uintptr_t)p & 15) == 0; };
     const uint32_t vec_defaults = n_ref % 4 == 0 && cref % 4 == 0 && al(d_ref_len) &&
                                   al(cnt.numer) && al(cnt.denom);
-#define FPM_PROBE(C, H)                                                                         \
-    hipLaunchKernelGGL((probe_rows_kernel<C, H>), dim3(xcd_grid(n_qry), nchunks), dim3(256), lds, \
+#define FPM_PROBE(C, ...)                                                                       \
+    hipLaunchKernelGGL((probe_rows_kernel<C, __VA_ARGS__>), dim3(xcd_grid(n_qry), nchunks),      \
+                       dim3(256), lds,                                                           \
                        st, d_qry, d_qry_len, stride, n_qry, q_lo, n_ref, hash_bytes, g, dir,     \
                        entries, cref,                                                            \
                        d_ref_len, S, (uint32_t)sym, (uint32_t)defaults, vec_defaults,           \
                        (uint32_t)self_set, (C *)cnt.numer, (C *)cnt.denom, cand, n_cand, row_seg, \
-                       d_qry_it_len, q_unsorted, events, cap, cand_over)
-    if (cnt.c16 && half) FPM_PROBE(uint16_t, true);
+                       d_qry_it_len, q_unsorted, events, cap, cand_over, cmp)
+    if (cmp.rows && cnt.c16) FPM_PROBE(uint16_t, true, true);
+    else if (cmp.rows) FPM_PROBE(uint32_t, true, true);
+    else if (cnt.c16 && half) FPM_PROBE(uint16_t, true);
     else if (cnt.c16) FPM_PROBE(uint16_t, false);
     else if (half) FPM_PROBE(uint32_t, true);
     else FPM_PROBE(uint32_t, false);

@@ -311,6 +311,7 @@ int fpm_ctx_create(int device, fpm_ctx **out)
     if (const char *v = getenv("FPM_FILL_COUNTS")) ctx->fill_counts = atoi(v) != 0 ? 1 : 0;
     if (const char *v = getenv("FPM_PROBE_HALF")) ctx->probe_half = atoi(v) != 0;
     if (const char *v = getenv("FPM_INDEX_CUT")) ctx->index_cut = atoi(v) != 0;
+    if (const char *v = getenv("FPM_RANK_COMPACT")) ctx->rank_compact = atoi(v) != 0;
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
@@ -540,6 +541,35 @@ int fpm_ctx_last_index_cut(fpm_ctx *ctx, int *cut, uint64_t *indexed, uint64_t *
     if (cut) *cut = ctx->last_index_cut ? 1 : 0;
     if (indexed) *indexed = ctx->last_indexed;
     if (entries) *entries = ctx->last_entries;
+    return FPM_OK;
+}
+
+int fpm_ctx_set_rank_compact(fpm_ctx *ctx, int on)
+{
+    if (!ctx) return fail(FPM_EINVAL, "null context");
+    ctx->rank_compact = on != 0;
+    return FPM_OK;
+}
+
+int fpm_ctx_last_rank_compact(fpm_ctx *ctx, int *compact, uint64_t *kept, uint64_t *entries)
+{
+    if (!ctx) return fail(FPM_EINVAL, "null context");
+    if (ctx->last_rank_compact && ctx->last_cmp_len) {
+        // the probe's per-row lengths: read once, after the call's work
+        if (int rc = set_device(ctx)) return rc;
+        HIP_TRY(hipStreamSynchronize(ctx->last_cmp_stream));
+        std::vector<uint32_t> len(2 * (size_t)ctx->last_cmp_n);
+        HIP_TRY(hipMemcpy(len.data(), ctx->last_cmp_len, len.size() * 4, hipMemcpyDeviceToHost));
+        ctx->last_kept = ctx->last_cmp_entries = 0;
+        for (uint32_t r = 0; r < ctx->last_cmp_n; r++) {
+            ctx->last_kept += len[r];
+            ctx->last_cmp_entries += len[ctx->last_cmp_n + r];
+        }
+        ctx->last_cmp_len = nullptr;
+    }
+    if (compact) *compact = ctx->last_rank_compact ? 1 : 0;
+    if (kept) *kept = ctx->last_rank_compact ? ctx->last_kept : 0;
+    if (entries) *entries = ctx->last_rank_compact ? ctx->last_cmp_entries : 0;
     return FPM_OK;
 }
 

@@ -283,6 +283,7 @@ struct SparsePlan {
     bool skip_count = false;                    // no probe count ran: the probe counts and tests
     bool spec_probe = false;                    // the probe is enqueued already (speculated)
     bool spec_half = false;                     // and took the half form
+    CmpRows spec_cmp{};                         // and wrote the compacted rows (if any)
     unsigned long long *n_cand() const { return ctr + kCtrCand; }
     uint32_t *unsorted() const { return (uint32_t *)(ctr + kCtrUnsorted); }
     uint32_t *cand_over() const { return (uint32_t *)(ctr + kCtrCandOver); }
@@ -309,6 +310,28 @@ static bool index_cut_ok(const Compare &c)
 {
     return c.ctx->index_cut && c.ctx->probe_half && !c.rs && c.self_set && c.hash_bytes == 8 &&
            c.S > 0 && c.R.n <= (1u << 19) && std::max(c.R.stride, c.Q.stride) <= 2048;
+}
+
+// The compacted candidate rows of a call whose probe takes the half form: one
+// transient sorted u64 set against itself, every ref of a row in one probe workgroup, rows the
+// probe's kept bits cover, the context's switch on.  Empty when the call does not qualify or the
+// buffers cannot be had: the call then ranks the rows themselves.
+static CmpRows compact_rows(const Compare &c, bool half)
+{
+    fpm_ctx *ctx = c.ctx;
+    CmpRows cm;
+    if (!half || !ctx->rank_compact || c.rs || !c.self_set || c.hash_bytes != 8 ||
+        c.R.n > (1u << 19) || c.R.stride > kCmpMaxRow)
+        return cm;
+    void *rows = nullptr, *len = nullptr;
+    if (scratch(ctx, kSlotCmpRows, (size_t)c.R.n * cmp_row_bytes(c.R.stride), &rows) != hipSuccess ||
+        scratch(ctx, kSlotCmpLen, (size_t)c.R.n * 8, &len) != hipSuccess) {
+        (void)hipGetLastError();
+        return cm;
+    }
+    cm.rows = rows;
+    cm.len = (uint32_t *)len;
+    return cm;
 }
 
 // The sparse / dense rule, the candidate capacity and the speculation profile are stated in the
@@ -493,11 +516,15 @@ static int index_transient(Compare &c, SparsePlan &p)
         // the form the confirmed call takes (sym = self_set there: it is kept only on the
         // rank kernel's path)
         p.spec_half = probe_half(c, p, self_set);
+        // (the compacted rows' buffers are had before the probe is enqueued; a dropped
+        // speculation drops them with it)
+        p.spec_cmp = compact_rows(c, p.spec_half);
         TimedLaunch tl(ctx, FPM_K_PROBE, st);
         HIP_TRY(launch_probe_rows(Q.rows, Q.len, Q.stride, Q.n, R.n, hash_bytes, p.geom, p.dir,
                                   p.entries, R.len, c.S, self_set, pf.defaults, self_set, c.cnt,
                                   (uint64_t *)cand, p.n_cand(), (uint64_t *)row_seg, nullptr,
-                                  nullptr, nullptr, pf.cap, p.cand_over(), st, 0, p.spec_half));
+                                  nullptr, nullptr, pf.cap, p.cand_over(), st, 0, p.spec_half,
+                                  p.spec_cmp));
         tl.done();
         p.spec_probe = true;
         return FPM_OK;
@@ -594,15 +621,20 @@ static int index_phase(Compare &c, SparsePlan &p)
 }
 
 // the rank kernel over the probe's candidates: results into per-candidate slots (cnum / cden)
+// (cmp: the compacted rows the call's probe wrote, if any)
 static hipError_t rank_candidates(const Compare &c, const void *cand, const void *row_seg,
-                                  bool sym, uint32_t *cnum, uint32_t *cden)
+                                  bool sym, uint32_t *cnum, uint32_t *cden, CmpRows cmp = CmpRows{})
 {
     uint32_t rank_cap = 0;
     const hipError_t e =
         launch_merge_rows((const uint64_t *)cand, (const uint64_t *)row_seg, c.Q.n,
                           (const uint64_t *)c.R.rows, c.R.len, c.R.stride, c.R.n,
                           (const uint64_t *)c.Q.rows, c.Q.len, c.Q.stride, c.S, sym, c.cnt, cnum,
-                          cden, c.st, 0, &rank_cap);
+                          cden, c.st, 0, &rank_cap, cmp);
+    c.ctx->last_rank_compact = cmp.rows != nullptr;
+    c.ctx->last_cmp_len = cmp.len;
+    c.ctx->last_cmp_n = c.R.n;
+    c.ctx->last_cmp_stream = c.st;
     c.ctx->last_kernel = rank_cap == 1024 ? FPM_DK_CAND_RANK_1024 : FPM_DK_CAND_RANK_2048;
     return e;
 }
@@ -638,6 +670,7 @@ static int candidate_phase(Compare &c, SparsePlan &p, bool rows_merge, uint64_t 
         ctx->last_events = p.ev;
         cap = std::max<uint64_t>(1, std::min<uint64_t>(p.ev, c.n_pairs));
     }
+    const CmpRows cmp = p.spec_probe ? p.spec_cmp : compact_rows(c, half);
     void *cand, *row_seg;
     HIP_TRY(scratch(ctx, kSlotCand, cap * 8, &cand));
     HIP_TRY(scratch(ctx, kSlotRowSeg, (size_t)Q.n * 8, &row_seg));
@@ -649,7 +682,7 @@ static int candidate_phase(Compare &c, SparsePlan &p, bool rows_merge, uint64_t 
                                   (uint64_t *)row_seg, p.p_len,
                                   p.skip_count ? p.unsorted() : nullptr,
                                   p.skip_count ? p.ctr : nullptr, cap, p.cand_over(), st, 0,
-                                  half));
+                                  half, cmp));
         tl.done();
     }
     // A resident sorted set against a block without a count (skip_count): the rank
@@ -716,7 +749,7 @@ static int candidate_phase(Compare &c, SparsePlan &p, bool rows_merge, uint64_t 
     if (!rank_done) {
         TimedLaunch tl(ctx, FPM_K_COMPARE, st);
         if (rows_merge)
-            HIP_TRY(rank_candidates(c, cand, row_seg, sym, cnum, cden));
+            HIP_TRY(rank_candidates(c, cand, row_seg, sym, cnum, cden, cmp));
         else {
             HIP_TRY(launch_walk_candidates((const uint64_t *)cand, p.n_cand(), cap, R.rows, R.len,
                                            R.stride, R.n, Q.rows, Q.len, Q.stride, c.hash_bytes,
@@ -819,6 +852,7 @@ static int compare_impl(fpm_ctx *ctx, const RowSet &R, const RowSet &Q, uint32_t
     ctx->last_kernel = FPM_DK_NONE;
     ctx->last_probe = FPM_PROBE_NONE;
     ctx->last_index_cut = false;
+    ctx->last_rank_compact = false;
     ctx->last_indexed = ctx->last_entries = 0;
     ctx->last_events = 0;
     ctx->last_cand = 0;

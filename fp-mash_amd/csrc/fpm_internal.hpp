@@ -136,6 +136,8 @@ enum ScratchSlot : int {
     kSlotMergeDescs = 18,  // fpm_sketch_merge_dev: merge descriptors
     kSlotRecRefPos = 19,   // record positions of the references
     kSlotRecQryPos = 20,   // record positions of the queries (shared)
+    kSlotCmpRows = 21,     // the compacted candidate rows: values and positions (shared)
+    kSlotCmpLen = 22,      // their lengths, and the rows' own (shared)
     kSlotCount
 };
 
@@ -181,6 +183,14 @@ struct fpm_ctx {
     // reach, the entries it holds and the entries its rows hold (0 / 0: no index was built)
     bool last_index_cut = false;
     uint64_t last_indexed = 0, last_entries = 0;
+    bool rank_compact = true;        // fpm_ctx_set_rank_compact (FPM_RANK_COMPACT=0 starts it off)
+    // fpm_ctx_last_rank_compact: the last compare ranked its candidates on compacted rows; their
+    // lengths (kept, then the rows' own: 2 n u32 on the device) are summed when asked for
+    bool last_rank_compact = false;
+    const uint32_t *last_cmp_len = nullptr;
+    uint32_t last_cmp_n = 0;
+    hipStream_t last_cmp_stream = nullptr;
+    uint64_t last_kept = 0, last_cmp_entries = 0;
     int contain_mode = FPM_CONTAIN_AUTO;        // fpm_ctx_set_contain_mode
     int last_contain_kernel = FPM_CK_NONE;      // fpm_ctx_last_contain_kernel
     int last_screen_kernel = FPM_SK_NONE;       // fpm_ctx_last_screen_kernel

@@ -257,6 +257,20 @@ hipError_t launch_dist_counts_const(uint16_t *numer, uint16_t *denom, uint64_t c
 hipError_t launch_dist_counts_fixup(const uint32_t *d_ref_len, uint32_t n_ref,
                                     const uint32_t *d_qry_len, uint32_t n_qry, uint32_t S,
                                     uint16_t *denom, hipStream_t st);
+// The compacted candidate rows of one sorted u64 set against itself: the half probe
+// writes them, the rank kernel streams them in place of the ref rows.  Row r's block of
+// cmp_row_bytes(stride) bytes starts at rows + r * that: first its kept values (u64, ascending:
+// the values of its probed prefix that another row holds too, then its whole tail), and at byte
+// stride * 8 their positions in the original row, u16, interleaved by rank-kernel chunk (entry d
+// at u16 index (d / 128) * 128 + (d % 64) * 2 + (d / 64) % 2: one dword holds the positions of
+// a lane's two values of a chunk).  len[r] = the kept entries, len[n + r] = the row's own length.
+struct CmpRows {
+    void *rows = nullptr;
+    uint32_t *len = nullptr;
+};
+constexpr uint64_t cmp_row_bytes(uint64_t stride) { return stride * 8 + (stride + 127) / 128 * 256; }
+constexpr uint32_t kCmpMaxRow = 2048;   // the longest row the probe's kept bits cover
+
 // `defaults`: also write (0, min(S, la+lb)) to every numer / denom cell of the row (off
 // when launch_dist_fill already did)
 hipError_t launch_probe_rows(const void *d_qry, const uint32_t *d_qry_len, uint64_t stride,
@@ -267,7 +281,11 @@ hipError_t launch_probe_rows(const void *d_qry, const uint32_t *d_qry_len, uint6
                              unsigned long long *n_cand, uint64_t *row_seg,
                              const uint32_t *d_qry_it_len, uint32_t *q_unsorted,
                              unsigned long long *events, uint64_t cap, uint32_t *cand_over,
-                             hipStream_t st, uint32_t q_lo = 0, bool half = false);
+                             hipStream_t st, uint32_t q_lo = 0, bool half = false,
+                             CmpRows cmp = CmpRows{});
+// (cmp.rows non-null: the half probe also writes each row's compacted copy.  Needs the half
+// form, u64 rows of stride <= kCmpMaxRow and every ref in one workgroup (n_ref <= 2^19):
+// hipErrorInvalidValue otherwise)
 // (half: the symmetric probe of one sorted set against itself over an index cut at this S
 // (g.cut == S): each row probes only its visited prefix and a pair is taken by its parity
 // owner when that row sees it, else by the other row; dist_index.hip step 2.  Needs sym and
@@ -283,7 +301,9 @@ hipError_t launch_merge_rows(const uint64_t *d_cand, const uint64_t *row_seg, ui
                              uint32_t n_ref, const uint64_t *d_qry, const uint32_t *d_qry_len,
                              uint64_t qry_stride, uint32_t S, bool sym, Counts cnt,
                              uint32_t *d_cnum, uint32_t *d_cden, hipStream_t st, uint32_t q_lo = 0,
-                             uint32_t *rank_cap = nullptr);
+                             uint32_t *rank_cap = nullptr, CmpRows cmp = CmpRows{});
+// (cmp.rows non-null: one set against itself (sym, d_ref == d_qry) whose probe wrote the
+// compacted rows: the candidates are streamed from those, the diagonal answered in closed form)
 // (d_cnum, d_cden non-null: results go to candidate slot c instead of the grid cells;
 // q_lo, n_qry: the query rows [q_lo, q_lo + n_qry), whose probe has run;
 // *rank_cap: the CAP of the rank_rows_kernel instance launched, 1024 or 2048)

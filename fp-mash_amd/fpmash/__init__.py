@@ -96,6 +96,8 @@ SYMBOLS = [
     ("fpm_ctx_last_dist_probe", C.c_int, [vp, C.POINTER(C.c_int)]),
     ("fpm_ctx_set_index_cut", C.c_int, [vp, C.c_int]),
     ("fpm_ctx_last_index_cut", C.c_int, [vp, C.POINTER(C.c_int), u64p, u64p]),
+    ("fpm_ctx_set_rank_compact", C.c_int, [vp, C.c_int]),
+    ("fpm_ctx_last_rank_compact", C.c_int, [vp, C.POINTER(C.c_int), u64p, u64p]),
     ("fpm_sketch_batch", C.c_int, [vp, vp, C.c_char_p, u64p, C.c_uint32, u32p, C.c_uint32,
                                    u64p, u32p]),
     ("fpm_sketch_stage", C.c_int, [vp, vp, C.c_char_p, u64p, C.c_uint32, u32p, C.c_uint32,
@@ -829,6 +831,19 @@ class Context:
         c, i, e = C.c_int(), C.c_uint64(), C.c_uint64()
         _check(lib().fpm_ctx_last_index_cut(self.h, C.byref(c), C.byref(i), C.byref(e)))
         return {"cut": bool(c.value), "indexed": i.value, "entries": e.value}
+
+    def set_rank_compact(self, on=True):
+        """fpm_ctx_set_rank_compact: the candidates of one sorted set against itself are ranked
+        on rows without the probed hashes no other row holds (default on; same results)"""
+        _check(lib().fpm_ctx_set_rank_compact(self.h, int(on)))
+
+    def last_rank_compact(self):
+        """fpm_ctx_last_rank_compact: {"compact": whether the last compare ranked compacted
+        rows, "kept": the entries those hold, "entries": the entries of the rows themselves}
+        (a test hook; synchronises)"""
+        c, k, e = C.c_int(), C.c_uint64(), C.c_uint64()
+        _check(lib().fpm_ctx_last_rank_compact(self.h, C.byref(c), C.byref(k), C.byref(e)))
+        return {"compact": bool(c.value), "kept": k.value, "entries": e.value}
 
     # --- sketch -----------------------------------------------------------
     def sketch(self, params, seqs, groups=None, n_groups=None, counts=False, min_copies=1):

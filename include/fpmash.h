@@ -171,6 +171,18 @@ int fpm_ctx_set_index_cut(fpm_ctx *ctx, int on);
  * used no index).  Any pointer may be NULL.  From counters the compare already read: no
  * synchronisation. */
 int fpm_ctx_last_index_cut(fpm_ctx *ctx, int *cut, uint64_t *indexed, uint64_t *entries);
+/* One sorted u64 set against itself, half probe and rank kernel: the probe writes each row once
+ * more without the hashes of its probed half that no other row holds, and the candidates are
+ * ranked on those compacted rows (a hash of one row alone shares nothing; the kept hashes carry
+ * their positions).  The diagonal is answered without ranking.  On by default; a context
+ * created with FPM_RANK_COMPACT=0 in the environment starts with it off.  Same results either
+ * way. */
+int fpm_ctx_set_rank_compact(fpm_ctx *ctx, int on);
+/* The candidate rows of the last compare (a test hook): *compact whether they were ranked
+ * compacted, *kept the entries the compacted rows hold, *entries the entries of the rows
+ * themselves (both 0 when not compacted).  Any pointer may be NULL.  Reads the probe's per-row
+ * lengths: synchronises with the compare's stream. */
+int fpm_ctx_last_rank_compact(fpm_ctx *ctx, int *compact, uint64_t *kept, uint64_t *entries);
 
 /* ---- k-mer sketch ------------------------------------------------------------
  * Replaces addMinHashes (Sketch.cpp:664-735) + MinHashHeap::tryInsert
