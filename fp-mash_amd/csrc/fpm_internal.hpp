@@ -194,6 +194,7 @@ struct fpm_ctx {
     int contain_mode = FPM_CONTAIN_AUTO;        // fpm_ctx_set_contain_mode
     int last_contain_kernel = FPM_CK_NONE;      // fpm_ctx_last_contain_kernel
     int last_screen_kernel = FPM_SK_NONE;       // fpm_ctx_last_screen_kernel
+    int last_tax_kernel = FPM_TK_NONE;          // fpm_ctx_last_tax_kernel
     uint64_t last_events = 0, last_cand = 0;
     const unsigned long long *last_cand_dev = nullptr;   // the last sparse call's counter
     hipStream_t last_cand_stream = nullptr;

@@ -442,6 +442,28 @@ hipError_t launch_screen_winner(const uint32_t *d_count, const uint32_t *d_ustar
 hipError_t launch_screen_pvalues(const uint32_t *d_shared, const uint32_t *d_size, uint32_t n,
                                  double r, double *d_p, hipStream_t st);
 
+// taxscreen (taxscreen.hip): the LCA fold per entry of U and the clade sums.  Nodes are dense
+// indices; parent[v] is an index or kTaxRoot, depth[v] the links from v to its root (the host
+// computes it while it checks for cycles: every walk in the kernels is counted by it); top is
+// the node of taxID 1, or kTaxUnknown.  ref_node[i]: kTaxNone, kTaxUnknown or a node.
+constexpr uint32_t kTaxRoot = 0xFFFFFFFFu, kTaxNone = 0xFFFFFFFFu, kTaxUnknown = 0xFFFFFFFEu;
+// posting lists of this many holders and more are folded by a wave, shorter ones by one lane
+constexpr uint32_t kTaxWaveCut = 64;
+struct TaxTree {
+    const uint32_t *parent = nullptr, *depth = nullptr;
+    uint32_t n_nodes = 0, top = kTaxUnknown;
+};
+// lca: n entries; tax_hashes / tax_count: n_nodes counters, zeroed by the caller; totals[0] +=
+// the entries with count >= 1; *wave_entries += the entries folded by a wave
+hipError_t launch_tax_lca(const uint32_t *d_count, const uint32_t *d_ustart, const uint32_t *d_post,
+                          uint32_t n, const uint32_t *d_ref_node, const TaxTree &t, uint32_t *d_lca,
+                          uint32_t *d_tax_hashes, uint32_t *d_tax_count,
+                          unsigned long long *d_totals, uint32_t *d_wave_entries, hipStream_t st);
+// clade_hashes / clade_count: n_nodes counters, zeroed by the caller
+hipError_t launch_tax_clade(const TaxTree &t, const uint32_t *d_tax_hashes,
+                            const uint32_t *d_tax_count, uint32_t *d_clade_hashes,
+                            uint32_t *d_clade_count, hipStream_t st);
+
 // The transposed grid of a rectangular compare (fpm_refset_dist_mirror_dev): cell (r, q) at
 // r * n_qry + q holds the pair "query r of the ref set against ref q of the query set".  For
 // sorted distinct lists (numer, denom) is symmetric, and so are distance and p-value.

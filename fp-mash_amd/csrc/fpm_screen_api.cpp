@@ -1,7 +1,8 @@
 // fpm_screen_api.cpp — the screen part of the C ABI (include/fpmash.h): the table of a sketch
 // database, the pool passes that fill its counters and the pool's bottom-s row, and the
-// per-reference sums, -w and p-values read from them.  The kernels are in screen.hip, the
-// pool pass in sketch.hip (screen_count_kernel), the binomial tail in dist.hip.
+// per-reference sums, -w and p-values read from them, and taxscreen's per-hash LCA and clade
+// tallies over the same table.  The kernels are in screen.hip and taxscreen.hip, the pool pass
+// in sketch.hip (screen_count_kernel), the binomial tail in dist.hip.
 #include "fpm_internal.hpp"
 #include "screen_table.hpp"
 
@@ -330,6 +331,110 @@ int fpm_screen_pvalues(fpm_screen *sc, const uint32_t *shared, double kmer_space
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(copy_out(ctx, out_p, dp.p, (size_t)sc->n_db * 8));
+    return FPM_OK;
+}
+
+int fpm_screen_tax(fpm_screen *sc, const uint32_t *parent, uint32_t n_nodes, uint32_t top,
+                   const uint32_t *ref_node, uint32_t *out_lca, uint32_t *out_tax_hashes,
+                   uint32_t *out_tax_count, uint32_t *out_clade_hashes, uint32_t *out_clade_count,
+                   uint64_t out_totals[2])
+{
+    if (!sc || !out_totals || (n_nodes && !parent) || (sc->n_db && !ref_node))
+        return fail(FPM_EINVAL, "fpm_screen_tax: null argument");
+    fpm_ctx *ctx = sc->ctx;
+    // node indices stay below the three reserved values and the fold's internal one
+    if (n_nodes > 0xFFFFFFF0u) return fail(FPM_EINVAL, "fpm_screen_tax: too many nodes");
+    if (top != FPM_TAX_UNKNOWN && top >= n_nodes)
+        return fail(FPM_EINVAL, "fpm_screen_tax: top is not a node");
+    for (uint32_t i = 0; i < sc->n_db; i++)
+        if (ref_node[i] < FPM_TAX_UNKNOWN && ref_node[i] >= n_nodes)
+            return fail(FPM_EINVAL, "fpm_screen_tax: a ref_node is not a node");
+    // depth[v] = links from v to its root; a chain that does not end in FPM_TAX_ROOT within
+    // n_nodes links is a cycle.  Chains are walked once: up to the first node whose depth is
+    // known, then back down.
+    constexpr uint32_t kUnset = 0xFFFFFFFFu;
+    std::vector<uint32_t> depth(n_nodes, kUnset), path;
+    for (uint32_t v = 0; v < n_nodes; v++) {
+        if (parent[v] != FPM_TAX_ROOT && parent[v] >= n_nodes)
+            return fail(FPM_EINVAL, "fpm_screen_tax: a parent index is out of range");
+    }
+    for (uint32_t v = 0; v < n_nodes; v++) {
+        if (depth[v] != kUnset) continue;
+        path.clear();
+        uint32_t x = v, base = 0;
+        for (;;) {
+            if (path.size() > n_nodes) return fail(FPM_EINVAL, "fpm_screen_tax: the parent links hold a cycle");
+            path.push_back(x);
+            const uint32_t p = parent[x];
+            if (p == FPM_TAX_ROOT) { base = 0; break; }
+            if (depth[p] != kUnset) { base = depth[p] + 1; break; }
+            x = p;
+        }
+        // path.back() has depth `base` (a cycle never reaches a break: the length bound ends it)
+        for (size_t i = path.size(); i-- > 0;) depth[path[i]] = base + (uint32_t)(path.size() - 1 - i);
+    }
+    if (int rc = set_device(ctx)) return rc;
+    HIP_TRY(hipDeviceSynchronize());   // pool passes may have run on other streams
+    hipStream_t st = ctx->stream;
+    const uint32_t nU = sc->tab.n;
+    const size_t nb = (size_t)n_nodes * 4;
+    DevBuf dpar, ddep, dref, dlca, dcnt, dtot;
+    hipError_t e = dpar.get(nb);
+    if (e == hipSuccess) e = ddep.get(nb);
+    if (e == hipSuccess) e = dref.get((size_t)sc->n_db * 4);
+    if (e == hipSuccess) e = dlca.get((size_t)nU * 4);
+    if (e == hipSuccess) e = dcnt.get(4 * nb);     // tax_hashes, tax_count, clade_hashes, clade_count
+    if (e == hipSuccess) e = dtot.get(16);         // totals[0], the wave's entries
+    if (e == hipSuccess && n_nodes) e = copy_in(ctx, dpar.p, parent, nb);
+    if (e == hipSuccess && n_nodes) e = copy_in(ctx, ddep.p, depth.data(), nb);
+    if (e == hipSuccess && sc->n_db) e = copy_in(ctx, dref.p, ref_node, (size_t)sc->n_db * 4);
+    if (e != hipSuccess) return fail(FPM_ENOMEM, std::string("taxscreen staging: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemsetAsync(dcnt.p, 0, std::max<size_t>(4 * nb, 16), st));
+    HIP_TRY(hipMemsetAsync(dtot.p, 0, 16, st));
+    TaxTree t;
+    t.parent = dpar.as<uint32_t>();
+    t.depth = ddep.as<uint32_t>();
+    t.n_nodes = n_nodes;
+    t.top = top;
+    uint32_t *c0 = dcnt.as<uint32_t>(), *c1 = c0 + n_nodes, *c2 = c1 + n_nodes, *c3 = c2 + n_nodes;
+    unsigned long long *d_tot = dtot.as<unsigned long long>();
+    ctx->last_tax_kernel = FPM_TK_NONE;
+    {
+        TimedLaunch tl(ctx, FPM_K_COMPARE, st);
+        HIP_TRY(launch_tax_lca(sc->tab.count, sc->d_ustart, sc->d_post, nU, dref.as<uint32_t>(), t,
+                               dlca.as<uint32_t>(), c0, c1, d_tot, (uint32_t *)(d_tot + 1), st));
+        tl.done();
+    }
+    {
+        TimedLaunch tl(ctx, FPM_K_FINALIZE, st);
+        HIP_TRY(launch_tax_clade(t, c0, c1, c2, c3, st));
+        tl.done();
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    unsigned long long host[2] = {0, 0};
+    HIP_TRY(copy_out(ctx, host, d_tot, 16));
+    if (nU) ctx->last_tax_kernel = (uint32_t)host[1] ? FPM_TK_WAVE : FPM_TK_THREAD;
+    out_totals[0] = host[0];
+    out_totals[1] = nU;
+    if (out_lca && nU) HIP_TRY(copy_out(ctx, out_lca, dlca.p, (size_t)nU * 4));
+    uint32_t *outs[4] = {out_tax_hashes, out_tax_count, out_clade_hashes, out_clade_count};
+    const uint32_t *srcs[4] = {c0, c1, c2, c3};
+    for (int i = 0; i < 4; i++)
+        if (outs[i] && n_nodes) HIP_TRY(copy_out(ctx, outs[i], srcs[i], nb));
+    return FPM_OK;
+}
+
+int fpm_ctx_last_tax_kernel(fpm_ctx *ctx, int *kernel)
+{
+    if (!ctx || !kernel) return fail(FPM_EINVAL, "null argument");
+    *kernel = ctx->last_tax_kernel;
+    return FPM_OK;
+}
+
+int fpm_screen_tax_wave_cut(fpm_ctx *ctx, uint32_t *cut)
+{
+    if (!ctx || !cut) return fail(FPM_EINVAL, "null argument");
+    *cut = kTaxWaveCut;
     return FPM_OK;
 }
 

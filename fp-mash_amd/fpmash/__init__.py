@@ -6,6 +6,7 @@ A ctypes mirror of the reference's engine calls for this path:
   compare/compareSketches/pValue (CommandDistance.cpp:335-450)             -> Context.dist
   contain/containSketches (CommandContain.cpp:314-412)                     -> Context.contain
   screen: hashSequence, sums, -w, pValueWithin (CommandScreen.cpp:133-406) -> Context.screen
+  taxscreen: the LCA fold, tallies and clade sums (CommandTaxScreen.cpp:386-437) -> Context.taxscreen
 The shared library is built in-tree (fp-mash_amd/lib/libfpmash.so).  There is no
 CPU fallback: if the library is missing this import fails, and without a gfx950
 device Context() raises FpmError(FPM_ENODEV).
@@ -53,6 +54,10 @@ CONTAIN_BLOCK_REFS = 64                          # FPM_CONTAIN_BLOCK_REFS
 # fpm_ctx_last_screen_kernel codes (FPM_SK_*)
 SK_NONE, SK_ROWS_LDS, SK_ROWS_GLOBAL = range(3)
 SCREEN_KERNELS = ["none", "screen_rows_kernel<lds>", "screen_rows_kernel<global>"]
+# fpm_screen_tax node codes (FPM_TAX_*) and fpm_ctx_last_tax_kernel codes (FPM_TK_*)
+TAX_ROOT, TAX_NONE, TAX_UNKNOWN = 0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFE
+TK_NONE, TK_THREAD, TK_WAVE = range(3)
+TAX_KERNELS = ["none", "tax_lca_kernel (lane per entry)", "tax_lca_kernel (wave on long lists)"]
 
 ALPHABET_NUCLEOTIDE = "ACGT"                     # Sketch.h alphabetNucleotide
 ALPHABET_PROTEIN = "ACDEFGHIKLMNPQRSTVWY"         # Sketch.h alphabetProtein
@@ -172,6 +177,10 @@ SYMBOLS = [
     ("fpm_screen_pvalues", C.c_int, [vp, u32p, C.c_double, f64p]),
     ("fpm_ctx_last_screen_kernel", C.c_int, [vp, C.POINTER(C.c_int)]),
     ("fpm_screen_lds_cap", C.c_int, [vp, u32p]),
+    ("fpm_screen_tax", C.c_int, [vp, u32p, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p, u32p,
+                                 u32p, u64p]),
+    ("fpm_ctx_last_tax_kernel", C.c_int, [vp, C.POINTER(C.c_int)]),
+    ("fpm_screen_tax_wave_cut", C.c_int, [vp, u32p]),
     ("fpm_refset_create", C.c_int, [vp, vp, u32p, u64p, C.c_uint64, C.c_uint32, C.c_uint32,
                                     C.c_uint32, C.POINTER(vp)]),
     ("fpm_refset_create_dev", C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32,
@@ -701,6 +710,30 @@ class Screen:
         _check(lib().fpm_screen_pvalues(self.h, _p(sh, u32p), float(kmer_space), _p(out, f64p)))
         return out[:self.n]
 
+    def tax(self, parent, top, ref_node, lca=True):
+        """fpm_screen_tax: parent (u32 per node, TAX_ROOT for a root), top (the node of taxID 1
+        or TAX_UNKNOWN), ref_node (u32 per reference: a node, TAX_NONE or TAX_UNKNOWN) -> dict:
+        lca (u32 per entry of U; None with lca=False), tax_hashes, tax_count, clade_hashes,
+        clade_count (u32 per node), total_count, total_hashes"""
+        parent = np.ascontiguousarray(parent, dtype=np.uint32)
+        ref_node = np.ascontiguousarray(ref_node, dtype=np.uint32)
+        if len(ref_node) != self.n:
+            raise ValueError("tax: one ref_node per reference")
+        n = len(parent)
+        nu = np.zeros(1, np.uint64)
+        _check(lib().fpm_screen_counts(self.h, None, None, _p(nu, u64p)))
+        nu = int(nu[0])
+        out = np.zeros(max(nu, 1), np.uint32) if lca else None
+        arr = [np.zeros(max(n, 1), np.uint32) for _ in range(4)]
+        tot = np.zeros(2, np.uint64)
+        _check(lib().fpm_screen_tax(self.h, _p(parent, u32p), n, int(top), _p(ref_node, u32p),
+                                    _p(out, u32p) if lca else None, _p(arr[0], u32p),
+                                    _p(arr[1], u32p), _p(arr[2], u32p), _p(arr[3], u32p),
+                                    _p(tot, u64p)))
+        return {"lca": out[:nu] if lca else None, "tax_hashes": arr[0][:n],
+                "tax_count": arr[1][:n], "clade_hashes": arr[2][:n], "clade_count": arr[3][:n],
+                "total_count": int(tot[0]), "total_hashes": int(tot[1])}
+
     def free(self):
         if self.h:
             lib().fpm_screen_free(self.h)
@@ -1086,6 +1119,35 @@ class Context:
         v = np.zeros(1, np.uint32)
         _check(lib().fpm_screen_lds_cap(self.h, _p(v, u32p)))
         return int(v[0])
+
+    def last_tax_kernel(self):
+        """fpm_ctx_last_tax_kernel: how the last Screen.tax folded its posting lists (a TK_*
+        code; a test hook)"""
+        k = C.c_int()
+        _check(lib().fpm_ctx_last_tax_kernel(self.h, C.byref(k)))
+        return k.value
+
+    def tax_wave_cut(self):
+        """fpm_screen_tax_wave_cut: the holders from which a posting list is folded by a wave"""
+        v = np.zeros(1, np.uint32)
+        _check(lib().fpm_screen_tax_wave_cut(self.h, _p(v, u32p)))
+        return int(v[0])
+
+    def taxscreen(self, params, db_lists, pool, parent, top, ref_node, slices=1):
+        """`mash taxscreen` without its files: the pool pass of screen(), then Screen.tax over
+        the taxonomy (parent, top) and the references' nodes -> Screen.tax's dict plus
+        set_size."""
+        s = int(params.sketch_size)
+        sc = Screen.from_lists(self, [l[:s] for l in db_lists], s, use64=bool(params.use64))
+        try:
+            step = max(1, -(-len(pool) // max(slices, 1)))
+            for at in range(0, len(pool), step):
+                sc.add_records(params, pool[at:at + step])
+            r = sc.tax(parent, top, ref_node)
+            r["set_size"] = sc.set_size()
+            return r
+        finally:
+            sc.free()
 
     def screen(self, params, db_lists, pool, lengths=None, winner=False, slices=1):
         """The documented `mash screen` over a database (lists of ascending hashes, cut to the

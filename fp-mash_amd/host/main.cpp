@@ -1,9 +1,10 @@
 // main.cpp — `fpmash`: the reference's CLI entry (mash.cpp:19-40) for the hot-path
-// verbs.  `fpmash sketch|dist|info|paste|triangle|contain|screen [-fp] ...` is a drop-in for the same
-// `mash` verbs.
+// verbs.  `fpmash sketch|dist|info|paste|triangle|contain|screen|taxscreen [-fp] ...` is a drop-in
+// for the same `mash` verbs.
 #include "Command.h"
 #include "CommandContain.h"
 #include "CommandScreen.h"
+#include "CommandTaxScreen.h"
 #include "Timing.h"
 
 #include <cstdio>
@@ -29,6 +30,7 @@ int main(int argc, const char **argv)
     commandList.addCommand(new fpmhost::CommandTriangle());
     commandList.addCommand(new fpmhost::CommandContain());
     commandList.addCommand(new fpmhost::CommandScreen());
+    commandList.addCommand(new fpmhost::CommandTaxScreen());
     const int rc = commandList.run(argc, argv);
     fpmhost::phaseMark("command done");
     // Every output is written and the device work is complete (results were fetched): leave

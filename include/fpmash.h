@@ -685,6 +685,55 @@ int fpm_screen_pvalues(fpm_screen *sc, const uint32_t *shared, double kmer_space
 int fpm_ctx_last_screen_kernel(fpm_ctx *ctx, int *kernel);
 int fpm_screen_lds_cap(fpm_ctx *ctx, uint32_t *cap);
 
+/* ---- taxscreen ----------------------------------------------------------------------
+ * `mash taxscreen` after its pool pass (the same as screen's): one lowest-common-ancestor fold
+ * per entry of U over the taxa of its holders, per-taxon tallies and clade sums:
+ *   the fold per distinct database hash                  CommandTaxScreen.cpp:386-397
+ *   getLowestCommonAncestor                              taxdb.hpp:158-190
+ *   taxHashCount / taxCount (minCov = 1)                 CommandTaxScreen.cpp:398-403
+ *   cladeCount / cladeHashCount up the ancestors         CommandTaxScreen.cpp:406-437
+ * Parsing the dump, the reference -> taxID mapping and writeReport (taxdb.hpp:192-236) stay
+ * with the caller.
+ *
+ * The taxonomy is n_nodes dense node indices: parent[v] is an index or FPM_TAX_ROOT (a node
+ * that is its own parent in nodes.dmp, taxdb.hpp:97-99, or whose parent has no line).  top is
+ * the node of taxID 1, the value of the reference's `return 1` (:167, :173, :189), or
+ * FPM_TAX_UNKNOWN when the dump has none.  ref_node[i] is reference i's node, FPM_TAX_NONE for
+ * taxID 0 (`if (a == 0) return b`, :159-160) or FPM_TAX_UNKNOWN for a taxID without a node.
+ *
+ * out_lca[u], with T the ref_node values of u's holders that are not NONE: NONE when T is
+ * empty; its one element (maybe UNKNOWN) when it has one; else top when any is UNKNOWN, when
+ * they share no ancestor or when their deepest common ancestor is a root (the path of `a`
+ * stops before a root and before taxID 1, :176, and so does the walk from `b`, :183); else that
+ * ancestor.  The result does not depend on the order of the holders (the reference visits an
+ * unordered set).  tax_hashes[v] = #{u : lca[u] = v}, tax_count[v] the same over the entries
+ * with count >= 1; clade_*[v] = the sums of tax_* over v and its descendants (every tallied
+ * taxon visited once; the reference inserts into the map it iterates).  out_totals[0] = the
+ * entries with count >= 1, out_totals[1] = |U|: entries whose lca is NONE or UNKNOWN count
+ * there and nowhere else (getEntry fails for them, :417).
+ *
+ * Host buffers in and out (out_lca and the four arrays may be NULL); synchronises; may follow
+ * any number of fpm_screen_add_* calls and leaves the counters as they are.  FPM_EINVAL,
+ * before anything is launched, for parent links that hold a cycle, a parent index or a
+ * ref_node out of range, or a top that is no node.  No CPU fallback. */
+#define FPM_TAX_ROOT    0xFFFFFFFFu
+#define FPM_TAX_NONE    0xFFFFFFFFu   /* in ref_node / out_lca */
+#define FPM_TAX_UNKNOWN 0xFFFFFFFEu
+int fpm_screen_tax(fpm_screen *sc, const uint32_t *parent, uint32_t n_nodes, uint32_t top,
+                   const uint32_t *ref_node,
+                   uint32_t *out_lca,            /* |U|, in U's order; may be NULL */
+                   uint32_t *out_tax_hashes, uint32_t *out_tax_count,
+                   uint32_t *out_clade_hashes, uint32_t *out_clade_count,  /* n_nodes each */
+                   uint64_t out_totals[2]);      /* total_count, total_hashes */
+/* How the last fpm_screen_tax folded its posting lists (a test hook like
+ * fpm_ctx_last_screen_kernel): every list by one lane (THREAD), or at least one list of
+ * fpm_screen_tax_wave_cut holders or more by a whole wave (WAVE).  NONE: U is empty. */
+#define FPM_TK_NONE 0
+#define FPM_TK_THREAD 1
+#define FPM_TK_WAVE 2
+int fpm_ctx_last_tax_kernel(fpm_ctx *ctx, int *kernel);
+int fpm_screen_tax_wave_cut(fpm_ctx *ctx, uint32_t *cut);
+
 /* ---- communicator: RCCL over xGMI for the cross-GPU min-merge ------------------------
  * north_star reserves the collective for "the final min-merge only where the reference set
  * exceeds one GPU's HBM" (or one sketch is split over GPUs).  The reference has no collective:
