@@ -1,7 +1,7 @@
 // fpm_internal.hpp — what the files implementing the C ABI of include/fpmash.h share:
 // the context, its pool / ring / copy helpers, the device scratch slots and the counter block.
 // fpm_ctx.cpp defines the helpers; fpm_sketch_api.cpp, fpm_text_api.cpp, fpm_dist_api.cpp,
-// fpm_contain_api.cpp, fpm_screen_api.cpp and fpm_comm.cpp use them.  Nothing declared here is exported from the library.
+// fpm_contain_api.cpp, fpm_screen_api.cpp, fpm_kfinger_api.cpp and fpm_comm.cpp use them.  Nothing declared here is exported from the library.
 #pragma once
 
 #include "fpm_kernels.hpp"
@@ -320,6 +320,14 @@ struct StageRecords {
 // fpm_sketch_api.cpp: the staging behind fpm_sketch_stage and fpm_sketch_stage_seq
 FPM_HIDDEN int stage_core(fpm_ctx *ctx, const fpm_sketch_params *p, StageRecords &R,
                           fpm_sketch_job **job_out);
+
+// fpm_text_api.cpp: the records of a device parse for a job that adopts them (fpm_kfinger_stage_seq):
+// each record's offset and length in the packed buffer, and the buffer itself, which leaves the
+// parse handle (the caller frees it with hipFree)
+struct fpm_seqtext;
+FPM_HIDDEN int seqtext_records(fpm_ctx *ctx, fpm_seqtext *seq, uint64_t *n_rec,
+                               std::vector<uint64_t> *pos, std::vector<uint64_t> *len,
+                               uint8_t **d_packed);
 
 // fpm_sketch_api.cpp: what fpm_screen_add_job reads of a staged job (its tiles by class cover
 // every window of its records exactly once; row 0 / count 0 are its first group's sketch)

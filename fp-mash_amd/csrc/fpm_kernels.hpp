@@ -1,6 +1,6 @@
 // fpm_kernels.hpp — launch interface between the C-ABI (fpm_*_api.cpp) and the
 // gfx950 kernels (sketch.hip, dist.hip, dist_index.hip, fingerprint.hip, seqparse.hip,
-// contain.hip).  Host-only types.
+// contain.hip, screen.hip, taxscreen.hip, kfinger.hip).  Host-only types.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -463,6 +463,41 @@ hipError_t launch_tax_lca(const uint32_t *d_count, const uint32_t *d_ustart, con
 hipError_t launch_tax_clade(const TaxTree &t, const uint32_t *d_tax_hashes,
                             const uint32_t *d_tax_count, uint32_t *d_clade_hashes,
                             uint32_t *d_clade_count, hipStream_t st);
+
+// kfinger (kfinger.hip): CFL k-fingers of sequence records, one lane per line.  A workgroup
+// takes one descriptor: kind 0, the window starts [start, start + count) of record rec (its
+// length >= the window); kind 1, the records rec .. rec + count - 1, each shorter than the window
+// (one line each) and together at most kKfStage bytes.  count <= kKfRun; the descriptor's lines
+// are line_base .. line_base + count - 1.  Records are indexed by rec_pos / rec_len (offset in
+// the sequence buffer, length).
+constexpr uint32_t kKfMaxWindow = 4096;   // the widest window: lengths fit u16, the stage 4.3 KB
+constexpr uint32_t kKfRun = 256;          // window starts (lanes) per workgroup
+constexpr uint32_t kKfStage = kKfRun + kKfMaxWindow - 1;   // bytes a workgroup stages at most
+struct KfDesc {
+    uint64_t line_base;
+    uint32_t rec, start, count, kind;
+};
+// pass one: per line its hash (u32, or u64 with use64), factor count and the text bytes after
+// its ID; *d_val_total (zeroed by the caller) += the factors of all lines
+hipError_t launch_kf_hash(const uint8_t *d_seq, const uint64_t *d_rec_pos,
+                          const uint32_t *d_rec_len, const KfDesc *d_descs, uint32_t n_desc,
+                          uint32_t w, uint32_t seed, uint32_t use64, void *d_hash,
+                          uint32_t *d_n_vals, uint32_t *d_body, unsigned long long *d_val_total,
+                          hipStream_t st);
+// size[line] = body[line] + id_len[its record]; *d_text_total (zeroed by the caller) += the sum
+hipError_t launch_kf_text_size(const KfDesc *d_descs, uint32_t n_desc, const uint32_t *d_body,
+                               const uint32_t *d_id_len, uint32_t *d_size,
+                               unsigned long long *d_text_total, hipStream_t st);
+// pass two, at the offsets an exclusive scan of the sizes gave (d_off, per line): the factor
+// lengths as u16, or the text lines (record r's ID: d_ids[d_id_off[r] .. + d_id_len[r]))
+hipError_t launch_kf_values(const uint8_t *d_seq, const uint64_t *d_rec_pos,
+                            const uint32_t *d_rec_len, const KfDesc *d_descs, uint32_t n_desc,
+                            uint32_t w, const uint32_t *d_off, uint16_t *d_vals, hipStream_t st);
+hipError_t launch_kf_text(const uint8_t *d_seq, const uint64_t *d_rec_pos,
+                          const uint32_t *d_rec_len, const KfDesc *d_descs, uint32_t n_desc,
+                          uint32_t w, const uint32_t *d_off, const uint8_t *d_ids,
+                          const uint64_t *d_id_off, const uint32_t *d_id_len, uint8_t *d_out,
+                          hipStream_t st);
 
 // The transposed grid of a rectangular compare (fpm_refset_dist_mirror_dev): cell (r, q) at
 // r * n_qry + q holds the pair "query r of the ref set against ref q of the query set".  For

@@ -486,6 +486,26 @@ int fpm_seq_packed(fpm_seqtext *j, uint64_t *seq_off, uint8_t *out, uint64_t cap
     return FPM_OK;
 }
 
+}  // extern "C"
+
+int seqtext_records(fpm_ctx *ctx, fpm_seqtext *seq, uint64_t *n_rec, std::vector<uint64_t> *pos,
+                    std::vector<uint64_t> *len, uint8_t **d_packed)
+{
+    if (seq->ctx != ctx) return fail(FPM_EINVAL, "records parsed on another context");
+    if (!seq->d_out) return fail(FPM_EINVAL, "records already staged");
+    const uint64_t n = seq->n_rec, nn = n ? n : 1;
+    pos->resize(n);
+    len->resize(n);
+    HIP_TRY(d2h_staged(ctx, pos->data(), seq->d_rec + 3 * nn, n * 8));
+    HIP_TRY(d2h_staged(ctx, len->data(), seq->d_rec + 4 * nn, n * 8));
+    *n_rec = n;
+    *d_packed = seq->d_out;
+    seq->d_out = nullptr;
+    return FPM_OK;
+}
+
+extern "C" {
+
 void fpm_seq_free(fpm_seqtext *j)
 {
     seqtext_release(j);

@@ -3,6 +3,7 @@
 A ctypes mirror of the reference's engine calls for this path:
   Sketch sketching (addMinHashes/MinHashHeap, Sketch.cpp:664-735, 1490-1517) -> Context.sketch
   -fp line hashing (getHashFingerPrint, hash.cpp:45-73)                    -> Context.fp_hash_lines
+  lyn2vec CFL k-fingers (fingerprint_utils.py:95-110, 443-476) + their hashes -> Context.kfinger
   compare/compareSketches/pValue (CommandDistance.cpp:335-450)             -> Context.dist
   contain/containSketches (CommandContain.cpp:314-412)                     -> Context.contain
   screen: hashSequence, sums, -w, pValueWithin (CommandScreen.cpp:133-406) -> Context.screen
@@ -25,7 +26,7 @@ BIN_PATH = os.path.join(PKG_ROOT, "bin", "fpmash")
 
 FPM_OK, FPM_EINVAL, FPM_ENODEV, FPM_EHIP, FPM_ENOMEM = 0, -1, -2, -3, -4
 (K_SKETCH, K_MERGE, K_FPHASH, K_COMPARE, K_FINALIZE, K_INDEX, K_PROBE, K_FPTEXT, K_FILL,
- K_SEQPARSE, K_SCREEN) = range(11)
+ K_SEQPARSE, K_SCREEN, K_KFINGER, K_KFINGER_OUT) = range(13)
 NO_GROUP = 0xFFFFFFFF
 KERNEL_NAMES = {K_SKETCH: "sketch_tiles_kernel", K_MERGE: "merge_kernel",
                 K_FPHASH: "fp_hash_kernel",
@@ -33,7 +34,9 @@ KERNEL_NAMES = {K_SKETCH: "sketch_tiles_kernel", K_MERGE: "merge_kernel",
                 K_FINALIZE: "dist finalize (dense / candidate cells)", K_INDEX: "dist index build",
                 K_PROBE: "probe_rows_kernel", K_FPTEXT: "fp text parse (nl index + fp_line)",
                 K_FILL: "dist_fill_kernel", K_SEQPARSE: "FASTA parse (seq chunk scan + emit)",
-                K_SCREEN: "screen_count_kernel"}
+                K_SCREEN: "screen_count_kernel",
+                K_KFINGER: "kf_hash_kernel (Duval + line hash)",
+                K_KFINGER_OUT: "kfinger pass two (sizes + scan + kf_emit_kernel)"}
 DIST_AUTO, DIST_DENSE, DIST_SPARSE = 0, 1, 2
 # fpm_ctx_last_dist_stats path codes
 DIST_PATHS = ["dense walk", "bucket index + literal walk", "bucket index + bucketed rank"]
@@ -66,6 +69,7 @@ u64p = C.POINTER(C.c_uint64)
 u32p = C.POINTER(C.c_uint32)
 f64p = C.POINTER(C.c_double)
 u8p = C.POINTER(C.c_uint8)
+u16p = C.POINTER(C.c_uint16)
 vp = C.c_void_p
 
 # every symbol include/fpmash.h declares: (name, restype, argtypes)
@@ -132,6 +136,17 @@ SYMBOLS = [
     ("fpm_fp_text_refs", C.c_int, [vp, C.c_uint64, u64p, u64p, u64p, u32p, u64p]),
     ("fpm_fp_text_free", None, [vp]),
     ("fpm_fp_text_limits", None, [u32p, u32p, u32p]),
+    ("fpm_kfinger_stage", C.c_int, [vp, C.c_char_p, u64p, C.c_uint32, C.c_uint32, C.c_uint64,
+                                    C.POINTER(vp), u64p]),
+    ("fpm_kfinger_stage_seq", C.c_int, [vp, vp, u8p, C.c_uint32, C.c_uint64, C.POINTER(vp),
+                                        u64p]),
+    ("fpm_kfinger_run", C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
+    ("fpm_kfinger_fetch", C.c_int, [vp, u64p, vp, u32p]),
+    ("fpm_kfinger_device_output", C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), u64p, u32p]),
+    ("fpm_kfinger_values", C.c_int, [vp, u64p, u16p, C.c_uint64, u64p]),
+    ("fpm_kfinger_text", C.c_int, [vp, C.c_char_p, u64p, vp, C.c_uint64, u64p]),
+    ("fpm_kfinger_free", None, [vp]),
+    ("fpm_kfinger_limits", None, [u32p, u32p]),
     ("fpm_compare_grid", C.c_int, [vp, vp, u32p, C.c_uint64, C.c_uint32, vp, u32p, C.c_uint64,
                                    C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p]),
     ("fpm_compare_grid_dev", C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64,
@@ -344,6 +359,27 @@ def fp_text_limits():
     c, s, h = C.c_uint32(), C.c_uint32(), C.c_uint32()
     lib().fpm_fp_text_limits(C.byref(c), C.byref(s), C.byref(h))
     return c.value, s.value, h.value
+
+
+def kfinger_limits():
+    """(widest window, run length: window starts per workgroup) of the k-finger kernels
+    (fpm_kfinger_limits)."""
+    w, r = C.c_uint32(), C.c_uint32()
+    lib().fpm_kfinger_limits(C.byref(w), C.byref(r))
+    return w.value, r.value
+
+
+def kfinger_id(header: bytes) -> bytes:
+    """The ID of a record's k-finger lines from its header line (the bytes after '>' / '@'): the
+    first whitespace-separated token of the kseq comment (lyn2vec's s_list[1]), or the record's
+    name when the header has no comment, followed by "_0"."""
+    tok = header.split(None, 2)
+    if not tok or header[:1].isspace():
+        # an empty kseq name: the whole line is the comment
+        name, rest = b"", tok
+    else:
+        name, rest = tok[0], tok[1:]
+    return (rest[0] if rest else name) + b"_0"
 
 
 def _p(a, t):
@@ -1333,6 +1369,86 @@ class Context:
             lib().fpm_fp_text_free(job)
         return {"first": first[:m], "id_off": io[:m], "id_len": il[:m], "length": ln[:m],
                 "hash": h[:n], "n_lines": n}
+
+    # --- k-fingers from sequence ----------------------------------------------------
+    @staticmethod
+    def _kfinger_out(job, n, n_rec, seed, use64, ids, values, text):
+        """run + fetch (+ the pass-two outputs) of a staged k-finger job; frees it"""
+        L = lib()
+        try:
+            _check(L.fpm_kfinger_run(job, seed, int(use64), None))
+            first = np.zeros(n_rec + 1, np.uint64)
+            h = np.zeros(max(n, 1), np.uint64 if use64 else np.uint32)
+            nv = np.zeros(max(n, 1), np.uint32)
+            _check(L.fpm_kfinger_fetch(job, _p(first, u64p), h.ctypes.data, _p(nv, u32p)))
+            res = {"n_lines": n, "rec_first_line": first, "hash": h[:n], "n_vals": nv[:n]}
+            if values:
+                tot = C.c_uint64()
+                _check(L.fpm_kfinger_values(job, None, None, 0, C.byref(tot)))
+                vals = np.zeros(max(tot.value, 1), np.uint16)
+                off = np.zeros(n + 1, np.uint64)
+                _check(L.fpm_kfinger_values(job, _p(off, u64p), _p(vals, u16p), tot.value,
+                                            C.byref(tot)))
+                res["val_off"], res["vals"] = off, vals[:tot.value]
+            if text:
+                if ids is None or len(ids) != n_rec:
+                    raise ValueError("text=True needs one ID per record")
+                blob, off = pack_records([bytes(i) for i in ids])
+                nb = C.c_uint64()
+                _check(L.fpm_kfinger_text(job, blob, _p(off, u64p), None, 0, C.byref(nb)))
+                out = np.zeros(max(nb.value, 1), np.uint8)
+                _check(L.fpm_kfinger_text(job, blob, _p(off, u64p), out.ctypes.data, nb.value,
+                                          C.byref(nb)))
+                res["text"] = out[:nb.value].tobytes()
+            return res
+        finally:
+            L.fpm_kfinger_free(job)
+
+    def kfinger(self, seqs, window=100, seed=42, use64=False, max_lines=None, ids=None,
+                values=False, text=False):
+        """CFL k-fingers of the records `seqs` (lyn2vec --type basic --type_factorization CFL,
+        fingerprint_utils.py:95-110, 443-476) and their line hashes (hash.cpp:45-73), on the
+        device.  -> n_lines, rec_first_line (len(seqs) + 1), hash and n_vals per line; with
+        values the factor lengths (vals u16, line l's at val_off[l] .. val_off[l + 1]); with
+        text the lines' text, ids[r] being record r's full ID bytes (lyn2vec's "<id>_0").
+        max_lines: only the first so many lines exist (None: all)."""
+        data, off = pack_records([bytes(s) for s in seqs])
+        job, n = vp(), C.c_uint64()
+        cap = 0xFFFFFFFFFFFFFFFF if max_lines is None else int(max_lines)
+        _check(lib().fpm_kfinger_stage(self.h, data, _p(off, u64p), len(seqs), window, cap,
+                                       C.byref(job), C.byref(n)))
+        return self._kfinger_out(job, n.value, len(seqs), seed, use64, ids, values, text)
+
+    def kfinger_fasta(self, files, take=None, window=100, seed=42, use64=False, max_lines=None,
+                      ids=None, values=False, text=False):
+        """kfinger over the records of FASTA / FASTQ file images parsed on the device
+        (fpm_seq_parse + fpm_kfinger_stage_seq); take[r] false leaves record r out.  ids None:
+        each record's ID by kfinger_id of its header line.  Also returns the parse's records."""
+        seq_job, recs, quality = self.seq_parse(files)
+        try:
+            if quality:
+                raise ValueError("quality lines: walk such input on the host")
+            n_rec = len(recs["seg"])
+            if ids is None:
+                ids = []
+                for r in range(n_rec):
+                    img = files[int(recs["seg"][r])]
+                    o, ln = int(recs["hdr_off"][r]), int(recs["hdr_len"][r])
+                    ids.append(kfinger_id(img[o + 1:o + ln]))
+            t = None
+            if take is not None:
+                t = np.ascontiguousarray(np.asarray(take, dtype=bool), dtype=np.uint8)
+                if t.size == 0:
+                    t = np.zeros(1, np.uint8)
+            job, n = vp(), C.c_uint64()
+            cap = 0xFFFFFFFFFFFFFFFF if max_lines is None else int(max_lines)
+            _check(lib().fpm_kfinger_stage_seq(self.h, seq_job, _p(t, u8p), window, cap,
+                                               C.byref(job), C.byref(n)))
+        finally:
+            lib().fpm_seq_free(seq_job)
+        res = self._kfinger_out(job, n.value, n_rec, seed, use64, ids, values, text)
+        res["records"] = recs
+        return res
 
     def positional(self, ref_lists, qry_lists, use64=False, max_dist=1.0, max_pvalue=1.0):
         """triangle -fp's positional compare over the grid (query-major)."""

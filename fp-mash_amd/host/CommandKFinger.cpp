@@ -1,0 +1,338 @@
+// CommandKFinger.cpp — `fpmash kfinger`: FASTA / FASTQ records -> CFL k-finger lines on the
+// device (fpm_kfinger_*: the cyclic windows, Duval and the line text of lyn2vec's
+// fingerprint_utils.py:95-110, 443-476 and factorizations.py:102-126).  By default the lines
+// are written as one text, the input of `sketch -fp`; with -S they are hashed where they are
+// made (getHashFingerPrint, hash.cpp:45-73) and grouped into the References
+// Sketch::initFromFingerprints (Sketch.cpp:56-151) makes of that text, so the .msh is the one
+// `sketch -fp` writes for it, with no text in between.  Records are found by kseq's rules, like
+// every other verb's; the inputs are streamed in slices of whole records bounded by bytes.
+#include "CommandKFinger.h"
+#include "Device.h"
+#include "SeqReader.h"
+#include "Sketch.h"
+#include "Timing.h"
+
+#include <cctype>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <iostream>
+#include <memory>
+
+namespace fpmhost {
+
+namespace {
+
+const uint64_t kLimitReadFingerprint = 1000000;   // Sketch.cpp:37
+
+// sequence bytes per slice (FPMASH_KFINGER_SLICE overrides, in bytes): a slice of n bases makes
+// up to n lines
+size_t kfingerSliceBytes()
+{
+    const char *v = getenv("FPMASH_KFINGER_SLICE");
+    const long long n = v ? atoll(v) : 0;
+    return n > 0 ? (size_t)n : (size_t)16 << 20;
+}
+
+uint32_t maxWindow()
+{
+    uint32_t w = 0;
+    fpm_kfinger_limits(&w, nullptr);
+    return w;
+}
+
+// The ID of a record's lines: the first whitespace-separated token of its comment (lyn2vec's
+// s_list[1]), or its name when the header has no comment, then "_0" (the forward strand; lyn2vec
+// writes no other, fingerprint_utils.py:276-307).
+std::string lineId(const std::string &name, const std::string &comment)
+{
+    size_t a = 0;
+    while (a < comment.size() && isspace((unsigned char)comment[a])) a++;
+    size_t b = a;
+    while (b < comment.size() && !isspace((unsigned char)comment[b])) b++;
+    return (b > a ? comment.substr(a, b - a) : name) + "_0";
+}
+
+struct Generator {
+    fpm_ctx *ctx = nullptr;
+    uint32_t window = 100;
+    bool sketch = false;
+    uint32_t seed = 42;
+    bool use64 = false;
+    std::string outPath;
+    FILE *out = nullptr;
+    uint64_t records = 0;                 // kseq records read, empty ones included
+    uint64_t linesLeft = ~0ull;           // -S: what is left of the 1,000,000 lines (Sketch.cpp:37, 82)
+    // -S: the lines' hashes and their References so far
+    std::vector<uint64_t> h64;
+    std::vector<uint32_t> h32;
+    std::vector<FingerprintRef> heads;
+    bool haveId = false;
+    std::string lastId;
+
+    bool done() const { return sketch && linesLeft == 0; }
+
+    [[noreturn]] void die(const std::string &msg)
+    {
+        if (out) {
+            fclose(out);
+            remove(outPath.c_str());
+        }
+        std::cerr << "ERROR: " << msg << std::endl;
+        fatalExit();
+    }
+
+    void openText()
+    {
+        if (out || sketch) return;
+        out = fopen(outPath.c_str(), "wb");
+        if (!out) die("could not open " + outPath + " for writing.");
+    }
+
+    // Run a staged job over records with the IDs `ids` and take its lines.  false: the job's
+    // text would reach 2^32 bytes (nothing was taken; the caller splits its records).
+    bool consume(fpm_kfinger *job, uint64_t n, const std::vector<std::string> &ids)
+    {
+        std::unique_ptr<fpm_kfinger, void (*)(fpm_kfinger *)> hold(job, fpm_kfinger_free);
+        check(fpm_kfinger_run(job, seed, use64, nullptr), "kfinger");
+        if (sketch) {
+            std::vector<uint64_t> first(ids.size() + 1);
+            std::vector<uint32_t> nv(n);
+            const size_t at = use64 ? h64.size() : h32.size();
+            if (use64) h64.resize(at + n);
+            else h32.resize(at + n);
+            check(fpm_kfinger_fetch(job, first.data(),
+                                    use64 ? (void *)(h64.data() + at) : (void *)(h32.data() + at),
+                                    nv.data()),
+                  "kfinger");
+            for (size_t r = 0; r < ids.size(); r++) {
+                if (first[r + 1] == first[r]) continue;
+                // a new Reference where the ID changes (Sketch.cpp:104-129)
+                if (!haveId || ids[r] != lastId) {
+                    heads.push_back(FingerprintRef{ids[r], at + first[r], nv[first[r]]});
+                    lastId = ids[r];
+                    haveId = true;
+                }
+                for (uint64_t l = first[r]; l < first[r + 1]; l++) heads.back().length += nv[l];
+            }
+            linesLeft -= n;
+            return true;
+        }
+        std::string blob;
+        std::vector<uint64_t> off(ids.size() + 1, 0);
+        for (size_t r = 0; r < ids.size(); r++) {
+            blob += ids[r];
+            off[r + 1] = blob.size();
+        }
+        uint64_t bytes = 0;
+        const int rc = fpm_kfinger_text(job, blob.data(), off.data(), nullptr, 0, &bytes);
+        if (rc == FPM_EINVAL && bytes > 0xFFFFFFFFull) return false;
+        check(rc, "kfinger");
+        std::unique_ptr<char[]> text(new char[bytes ? bytes : 1]);
+        check(fpm_kfinger_text(job, blob.data(), off.data(), text.get(), bytes, &bytes), "kfinger");
+        openText();
+        if (fwrite(text.get(), 1, bytes, out) != bytes) die("could not write " + outPath + ".");
+        return true;
+    }
+
+    // host records [lo, hi) of one slice
+    void hostJob(const std::string &packed, const std::vector<uint64_t> &off,
+                 const std::vector<std::string> &ids, size_t lo, size_t hi)
+    {
+        if (lo == hi || done()) return;
+        fpm_kfinger *job = nullptr;
+        uint64_t n = 0;
+        check(fpm_kfinger_stage(ctx, packed.data(), off.data() + lo, (uint32_t)(hi - lo), window,
+                                linesLeft, &job, &n),
+              "kfinger");
+        if (consume(job, n, std::vector<std::string>(ids.begin() + lo, ids.begin() + hi))) return;
+        if (hi - lo == 1)
+            die("the k-finger text of record " + ids[lo] + " reaches 2^32 bytes; one record is "
+                "not split over jobs.");
+        hostJob(packed, off, ids, lo, lo + (hi - lo) / 2);
+        hostJob(packed, off, ids, lo + (hi - lo) / 2, hi);
+    }
+
+    // records walked on the host by kseq's rules, given to the device `budget` bytes at a time
+    bool hostWalk(const std::string &image, size_t budget)
+    {
+        SeqReader rd(image.data(), image.size());
+        std::string packed;
+        std::vector<uint64_t> off{0};
+        std::vector<std::string> ids;
+        auto flush = [&] {
+            hostJob(packed, off, ids, 0, ids.size());
+            packed.clear();
+            off.assign(1, 0);
+            ids.clear();
+        };
+        int l;
+        while ((l = rd.read()) >= 0) {
+            records++;
+            if (done()) continue;
+            if (!ids.empty() && packed.size() + rd.seq.size() > budget) flush();
+            packed += rd.seq;
+            off.push_back(packed.size());
+            ids.push_back(lineId(rd.name, rd.comment));
+        }
+        flush();
+        return l == -1;
+    }
+
+    // one input file: parsed and packed on the device when it fits a slice and has no FASTQ
+    // quality lines, else walked on the host
+    bool file(const std::string &image)
+    {
+        const size_t budget = kfingerSliceBytes();
+        if (image.size() > budget) return hostWalk(image, budget);
+        fpm_seqtext *parsed = nullptr;
+        uint64_t nRec = 0;
+        int quality = 0;
+        const char *ptr = image.data();
+        const uint64_t len = image.size();
+        check(fpm_seq_parse(ctx, &ptr, &len, 1, &parsed, &nRec, &quality), "sequence parse");
+        if (quality) {
+            fpm_seq_free(parsed);
+            return hostWalk(image, budget);
+        }
+        std::vector<uint32_t> seg(nRec);
+        std::vector<uint64_t> ho(nRec), hl(nRec), sl(nRec);
+        check(fpm_seq_records(parsed, seg.data(), ho.data(), hl.data(), sl.data()), "sequence parse");
+        std::vector<uint8_t> take(nRec ? nRec : 1, 0);
+        std::vector<std::string> ids(nRec);
+        uint64_t found = 0;
+        for (uint64_t r = 0; r < nRec; r++) {
+            // a '>' / '@' as the last byte of a file starts no record (kseq_read returns -1)
+            if (ho[r] + 1 >= image.size()) continue;
+            found++;
+            take[r] = 1;
+            std::string name, comment;
+            splitHeader(image.data() + ho[r] + 1, hl[r] - 1, name, comment);
+            ids[r] = lineId(name, comment);
+        }
+        bool ok = true;
+        if (found && !done()) {
+            fpm_kfinger *job = nullptr;
+            uint64_t n = 0;
+            check(fpm_kfinger_stage_seq(ctx, parsed, take.data(), window, linesLeft, &job, &n),
+                  "kfinger");
+            ok = consume(job, n, ids);
+        }
+        fpm_seq_free(parsed);
+        if (!ok) return hostWalk(image, budget);   // (counts the records itself)
+        records += found;
+        return true;
+    }
+};
+
+}  // namespace
+
+CommandKFinger::CommandKFinger()
+{
+    name = "kfinger";
+    summary = "Create k-finger fingerprints (CFL) from sequences.";
+    description = "Create the CFL k-finger lines of sequences (lyn2vec --type basic "
+                  "--type_factorization CFL): for every record and every cyclic window of it, the "
+                  "lengths of the window's Lyndon factors. Inputs can be fasta or fastq files "
+                  "(gzipped or not), and \"-\" can be given to read from standard input. The lines "
+                  "of all inputs are written to <prefix>.txt, the input of `sketch -fp`; with -S "
+                  "they are sketched instead, into the <prefix>.msh that `sketch -fp` writes for "
+                  "that text.";
+    argumentString = "<input> [<input>] ...";
+    useOption("help");
+    addOption("window", Option(Option::Integer, "w", "Input",
+        "Window size. Each record of at least this many bases gives one line per cyclic window "
+        "start, a shorter record one line.", "100", 1, maxWindow()));
+    addOption("prefix", Option(Option::File, "o", "Output",
+        "Output prefix (first input file used if unspecified). The suffix '.txt' (or '.msh' with "
+        "-S) will be appended.", ""));
+    addOption("sketch", Option(Option::Boolean, "S", "Output",
+        "Write the sketch of the k-finger lines (as `sketch -fp` of the text) instead of the "
+        "text.", ""));
+    // the sketch options of `sketch -fp` (its -w, the k-mer size warning, does not apply to
+    // fingerprints; its seed is -seed here, -S and -w being taken)
+    for (const char *n : {"threads", "kmer", "noncanonical", "protein", "alphabet", "case",
+                          "sketchSize", "individual", "reads", "memory", "minCov", "targetCov",
+                          "genome"})
+        useOption(n);
+    addOption("seed", Option(Option::Integer, "seed", "Sketch",
+        "Seed to provide to the hash function.", "42", 0, 0xFFFFFFFF));
+}
+
+int CommandKFinger::run() const
+{
+    if (arguments.empty() || options.at("help").active) {
+        print();
+        return 0;
+    }
+    Parameters parameters;
+    if (sketchParameterSetup(parameters, *this)) return 1;
+    if (parameters.reads) {
+        std::cerr << "ERROR: the reads options do not apply to k-finger lines." << std::endl;
+        return 1;
+    }
+    // what -fp makes of the sketch options (sketchParameterSetup.cpp:100-106)
+    parameters.fingerprint = true;
+    parameters.kmerSize = 1;
+    parameters.noncanonical = true;
+    setAlphabetFromString(parameters, "0123456789");
+    // (the window's range was checked when the option was read)
+    const uint32_t window = (uint32_t)options.at("window").getArgumentAsNumber();
+    for (size_t f = 0; f < arguments.size(); f++) {
+        if (arguments[f] == "-") {
+            if (f > 0) {
+                std::cerr << "ERROR: '-' for stdin must be first input" << std::endl;
+                return 1;
+            }
+        } else if (FILE *fp = fopen(arguments[f].c_str(), "r")) {
+            fclose(fp);
+        } else {
+            std::cerr << "ERROR: could not open " << arguments[f] << std::endl;
+            return 1;
+        }
+    }
+    warmDevices();
+    Generator g;
+    g.window = window;
+    g.sketch = options.at("sketch").active;
+    g.seed = parameters.seed;
+    g.use64 = parameters.use64;
+    if (g.sketch) g.linesLeft = kLimitReadFingerprint;
+    std::string prefix;
+    if (!options.at("prefix").argument.empty()) prefix = options.at("prefix").argument;
+    else prefix = arguments[0] == "-" ? "stdin" : arguments[0];
+    const char *suffix = g.sketch ? suffixSketch : ".txt";
+    if (!hasSuffix(prefix, suffix)) prefix += suffix;
+    g.outPath = prefix;
+    g.ctx = device();
+    phaseMark("device context");
+
+    // one file image at a time: device and host memory follow the slices
+    for (size_t f = 0; f < arguments.size(); f++) {
+        if (g.done() && g.records) break;
+        std::string image;
+        if (!loadSequenceFile(arguments[f], image)) g.die("could not open " + arguments[f]);
+        if (!g.file(image)) g.die("reading " + arguments[f] + ".");
+    }
+    phaseMark("k-fingers (read + parse + factorize)");
+    if (g.records == 0) g.die("Did not find sequence records in inputs");
+    if (!g.sketch) {
+        g.openText();   // records without a base: an empty text
+        if (fclose(g.out) != 0) {
+            g.out = nullptr;
+            g.die("could not write " + g.outPath + ".");
+        }
+        phaseMark("text write");
+        return 0;
+    }
+    std::unique_ptr<Sketch> owned(new Sketch());
+    const uint64_t nLines = parameters.use64 ? g.h64.size() : g.h32.size();
+    owned->initFromFingerprintLines(g.heads, nLines, parameters.use64 ? g.h64.data() : nullptr,
+                                    parameters.use64 ? nullptr : g.h32.data(), parameters);
+    std::cerr << "Writing to " << prefix << "..." << std::endl;
+    owned->writeToMsh(prefix);
+    if (!cleanExit()) (void)owned.release();
+    return 0;
+}
+
+}  // namespace fpmhost

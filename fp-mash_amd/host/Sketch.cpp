@@ -745,25 +745,42 @@ void Sketch::initFromFingerprints(const std::vector<std::string> &files, const P
                       << "\" from a previous file." << std::endl;
             fatalExit();
         }
-        std::vector<Reference> fileRefs(nr);
-        for (uint64_t r = 0; r < nr; r++) {
-            Reference &ref = fileRefs[r];
-            const std::string id(text.data() + idOff[r], idLen[r]);
-            ref.id = id;
-            ref.length = len[r];
-            ref.name = id;
-            ref.comment = "FingerPrint : " + id;
-            const uint64_t a = first[r], b = r + 1 < nr ? first[r + 1] : n;
-            ref.hashes.resize(b - a);
-            for (uint64_t i = a; i < b; i++)
-                ref.hashes[i - a] = parameters.use64 ? h64[i] : (uint64_t)h32[i];
-        }
-        if (nr) lastID.assign(text.data() + idOff[nr - 1], idLen[nr - 1]);
+        std::vector<FingerprintRef> heads(nr);
+        for (uint64_t r = 0; r < nr; r++)
+            heads[r] = FingerprintRef{std::string(text.data() + idOff[r], idLen[r]), first[r], len[r]};
+        appendFingerprintReferences(heads, n, parameters.use64 ? h64.data() : nullptr,
+                                    parameters.use64 ? nullptr : h32.data(), references);
+        if (nr) lastID = heads[nr - 1].id;
         phaseMark("fingerprint parse + references (device)");
-        for (auto &r : fileRefs) references.push_back(std::move(r));
     }
     createIndex();
     std::cout << "Initialization complete." << std::endl;
+}
+
+void appendFingerprintReferences(const std::vector<FingerprintRef> &heads, uint64_t nLines,
+                                 const uint64_t *h64, const uint32_t *h32,
+                                 std::vector<Reference> &out)
+{
+    const size_t nr = heads.size();
+    for (size_t r = 0; r < nr; r++) {
+        Reference ref;
+        ref.id = heads[r].id;
+        ref.length = heads[r].length;
+        ref.name = heads[r].id;
+        ref.comment = "FingerPrint : " + heads[r].id;
+        const uint64_t a = heads[r].firstLine, b = r + 1 < nr ? heads[r + 1].firstLine : nLines;
+        ref.hashes.resize(b - a);
+        for (uint64_t i = a; i < b; i++) ref.hashes[i - a] = h64 ? h64[i] : (uint64_t)h32[i];
+        out.push_back(std::move(ref));
+    }
+}
+
+void Sketch::initFromFingerprintLines(const std::vector<FingerprintRef> &heads, uint64_t nLines,
+                                      const uint64_t *h64, const uint32_t *h32, const Parameters &p)
+{
+    parameters = p;
+    appendFingerprintReferences(heads, nLines, h64, h32, references);
+    createIndex();
 }
 
 int Sketch::writeToMsh(const std::string &file) const

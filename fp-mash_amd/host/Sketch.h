@@ -56,8 +56,28 @@ struct Reference {
     const uint32_t *countData() const { return countView ? countView : counts.data(); }
 };
 
+// One Reference of a run of k-finger lines as initFromFingerprints groups them (Sketch.cpp:
+// 104-145): the ID the run's lines carry, its first line, and its length (the first line's value
+// count, :117, plus every line's, :134).
+struct FingerprintRef {
+    std::string id;
+    uint64_t firstLine = 0;
+    uint64_t length = 0;
+};
+
+// The References of nLines hashed k-finger lines (h64 or h32, the other NULL), heads[r] starting
+// Reference r at its first line: name = the ID, comment = "FingerPrint : <ID>", hashes in line
+// order (Sketch.cpp:104-145).  What `sketch -fp` builds from a text's lines and `kfinger -S` from
+// the lines it generates.
+void appendFingerprintReferences(const std::vector<FingerprintRef> &heads, uint64_t nLines,
+                                 const uint64_t *h64, const uint32_t *h32,
+                                 std::vector<Reference> &out);
+
 class Sketch {
 public:
+    // initFromFingerprints over lines that never were text (`kfinger -S`)
+    void initFromFingerprintLines(const std::vector<FingerprintRef> &heads, uint64_t nLines,
+                                  const uint64_t *h64, const uint32_t *h32, const Parameters &p);
     // Sketch::initFromFiles (Sketch.cpp:249-397): .msh inputs are loaded, sequence
     // files are sketched on the GPU (one sketch per file, or per record with -i).
     int initFromFiles(const std::vector<std::string> &files, const Parameters &p,

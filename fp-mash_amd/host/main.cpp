@@ -1,8 +1,10 @@
 // main.cpp — `fpmash`: the reference's CLI entry (mash.cpp:19-40) for the hot-path
 // verbs.  `fpmash sketch|dist|info|paste|triangle|contain|screen|taxscreen [-fp] ...` is a drop-in
-// for the same `mash` verbs.
+// for the same `mash` verbs; `fpmash kfinger` makes the k-finger lines `-fp` reads (lyn2vec's CFL
+// generator).
 #include "Command.h"
 #include "CommandContain.h"
+#include "CommandKFinger.h"
 #include "CommandScreen.h"
 #include "CommandTaxScreen.h"
 #include "Timing.h"
@@ -31,6 +33,7 @@ int main(int argc, const char **argv)
     commandList.addCommand(new fpmhost::CommandContain());
     commandList.addCommand(new fpmhost::CommandScreen());
     commandList.addCommand(new fpmhost::CommandTaxScreen());
+    commandList.addCommand(new fpmhost::CommandKFinger());
     const int rc = commandList.run(argc, argv);
     fpmhost::phaseMark("command done");
     // Every output is written and the device work is complete (results were fetched): leave

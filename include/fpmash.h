@@ -96,7 +96,8 @@ int fpm_memset(fpm_ctx *ctx, void *dptr, int value, size_t bytes);
 
 /* Per-kernel timing with HIP events recorded on the launch stream.
  * kernel ids: sketch tiles, sketch merge, fp hash, compare walk, finalize,
- * dist index build (insert + scan + scatter + probe count), dist row probe. */
+ * dist index build (insert + scan + scatter + probe count), dist row probe, ...; the two
+ * passes of the k-finger generator last. */
 #define FPM_K_SKETCH 0
 #define FPM_K_MERGE 1
 #define FPM_K_FPHASH 2
@@ -108,7 +109,9 @@ int fpm_memset(fpm_ctx *ctx, void *dptr, int value, size_t bytes);
 #define FPM_K_FILL 8
 #define FPM_K_SEQPARSE 9
 #define FPM_K_SCREEN 10   /* screen: the pool count pass (screen_count_kernel) */
-#define FPM_K_COUNT 11
+#define FPM_K_KFINGER 11      /* kfinger pass one: Duval + line hash (kf_hash_kernel) */
+#define FPM_K_KFINGER_OUT 12  /* kfinger pass two: sizes, scan, values / text (kf_emit_kernel) */
+#define FPM_K_COUNT 13
 /* one-pass bucket-index builds (dist_index.hip) that overflowed a level-1 slot and were
  * redone by the exact two-pass build, since the context was created */
 int fpm_ctx_index_rebuilds(fpm_ctx *ctx, uint64_t *count);
@@ -381,6 +384,55 @@ void fpm_fp_text_free(fpm_fptext *job);
  * wave span (64 lines, from the 16-byte block of the line before them) the line kernel stages
  * in LDS before it reads global memory instead, and lines per head-count workgroup. */
 void fpm_fp_text_limits(uint32_t *text_chunk, uint32_t *span_bytes, uint32_t *head_lines);
+
+/* ---- k-fingers from sequence --------------------------------------------------------
+ * Replaces lyn2vec `--type basic --type_factorization CFL` (the cyclic windows and their lines,
+ * fingerprint_utils.py:95-110, 443-476; Duval's factorization, factorizations.py:102-126) and
+ * the per-line getHashFingerPrint that follows it in Sketch::initFromFingerprints (hash.cpp:
+ * 45-73): the k-finger lines of sequence records and their hashes, with no text in between.
+ * A record of n bytes (ASCII a-z upper-cased, every other byte as it is) and a window w gives
+ * one line, the Lyndon factor lengths of the record, when n < w; n lines when n >= w, line i the
+ * factor lengths of the cyclic window (s + s[:w])[i : i + w]; none when n == 0.  Bytes compare
+ * unsigned.  Lines are numbered in record order, then window-start order; only the first
+ * max_lines exist (a cut may fall inside a record) and *n_lines is their number.
+ * fpm_kfinger_stage (fingerprint_utils.py:95-110: the windows of the records read): host records
+ * laid out as for fpm_sketch_stage, record r = seq[rec_off[r] .. rec_off[r+1]), bytes 0x01-0xFF.
+ * fpm_kfinger_stage_seq (the same, over kseq records): the records of a device parse; take[r]
+ * == 0 leaves record r out (take == NULL: every record); the job takes over the packed records
+ * as fpm_sketch_stage_seq does (stage once per parse).
+ * window outside 1 .. the limit of fpm_kfinger_limits, or a record of 2^32 bytes or more, is
+ * FPM_EINVAL.
+ * fpm_kfinger_run (factorizations.py:102-126 + hash.cpp:45-73): pass one on `stream` (NULL: the
+ * context's): per line the hash of its 8 x count little-endian bytes (u32, or u64 with use64:
+ * what fpm_fp_hash_lines gives for the same values) and its value count.
+ * fpm_kfinger_fetch: rec_first_line[r] = the first line of input record r (n_rec + 1 entries,
+ * the last one *n_lines; a record without lines repeats the next one's), the hashes and the value
+ * counts, copied back; any output may be NULL.  fpm_kfinger_device_output: the hashes and counts
+ * on the device (valid until the job is freed or run again).
+ * Pass two, after run (fingerprint_utils.py:443-476: the lines written): fpm_kfinger_values, the
+ * factor lengths as u16, line l's at vals[val_off[l] .. val_off[l+1]) (val_off: n_lines + 1
+ * entries, may be NULL); fpm_kfinger_text, the text, one line "<id> <len> <len> ...\n" per
+ * line, formatted on the device; ids holds each input record's full ID bytes (lyn2vec's
+ * "<id>_0"), record r's at ids[id_off[r] .. id_off[r+1]).  Both follow fpm_seq_packed's sizing:
+ * out == NULL only reports *total / *n_bytes, else FPM_EINVAL where cap is smaller.  A job whose
+ * text would reach 2^32 bytes (or whose values 2^32) is FPM_EINVAL: split the records over jobs.
+ * fpm_kfinger_limits (no device needed; any output may be NULL): the widest window and the run
+ * length, the window starts one workgroup takes, for tests that build inputs on them. */
+typedef struct fpm_kfinger fpm_kfinger;
+int fpm_kfinger_stage(fpm_ctx *ctx, const char *seq, const uint64_t *rec_off, uint32_t n_rec,
+                      uint32_t window, uint64_t max_lines, fpm_kfinger **job, uint64_t *n_lines);
+int fpm_kfinger_stage_seq(fpm_ctx *ctx, fpm_seqtext *seq, const uint8_t *take, uint32_t window,
+                          uint64_t max_lines, fpm_kfinger **job, uint64_t *n_lines);
+int fpm_kfinger_run(fpm_kfinger *job, uint32_t seed, uint32_t use64, void *stream);
+int fpm_kfinger_fetch(fpm_kfinger *job, uint64_t *rec_first_line, void *hash, uint32_t *n_vals);
+int fpm_kfinger_device_output(fpm_kfinger *job, void **d_hash, uint32_t **d_n_vals,
+                              uint64_t *n_lines, uint32_t *hash_bytes);
+int fpm_kfinger_values(fpm_kfinger *job, uint64_t *val_off, uint16_t *vals, uint64_t cap,
+                       uint64_t *total);
+int fpm_kfinger_text(fpm_kfinger *job, const char *ids, const uint64_t *id_off, char *out,
+                     uint64_t cap, uint64_t *n_bytes);
+void fpm_kfinger_free(fpm_kfinger *job);
+void fpm_kfinger_limits(uint32_t *max_window, uint32_t *run_length);
 
 /* ---- dist ---------------------------------------------------------------------
  * Replaces compare()/compareSketches()/pValue() (CommandDistance.cpp:335-450) over
