@@ -84,8 +84,7 @@ struct fpm_comm {
     int device = 0, nranks = 0, rank = 0;
     ncclComm_t comm = nullptr;
     // grow-only gather buffers of the min-merge: [nranks][s] hashes, [nranks] counts
-    void *rows = nullptr, *counts = nullptr;
-    size_t rows_bytes = 0, counts_bytes = 0;
+    fpm_ctx::Slot rows, counts;
 };
 
 namespace {
@@ -186,8 +185,6 @@ void fpm_comm_destroy(fpm_comm *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->comm) (void)rccl().comm_destroy(c->comm);
-    if (c->rows) (void)hipFree(c->rows);
-    if (c->counts) (void)hipFree(c->counts);
     delete c;
 }
 
@@ -210,28 +207,27 @@ int fpm_sketch_min_merge_comm(fpm_comm *c, const uint64_t *d_row, const uint32_t
     if (hipSetDevice(c->device) != hipSuccess) return fail(FPM_EHIP, "hipSetDevice");
     hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)fpm_ctx_stream(c->ctx);
     const size_t rb = (size_t)c->nranks * s * 8, cb = (size_t)c->nranks * 4;
-    auto grow = [&](void **p, size_t *have, size_t want) -> int {
-        if (*have >= want) return FPM_OK;
+    void *rows, *counts;
+    auto grow = [&](fpm_ctx::Slot &sl, size_t want, void **out) -> int {
         // the previous gather into it may still be queued
-        if (*p && (hipStreamSynchronize(st) != hipSuccess || hipFree(*p) != hipSuccess))
+        if (sl.p && sl.bytes < want && hipStreamSynchronize(st) != hipSuccess)
             return fail(FPM_EHIP, "min_merge_comm: buffer release");
-        *p = nullptr;
-        *have = 0;
-        if (hipMalloc(p, want) != hipSuccess) return fail(FPM_ENOMEM, "min_merge_comm: hipMalloc");
-        *have = want;
+        const hipError_t e = grow_slot(sl, want, out);
+        if (e == hipErrorOutOfMemory) return fail(FPM_ENOMEM, "min_merge_comm: hipMalloc");
+        if (e != hipSuccess) return fail(FPM_EHIP, "min_merge_comm: buffer release");
         return FPM_OK;
     };
-    if (int rc = grow(&c->rows, &c->rows_bytes, rb)) return rc;
-    if (int rc = grow(&c->counts, &c->counts_bytes, cb)) return rc;
+    if (int rc = grow(c->rows, rb, &rows)) return rc;
+    if (int rc = grow(c->counts, cb, &counts)) return rc;
     Rccl &r = rccl();
     if (ncclResult_t rc = r.group_start()) return rccl_fail("ncclGroupStart", rc);
-    ncclResult_t a = r.all_gather(d_row, c->rows, (size_t)s * 8, ncclUint8, c->comm, st);
-    ncclResult_t b = a ? a : r.all_gather(d_count, c->counts, 4, ncclUint8, c->comm, st);
+    ncclResult_t a = r.all_gather(d_row, rows, (size_t)s * 8, ncclUint8, c->comm, st);
+    ncclResult_t b = a ? a : r.all_gather(d_count, counts, 4, ncclUint8, c->comm, st);
     ncclResult_t e = r.group_end();
     if (a || b || e) return rccl_fail("ncclAllGather (min-merge)", a ? a : b ? b : e);
     // the merge on the same stream, after the gather (fpm_sketch_merge_dev: pairwise rounds)
-    const int rc = fpm_sketch_merge_dev(c->ctx, (const uint64_t *)c->rows,
-                                        (const uint32_t *)c->counts, (uint32_t)c->nranks, s,
+    const int rc = fpm_sketch_merge_dev(c->ctx, (const uint64_t *)rows,
+                                        (const uint32_t *)counts, (uint32_t)c->nranks, s,
                                         d_out, d_out_count, st);
     if (rc) return fail(rc, std::string("min_merge_comm: ") + fpm_last_error());
     return FPM_OK;

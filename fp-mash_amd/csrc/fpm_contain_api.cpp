@@ -6,11 +6,6 @@
 
 namespace {
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
 int contain_impl(fpm_ctx *ctx, const void *d_ref, const uint32_t *d_ref_len, uint64_t ref_stride,
                  uint32_t n_ref, const void *d_qry, const uint32_t *d_qry_len,
                  uint64_t qry_stride, uint32_t n_qry, uint32_t hash_bytes, uint32_t *d_common,
@@ -82,26 +77,22 @@ int fpm_contain(fpm_ctx *ctx, const void *ref, const uint32_t *ref_len, uint64_t
         return fail(FPM_EINVAL, "fpm_contain: null buffer");
     // one set against itself: one upload
     const bool same = ref == qry && ref_len == qry_len && ref_stride == qry_stride && n_ref == n_qry;
-    DevBuf r, rl, q, ql, co, stp;
-    auto up = [&](DevBuf &b, const void *h, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(&b.p, bytes ? bytes : 16);
-        if (e == hipSuccess && h && bytes) e = copy_in(ctx, b.p, h, bytes);
-        return e;
-    };
-    hipError_t e = up(r, ref, (size_t)n_ref * ref_stride * hash_bytes);
-    if (e == hipSuccess) e = up(rl, ref_len, (size_t)n_ref * 4);
-    if (e == hipSuccess && !same) e = up(q, qry, (size_t)n_qry * qry_stride * hash_bytes);
-    if (e == hipSuccess && !same) e = up(ql, qry_len, (size_t)n_qry * 4);
-    if (e == hipSuccess) e = up(co, nullptr, np * 4);
-    if (e == hipSuccess) e = up(stp, nullptr, np * 4);
+    DevBufs mem;
+    void *r, *q = nullptr;
+    uint32_t *rl, *ql = nullptr, *co, *stp;
+    hipError_t e = mem.upload(ctx, &r, ref, (size_t)n_ref * ref_stride * hash_bytes);
+    if (e == hipSuccess) e = mem.upload(ctx, &rl, ref_len, (size_t)n_ref * 4);
+    if (e == hipSuccess && !same) e = mem.upload(ctx, &q, qry, (size_t)n_qry * qry_stride * hash_bytes);
+    if (e == hipSuccess && !same) e = mem.upload(ctx, &ql, qry_len, (size_t)n_qry * 4);
+    if (e == hipSuccess) e = mem.get(&co, np * 4);
+    if (e == hipSuccess) e = mem.get(&stp, np * 4);
     if (e != hipSuccess) return fail(FPM_ENOMEM, std::string("contain staging: ") + hipGetErrorString(e));
-    if (int rc = contain_impl(ctx, r.p, (const uint32_t *)rl.p, ref_stride, n_ref,
-                              same ? r.p : q.p, (const uint32_t *)(same ? rl.p : ql.p), qry_stride,
-                              n_qry, hash_bytes, (uint32_t *)co.p, (uint32_t *)stp.p, nullptr))
+    if (int rc = contain_impl(ctx, r, rl, ref_stride, n_ref, same ? r : q, same ? rl : ql, qry_stride,
+                              n_qry, hash_bytes, co, stp, nullptr))
         return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(copy_out(ctx, out_common, co.p, np * 4));
-    HIP_TRY(copy_out(ctx, out_steps, stp.p, np * 4));
+    HIP_TRY(copy_out(ctx, out_common, co, np * 4));
+    HIP_TRY(copy_out(ctx, out_steps, stp, np * 4));
     return FPM_OK;
 }
 

@@ -17,44 +17,6 @@ int fail(int code, const std::string &msg)
     return code;
 }
 
-// smallest pooled buffer of >= bytes (and at most 4x: a 1 GB buffer is not kept busy by a
-// 1 KB request), else a new one
-hipError_t pool_alloc(fpm_ctx *ctx, void **p, size_t bytes)
-{
-    {
-        std::lock_guard<std::mutex> g(ctx->pool_mu);
-        size_t best = SIZE_MAX, bi = 0;
-        for (size_t i = 0; i < ctx->pool.size(); i++) {
-            const size_t b = ctx->pool[i].second;
-            if (b >= bytes && b <= 4 * bytes + 4096 && b < best) { best = b; bi = i; }
-            if (best == bytes) break;
-        }
-        if (best != SIZE_MAX) {
-            *p = ctx->pool[bi].first;
-            ctx->pool_bytes -= best;
-            ctx->pool[bi] = ctx->pool.back();
-            ctx->pool.pop_back();
-            return hipSuccess;
-        }
-    }
-    return hipMalloc(p, bytes);
-}
-
-// back to the pool (the caller's stream work on it is complete), or freed past kPoolBytes
-void pool_free(fpm_ctx *ctx, void *p, size_t bytes)
-{
-    if (!p) return;
-    {
-        std::lock_guard<std::mutex> g(ctx->pool_mu);
-        if (ctx->pool_bytes + bytes <= fpm_ctx::kPoolBytes) {
-            ctx->pool.push_back({p, bytes});
-            ctx->pool_bytes += bytes;
-            return;
-        }
-    }
-    (void)hipFree(p);
-}
-
 // Synchronous copies and memsets run on the context stream, after the work queued there, and
 // never on the null stream: the null stream's first use in a process creates one more
 // hardware queue (~9 ms in the CLI's trace), and a separate copy stream cost another ~8 ms of
@@ -242,22 +204,6 @@ int read_counters(fpm_ctx *ctx, const unsigned long long *d_src, uint32_t n,
     return wait_counters(ctx, seq, st);
 }
 
-// a device buffer of at least `bytes` in the grow-only slot `s` (12 % headroom on growth)
-hipError_t grow_slot(fpm_ctx::Slot &s, size_t bytes, void **out)
-{
-    if (s.bytes < bytes) {
-        if (s.p) { hipError_t e = hipFree(s.p); if (e != hipSuccess) return e; }
-        s.p = nullptr;
-        s.bytes = 0;
-        size_t b = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&s.p, b);
-        if (e != hipSuccess) return e;
-        s.bytes = b;
-    }
-    *out = s.p;
-    return hipSuccess;
-}
-
 // returns a device buffer of at least `bytes` for scratch slot `id`
 hipError_t scratch(fpm_ctx *ctx, ScratchSlot id, size_t bytes, void **out)
 {
@@ -327,8 +273,6 @@ void fpm_ctx_destroy(fpm_ctx *ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     fpm_ctx_reset_timing(ctx);
-    for (auto &s : ctx->scratch)
-        if (s.p) (void)hipFree(s.p);
     if (ctx->host_counters) (void)hipHostFree(ctx->host_counters);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->aux) (void)hipStreamDestroy(ctx->aux);

@@ -155,9 +155,9 @@ static int build_index(fpm_ctx *ctx, const RowSet &R, uint32_t hash_bytes, IdxGe
 // query blocks probe it without re-uploading the references or rebuilding the index.
 struct fpm_refset {
     fpm_ctx *ctx = nullptr;
-    RowSet ref{};                 // the reference rows (owned when uploaded from host buffers)
+    RowSet ref{};                 // the reference rows (in `mem` when uploaded from host buffers)
     uint32_t hash_bytes = 0, sketch_size = 0;
-    void *own[3] = {nullptr, nullptr, nullptr};
+    DevBufs mem;                  // owns those rows and kmax
     // the index: directory, entries, and the record rows / lengths / positions it is built
     // over when the rows are unsorted; the largest indexed key; host state
     enum { kDir, kEntries, kRecRows, kRecLen, kRecPos, kIdxSlots };
@@ -193,7 +193,7 @@ static int refset_build_index(fpm_refset *rs, hipStream_t st)
     if (!rs->sparse_ok) return FPM_OK;
     void *ctr;
     HIP_TRY(scratch(ctx, kSlotCounters, kCtrWords * 8, &ctr));
-    if (!rs->kmax) HIP_TRY(hipMalloc((void **)&rs->kmax, 8));
+    if (!rs->kmax) HIP_TRY(rs->mem.get(&rs->kmax, 8));
     auto build = [&](const RowSet &rows, IdxGeom &g, bool raw) -> int {
         void *dir, *entries;
         HIP_TRY(grow_slot(rs->slot[fpm_refset::kDir], ((1ULL << g.nbits) + 1) * 4, &dir));
@@ -1008,22 +1008,20 @@ static int list_out(void *numer, void *denom, bool c16, const fpm_cell_list *l, 
 }
 
 namespace {
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
 // The device side of a host-memory grid call (fpm_dist, fpm_fp_positional_grid): the uploaded
 // rows and the five result grids, freed on every return path.
 struct GridStage {
     fpm_ctx *ctx;
     hipError_t e = hipSuccess;
-    DevBuf r, rl, rL, q, ql, qL, nu, de, di, pv, pa;
-    void up(DevBuf &b, const void *h, size_t bytes)
+    DevBufs mem;
+    void *r = nullptr, *q = nullptr;
+    uint32_t *rl = nullptr, *ql = nullptr, *nu = nullptr, *de = nullptr;
+    uint64_t *rL = nullptr, *qL = nullptr;
+    double *di = nullptr, *pv = nullptr;
+    uint8_t *pa = nullptr;
+    template <typename T> void up(T *&b, const void *h, size_t bytes)
     {
-        if (e != hipSuccess) return;
-        e = hipMalloc(&b.p, bytes ? bytes : 16);
-        if (e == hipSuccess && h && bytes) e = copy_in(ctx, b.p, h, bytes);
+        if (e == hipSuccess) e = mem.upload(ctx, &b, h, bytes);
     }
     // the result grids of np cells: the counts, and with `full` distance / p-value / pass
     void results(uint64_t np, bool full)
@@ -1040,11 +1038,11 @@ struct GridStage {
               uint8_t *pass)
     {
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (numer) HIP_TRY(copy_out(ctx, numer, nu.p, np * 4));
-        if (denom) HIP_TRY(copy_out(ctx, denom, de.p, np * 4));
-        if (dist) HIP_TRY(copy_out(ctx, dist, di.p, np * 8));
-        if (pvalue) HIP_TRY(copy_out(ctx, pvalue, pv.p, np * 8));
-        if (pass) HIP_TRY(copy_out(ctx, pass, pa.p, np));
+        if (numer) HIP_TRY(copy_out(ctx, numer, nu, np * 4));
+        if (denom) HIP_TRY(copy_out(ctx, denom, de, np * 4));
+        if (dist) HIP_TRY(copy_out(ctx, dist, di, np * 8));
+        if (pvalue) HIP_TRY(copy_out(ctx, pvalue, pv, np * 8));
+        if (pass) HIP_TRY(copy_out(ctx, pass, pa, np));
         return FPM_OK;
     }
 };
@@ -1261,14 +1259,12 @@ int fpm_dist(fpm_ctx *ctx, const void *ref, const uint32_t *ref_len, const uint6
     }
     g.results(np, fin);
     if (g.e != hipSuccess) return fail(FPM_ENOMEM, std::string("dist staging: ") + hipGetErrorString(g.e));
-    const RowSet R{g.r.p, (const uint32_t *)g.rl.p, (const uint64_t *)g.rL.p, ref_stride, n_ref};
-    const RowSet Q{same ? g.r.p : g.q.p, (const uint32_t *)(same ? g.rl.p : g.ql.p),
-                   (const uint64_t *)g.qL.p, qry_stride, n_qry};
-    const Counts cnt{g.nu.p, g.de.p, false};
+    const RowSet R{g.r, g.rl, g.rL, ref_stride, n_ref};
+    const RowSet Q{same ? g.r : g.q, same ? g.rl : g.ql, g.qL, qry_stride, n_qry};
+    const Counts cnt{g.nu, g.de, false};
     int rc = fin ? dist_dev_impl(ctx, R, Q, hash_bytes, sketch_size,
                                  DistParams{kmer_size, kmer_space, max_dist, max_pvalue},
-                                 full_out(cnt.numer, cnt.denom, false, (double *)g.di.p,
-                                          (double *)g.pv.p, (uint8_t *)g.pa.p),
+                                 full_out(cnt.numer, cnt.denom, false, g.di, g.pv, g.pa),
                                  nullptr, "fpm_dist_dev")
                  : compare_impl(ctx, R, Q, hash_bytes, sketch_size, cnt, nullptr);
     if (rc) return rc;
@@ -1305,10 +1301,8 @@ int fpm_fp_positional_grid(fpm_ctx *ctx, const void *ref, const uint32_t *ref_le
     g.up(g.ql, qry_len, (size_t)n_qry * 4);
     g.results(np, true);
     if (g.e != hipSuccess) return fail(FPM_ENOMEM, std::string("positional staging: ") + hipGetErrorString(g.e));
-    HIP_TRY(launch_positional_grid(g.r.p, (const uint32_t *)g.rl.p, ref_stride, n_ref, g.q.p,
-                                   (const uint32_t *)g.ql.p, qry_stride, n_qry, hash_bytes,
-                                   max_dist, max_pvalue, (uint32_t *)g.nu.p, (uint32_t *)g.de.p,
-                                   (double *)g.di.p, (double *)g.pv.p, (uint8_t *)g.pa.p,
+    HIP_TRY(launch_positional_grid(g.r, g.rl, ref_stride, n_ref, g.q, g.ql, qry_stride, n_qry,
+                                   hash_bytes, max_dist, max_pvalue, g.nu, g.de, g.di, g.pv, g.pa,
                                    ctx->stream));
     return g.fetch(np, out_numer, out_denom, out_dist, out_pvalue, out_pass);
 }
@@ -1343,21 +1337,20 @@ int fpm_refset_create(fpm_ctx *ctx, const void *ref, const uint32_t *ref_len,
     if (int rc = set_device(ctx)) return rc;
     if (hash_bytes != 4 && hash_bytes != 8) return fail(FPM_EINVAL, "hash_bytes must be 4 or 8");
     // device copies of the rows, which the set then owns
-    DevBuf own[3];
-    const size_t mb = (size_t)n_ref * ref_stride * hash_bytes;
-    HIP_TRY(hipMalloc(&own[0].p, std::max<size_t>(16, mb)));
-    HIP_TRY(hipMalloc(&own[1].p, std::max<size_t>(16, (size_t)n_ref * 4)));
-    HIP_TRY(hipMalloc(&own[2].p, std::max<size_t>(16, (size_t)n_ref * 8)));
-    if ((size_t)n_ref * ref_stride) HIP_TRY(copy_in(ctx, own[0].p, ref, mb));
-    if (n_ref) {
-        HIP_TRY(copy_in(ctx, own[1].p, ref_len, (size_t)n_ref * 4));
-        if (ref_length) HIP_TRY(copy_in(ctx, own[2].p, ref_length, (size_t)n_ref * 8));
-    }
-    if (int rc = fpm_refset_create_dev(ctx, own[0].p, (const uint32_t *)own[1].p,
-                                       (const uint64_t *)own[2].p, ref_stride, n_ref, hash_bytes,
+    DevBufs own;
+    void *rows;
+    uint32_t *len;
+    uint64_t *length;
+    HIP_TRY(own.get(&rows, std::max<size_t>(16, (size_t)n_ref * ref_stride * hash_bytes)));
+    HIP_TRY(own.get(&len, std::max<size_t>(16, (size_t)n_ref * 4)));
+    HIP_TRY(own.get(&length, std::max<size_t>(16, (size_t)n_ref * 8)));
+    HIP_TRY(copy_in(ctx, rows, ref, (size_t)n_ref * ref_stride * hash_bytes));
+    HIP_TRY(copy_in(ctx, len, ref_len, (size_t)n_ref * 4));
+    if (ref_length) HIP_TRY(copy_in(ctx, length, ref_length, (size_t)n_ref * 8));
+    if (int rc = fpm_refset_create_dev(ctx, rows, len, length, ref_stride, n_ref, hash_bytes,
                                        sketch_size, out))
         return rc;
-    for (int i = 0; i < 3; i++) std::swap((*out)->own[i], own[i].p);
+    (*out)->mem.absorb(std::move(own));
     return FPM_OK;
 }
 
@@ -1531,13 +1524,6 @@ void fpm_refset_free(fpm_refset *rs)
 {
     if (!rs) return;
     if (rs->ctx) (void)hipSetDevice(rs->ctx->device);
-    for (auto &sl : rs->slot)
-        if (sl.p) (void)hipFree(sl.p);
-    for (auto &sl : rs->qslot)
-        if (sl.p) (void)hipFree(sl.p);
-    for (void *o : rs->own)
-        if (o) (void)hipFree(o);
-    if (rs->kmax) (void)hipFree(rs->kmax);
     delete rs;
 }
 

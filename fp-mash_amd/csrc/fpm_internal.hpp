@@ -1,7 +1,9 @@
 // fpm_internal.hpp — what the files implementing the C ABI of include/fpmash.h share:
-// the context, its pool / ring / copy helpers, the device scratch slots and the counter block.
-// fpm_ctx.cpp defines the helpers; fpm_sketch_api.cpp, fpm_text_api.cpp, fpm_dist_api.cpp,
-// fpm_contain_api.cpp, fpm_screen_api.cpp, fpm_kfinger_api.cpp and fpm_comm.cpp use them.  Nothing declared here is exported from the library.
+// the context, its pool / ring / copy helpers, the device scratch slots, the counter block and
+// DevBufs, the owner of device buffers.  fpm_ctx.cpp and fpm_devmem.cpp define the helpers;
+// fpm_sketch_api.cpp, fpm_text_api.cpp, fpm_dist_api.cpp, fpm_contain_api.cpp,
+// fpm_screen_api.cpp, fpm_kfinger_api.cpp and fpm_comm.cpp use them.  Nothing declared here is
+// exported from the library.
 #pragma once
 
 #include "fpm_kernels.hpp"
@@ -166,7 +168,15 @@ struct fpm_ctx {
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[FPM_K_COUNT];
     // grow-only device scratch, one buffer per named slot (no allocation in steady state)
-    struct Slot { void *p = nullptr; size_t bytes = 0; };
+    // (a slot frees its buffer when destroyed: set the device before deleting its holder)
+    struct Slot {
+        void *p = nullptr;
+        size_t bytes = 0;
+        Slot() = default;
+        Slot(const Slot &) = delete;
+        Slot &operator=(const Slot &) = delete;
+        ~Slot();
+    };
     Slot scratch[kSlotCount];
     unsigned long long *host_counters = nullptr;   // pinned + mapped, for the events read-back
     unsigned long long *dev_counters = nullptr;    // its device-side address
@@ -238,7 +248,8 @@ struct fpm_ctx {
     std::mutex pool_mu;
 };
 
-// RAII-free event bracket: records start before and stop after a launch.
+// Event bracket: records start before and stop after a launch; done() hands the pair to the
+// context, and a bracket left before done() (a launch failed) destroys it.
 struct TimedLaunch {
     fpm_ctx *ctx; int kid; hipStream_t st; hipEvent_t a = nullptr, b = nullptr;
     TimedLaunch(fpm_ctx *c, int k, hipStream_t s) : ctx(c), kid(k), st(s)
@@ -254,8 +265,16 @@ struct TimedLaunch {
         if (ctx->timing) {
             (void)hipEventRecord(b, st);
             ctx->ev[kid].push_back({a, b});
+            a = b = nullptr;
         }
     }
+    ~TimedLaunch()
+    {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+    TimedLaunch(const TimedLaunch &) = delete;
+    TimedLaunch &operator=(const TimedLaunch &) = delete;
 };
 
 #pragma GCC visibility push(hidden)
@@ -266,7 +285,7 @@ inline hipStream_t pick_stream(fpm_ctx *ctx, void *stream)
     return stream ? (hipStream_t)stream : ctx->stream;
 }
 
-// device buffers of released jobs, reused by the next (fpm_ctx::pool)
+// device buffers of released jobs, reused by the next (fpm_ctx::pool; fpm_devmem.cpp)
 hipError_t pool_alloc(fpm_ctx *ctx, void **p, size_t bytes);
 void pool_free(fpm_ctx *ctx, void *p, size_t bytes);
 
@@ -282,6 +301,54 @@ hipError_t ensure_aux(fpm_ctx *ctx);
 // grow-only device buffers: a slot of at least `bytes`; scratch() is the context's named slot
 hipError_t grow_slot(fpm_ctx::Slot &s, size_t bytes, void **out);
 hipError_t scratch(fpm_ctx *ctx, ScratchSlot id, size_t bytes, void **out);
+
+// The owner of device buffers: everything it still holds is freed with it, pooled buffers back
+// into its context's pool (the caller has synchronised the streams that used them), the others
+// with hipFree.  Handles keep their typed d_* fields as views and one DevBufs beside them;
+// staging calls keep a local one.  A zero-byte request allocates 16 bytes.
+class DevBufs {
+  public:
+    struct Buf { void *p; size_t bytes; bool pooled; };
+    fpm_ctx *ctx = nullptr;            // get_pooled's pool
+    DevBufs() = default;
+    explicit DevBufs(fpm_ctx *c) : ctx(c) {}
+    DevBufs(DevBufs &&o) noexcept : ctx(o.ctx), held_(std::move(o.held_)) { o.held_.clear(); }
+    DevBufs(const DevBufs &) = delete;
+    DevBufs &operator=(const DevBufs &) = delete;
+    ~DevBufs();
+    // on failure *out is null and nothing is recorded
+    template <typename T> hipError_t get(T **out, size_t bytes) { return typed(out, bytes, false); }
+    template <typename T> hipError_t get_pooled(T **out, size_t bytes) { return typed(out, bytes, true); }
+    // get, then the caller's host memory copied in (none given: allocated only)
+    template <typename T> hipError_t upload(fpm_ctx *c, T **out, const void *host, size_t bytes)
+    {
+        hipError_t e = get(out, bytes);
+        if (e == hipSuccess && host && bytes) e = copy_in(c, (void *)*out, host, bytes);
+        return e;
+    }
+    // takes over a hipMalloc'd buffer (the packed records of a parse)
+    void adopt(void *p) { if (p) held_.push_back({p, 0, false}); }
+    // gives `p` up to the caller; null when `p` is not held here (nothing changes then)
+    template <typename T> T *release(T *p) { return remove(p, false) ? p : nullptr; }
+    // frees `p` now
+    template <typename T> void drop(T *&p) { remove(p, true); p = nullptr; }
+    // takes over all of `o`'s buffers, in order (allocate all or none: into a local owner first)
+    void absorb(DevBufs &&o);
+    const std::vector<Buf> &held() const { return held_; }
+
+  private:
+    template <typename T> hipError_t typed(T **out, size_t bytes, bool pooled)
+    {
+        void *q = nullptr;
+        const hipError_t e = take(&q, bytes, pooled);
+        *out = static_cast<T *>(q);
+        return e;
+    }
+    hipError_t take(void **out, size_t bytes, bool pooled);
+    void free_buf(const Buf &b);
+    bool remove(const void *p, bool free_it);
+    std::vector<Buf> held_;
+};
 
 // device counters -> the context's host-mapped block (fpm_ctx.cpp)
 int publish_counters(fpm_ctx *ctx, const unsigned long long *d_src, uint32_t n, hipStream_t st,
@@ -311,7 +378,7 @@ struct StageRecords {
     std::vector<uint32_t> group;        // per record
     uint32_t n_groups = 0;
     const char *host_seq = nullptr;     // host path: record r is host_seq[pos..pos+len)
-    uint8_t *d_seq = nullptr;           // device path: packed buffer (ownership moves to the job)
+    uint8_t *d_seq = nullptr;           // device path: packed buffer (the job adopts it)
     uint64_t d_seq_bytes = 0;
     bool borrow = false;                // device path: d_seq stays with its owner (reads mode's
                                         // wide jobs over the staged job's buffer)

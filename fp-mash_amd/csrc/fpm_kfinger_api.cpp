@@ -15,6 +15,7 @@ struct fpm_kfinger {
     std::vector<uint64_t> rec_first_line;    // n_in + 1
     std::vector<uint32_t> src;               // input record of each kept record
     uint8_t *d_seq = nullptr;                // the records' bytes (hipMalloc: own or adopted)
+                                             // every other buffer below is pooled
     uint64_t *d_rec_pos = nullptr;           // per kept record
     uint32_t *d_rec_len = nullptr;
     KfDesc *d_desc = nullptr;
@@ -30,15 +31,7 @@ struct fpm_kfinger {
     uint64_t *d_id_off = nullptr;
     uint32_t *d_id_len = nullptr;
     uint64_t text_total = 0;
-    std::vector<std::pair<void *, size_t>> bufs;   // every pooled buffer above, with its size
-    template <typename T> hipError_t alloc(T **p, size_t bytes)
-    {
-        void *q = nullptr;
-        bytes = bytes ? bytes : 16;
-        const hipError_t e = pool_alloc(ctx, &q, bytes);
-        if (e == hipSuccess) { bufs.push_back({q, bytes}); *p = static_cast<T *>(q); }
-        return e;
-    }
+    DevBufs mem;                             // owns every buffer above
 };
 
 static void kfinger_release(fpm_kfinger *j)
@@ -48,8 +41,6 @@ static void kfinger_release(fpm_kfinger *j)
     // the job's kernels are done before its buffers are handed out again
     (void)hipStreamSynchronize(j->stream ? j->stream : j->ctx->stream);
     (void)hipStreamSynchronize(j->ctx->stream);
-    for (auto &b : j->bufs) pool_free(j->ctx, b.first, b.second);
-    if (j->d_seq) (void)hipFree(j->d_seq);
 }
 
 namespace {
@@ -59,7 +50,7 @@ using JobPtr = std::unique_ptr<fpm_kfinger, void (*)(fpm_kfinger *)>;
 JobPtr new_job(fpm_ctx *ctx)
 {
     JobPtr j(new fpm_kfinger, [](fpm_kfinger *p) { kfinger_release(p); delete p; });
-    j->ctx = ctx;
+    j->ctx = j->mem.ctx = ctx;
     return j;
 }
 
@@ -113,18 +104,18 @@ int plan(fpm_kfinger *j, const std::vector<uint64_t> &pos, const std::vector<uin
     j->n_lines = line;
     if (descs.size() > 0x7FFFFFFFull) return fail(FPM_EINVAL, "kfinger: too many lines for one job");
     j->n_desc = (uint32_t)descs.size();
-    HIP_TRY(j->alloc(&j->d_rec_pos, kpos.size() * 8));
-    HIP_TRY(j->alloc(&j->d_rec_len, klen.size() * 4));
-    HIP_TRY(j->alloc(&j->d_desc, descs.size() * sizeof(KfDesc)));
+    HIP_TRY(j->mem.get_pooled(&j->d_rec_pos, kpos.size() * 8));
+    HIP_TRY(j->mem.get_pooled(&j->d_rec_len, klen.size() * 4));
+    HIP_TRY(j->mem.get_pooled(&j->d_desc, descs.size() * sizeof(KfDesc)));
     if (!kpos.empty()) {
         HIP_TRY(h2d_staged(ctx, j->d_rec_pos, kpos.data(), kpos.size() * 8));
         HIP_TRY(h2d_staged(ctx, j->d_rec_len, klen.data(), klen.size() * 4));
     }
     if (!descs.empty()) HIP_TRY(h2d_staged(ctx, j->d_desc, descs.data(), descs.size() * sizeof(KfDesc)));
-    HIP_TRY(j->alloc(&j->d_hash, line * 8));
-    HIP_TRY(j->alloc(&j->d_n_vals, line * 4));
-    HIP_TRY(j->alloc(&j->d_body, line * 4));
-    HIP_TRY(j->alloc(&j->d_totals, 16));
+    HIP_TRY(j->mem.get_pooled(&j->d_hash, line * 8));
+    HIP_TRY(j->mem.get_pooled(&j->d_n_vals, line * 4));
+    HIP_TRY(j->mem.get_pooled(&j->d_body, line * 4));
+    HIP_TRY(j->mem.get_pooled(&j->d_totals, 16));
     return FPM_OK;
 }
 
@@ -134,8 +125,8 @@ bool window_ok(uint32_t w) { return w >= 1 && w <= kKfMaxWindow; }
 int scan_sizes(fpm_kfinger *j, hipStream_t st)
 {
     if (!j->d_off) {
-        HIP_TRY(j->alloc(&j->d_off, j->n_lines * 4));
-        HIP_TRY(j->alloc(&j->d_scan, scan_scratch_words(j->n_lines ? j->n_lines : 1) * 4));
+        HIP_TRY(j->mem.get_pooled(&j->d_off, j->n_lines * 4));
+        HIP_TRY(j->mem.get_pooled(&j->d_scan, scan_scratch_words(j->n_lines ? j->n_lines : 1) * 4));
     }
     HIP_TRY(launch_exscan(j->d_size, j->d_off, nullptr, j->n_lines, j->d_scan, nullptr, st));
     return FPM_OK;
@@ -162,7 +153,7 @@ int fpm_kfinger_stage(fpm_ctx *ctx, const char *seq, const uint64_t *rec_off, ui
         len[r] = rec_off[r + 1] - rec_off[r];
     }
     const uint64_t bytes = n_rec ? rec_off[n_rec] - rec_off[0] : 0;
-    HIP_TRY(hipMalloc((void **)&j->d_seq, bytes ? bytes : 16));
+    HIP_TRY(j->mem.get(&j->d_seq, bytes));
     if (bytes) HIP_TRY(h2d_staged(ctx, j->d_seq, seq + rec_off[0], bytes));
     if (int rc = plan(j.get(), pos, len, nullptr, window, max_lines)) return rc;
     *n_lines = j->n_lines;
@@ -184,7 +175,7 @@ int fpm_kfinger_stage_seq(fpm_ctx *ctx, fpm_seqtext *seq, const uint8_t *take, u
     std::vector<uint64_t> pos, len;
     if (int rc = seqtext_records(ctx, seq, &n, &pos, &len, &d_packed)) return rc;
     JobPtr j = new_job(ctx);
-    j->d_seq = d_packed;   // the job owns the packed records now
+    j->mem.adopt(j->d_seq = d_packed);   // the job owns the packed records now
     if (int rc = plan(j.get(), pos, len, take, window, max_lines)) return rc;
     *n_lines = j->n_lines;
     *job = j.release();
@@ -257,7 +248,7 @@ int fpm_kfinger_values(fpm_kfinger *j, uint64_t *val_off, uint16_t *vals, uint64
         return FPM_OK;
     }
     uint16_t *d_vals = nullptr;
-    HIP_TRY(j->alloc(&d_vals, tot * 2));
+    HIP_TRY(j->mem.get_pooled(&d_vals, tot * 2));
     {
         TimedLaunch tl(ctx, FPM_K_KFINGER_OUT, st);
         // the sizes are the value counts themselves
@@ -309,13 +300,13 @@ int fpm_kfinger_text(fpm_kfinger *j, const char *ids, const uint64_t *id_off, ch
     // their upload and the size pass are kept
     if (!j->text_sized || kid != j->text_ids || klen != j->text_id_len) {
         j->text_sized = false;
-        HIP_TRY(j->alloc(&j->d_ids, kid.size()));
-        HIP_TRY(j->alloc(&j->d_id_off, nk * 8));
-        HIP_TRY(j->alloc(&j->d_id_len, nk * 4));
+        HIP_TRY(j->mem.get_pooled(&j->d_ids, kid.size()));
+        HIP_TRY(j->mem.get_pooled(&j->d_id_off, nk * 8));
+        HIP_TRY(j->mem.get_pooled(&j->d_id_len, nk * 4));
         if (!kid.empty()) HIP_TRY(h2d_staged(ctx, j->d_ids, kid.data(), kid.size()));
         HIP_TRY(h2d_staged(ctx, j->d_id_off, koff.data(), nk * 8));
         HIP_TRY(h2d_staged(ctx, j->d_id_len, klen.data(), nk * 4));
-        if (!j->d_size) HIP_TRY(j->alloc(&j->d_size, n * 4));
+        if (!j->d_size) HIP_TRY(j->mem.get_pooled(&j->d_size, n * 4));
         HIP_TRY(hipMemsetAsync(j->d_totals + 1, 0, 8, st));
         {
             TimedLaunch tl(ctx, FPM_K_KFINGER_OUT, st);
@@ -338,7 +329,7 @@ int fpm_kfinger_text(fpm_kfinger *j, const char *ids, const uint64_t *id_off, ch
     if (!out) return FPM_OK;                              // sized by this call
     if (cap < tot) return fail(FPM_EINVAL, "kfinger_text: buffer too small");
     uint8_t *d_out = nullptr;
-    HIP_TRY(j->alloc(&d_out, tot));
+    HIP_TRY(j->mem.get_pooled(&d_out, tot));
     TimedLaunch tl(ctx, FPM_K_KFINGER_OUT, st);
     if (int rc = scan_sizes(j, st)) return rc;
     HIP_TRY(launch_kf_text(j->d_seq, j->d_rec_pos, j->d_rec_len, j->d_desc, j->n_desc, j->window,

@@ -19,26 +19,15 @@ struct fpm_screen {
     // pair[2] (pcnt[2]) their merge
     uint64_t *d_pair = nullptr;
     uint32_t *d_pcnt = nullptr;
+    DevBufs mem;                          // owns the table's arrays and every d_* above
 };
 
 namespace {
-
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t get(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-    template <typename T> T *as() { return (T *)p; }
-};
 
 void screen_release(fpm_screen *sc)
 {
     if (!sc) return;
     (void)hipSetDevice(sc->ctx->device);
-    for (void *p : {(void *)sc->tab.U, (void *)sc->tab.dir, (void *)sc->tab.count, (void *)sc->d_len,
-                    (void *)sc->d_slot, (void *)sc->d_ustart, (void *)sc->d_post,
-                    (void *)sc->d_owner, (void *)sc->d_shared, (void *)sc->d_median,
-                    (void *)sc->d_pair, (void *)sc->d_pcnt})
-        (void)hipFree(p);
     delete sc;
 }
 
@@ -62,12 +51,13 @@ int screen_build(fpm_ctx *ctx, const void *d_db, const uint32_t *d_db_len, uint6
     sc->h_len.assign(n_db, 0);
     auto body = [&]() -> int {
         const size_t cells = (size_t)n_db * stride;
-        HIP_TRY(hipMalloc((void **)&sc->d_len, std::max<size_t>(n_db, 1) * 4));
-        HIP_TRY(hipMalloc((void **)&sc->d_shared, std::max<size_t>(n_db, 1) * 4));
-        HIP_TRY(hipMalloc((void **)&sc->d_median, std::max<size_t>(n_db, 1) * 4));
-        HIP_TRY(hipMalloc((void **)&sc->d_slot, std::max<size_t>(cells, 1) * 4));
-        HIP_TRY(hipMalloc((void **)&sc->d_pair, (size_t)3 * sketch_size * 8));
-        HIP_TRY(hipMalloc((void **)&sc->d_pcnt, 16));
+        DevBufs &mem = sc->mem;
+        HIP_TRY(mem.get(&sc->d_len, std::max<size_t>(n_db, 1) * 4));
+        HIP_TRY(mem.get(&sc->d_shared, std::max<size_t>(n_db, 1) * 4));
+        HIP_TRY(mem.get(&sc->d_median, std::max<size_t>(n_db, 1) * 4));
+        HIP_TRY(mem.get(&sc->d_slot, std::max<size_t>(cells, 1) * 4));
+        HIP_TRY(mem.get(&sc->d_pair, (size_t)3 * sketch_size * 8));
+        HIP_TRY(mem.get(&sc->d_pcnt, 16));
         HIP_TRY(hipMemsetAsync(sc->d_pcnt, 0, 16, st));
         uint64_t E = 0;
         if (n_db) {
@@ -95,32 +85,33 @@ int screen_build(fpm_ctx *ctx, const void *d_db, const uint32_t *d_db_len, uint6
         sc->E = (uint32_t)E;
         uint32_t nU = 0;
         unsigned long long kmax = 0;
-        DevBuf okey, ocell, head, hx, scan_s;
+        DevBufs tmp;   // the build's scratch: freed on return
+        uint64_t *okey = nullptr;
+        uint32_t *ocell = nullptr, *head = nullptr, *hx = nullptr, *scan_s = nullptr;
         if (E) {
             // ~2 cells per sort bucket
             uint32_t sbits = 1;
             while (sbits < 22 && (2ull << sbits) < E) sbits++;
             const uint64_t nb = 1ull << sbits;
-            DevBuf km, hist, start, skey;
-            HIP_TRY(km.get(16));
-            HIP_TRY(hist.get(nb * 4));
-            HIP_TRY(start.get(nb * 4));
-            HIP_TRY(scan_s.get(scan_scratch_words(std::max<uint64_t>(nb, E)) * 4));
-            HIP_TRY(skey.get(E * 8));
-            HIP_TRY(okey.get(E * 8));
-            HIP_TRY(ocell.get(E * 4));
-            HIP_TRY(head.get(E * 4));
-            HIP_TRY(hx.get(E * 4));
-            HIP_TRY(hipMalloc((void **)&sc->d_post, E * 4));   // the scatter's cells, then the postings
+            DevBufs sort_tmp;   // the sort's own scratch: freed at the end of this block
+            unsigned long long *km;
+            uint32_t *hist, *start;
+            uint64_t *skey;
+            HIP_TRY(sort_tmp.get(&km, 16));
+            HIP_TRY(sort_tmp.get(&hist, nb * 4));
+            HIP_TRY(sort_tmp.get(&start, nb * 4));
+            HIP_TRY(tmp.get(&scan_s, scan_scratch_words(std::max<uint64_t>(nb, E)) * 4));
+            HIP_TRY(sort_tmp.get(&skey, E * 8));
+            HIP_TRY(tmp.get(&okey, E * 8));
+            HIP_TRY(tmp.get(&ocell, E * 4));
+            HIP_TRY(tmp.get(&head, E * 4));
+            HIP_TRY(tmp.get(&hx, E * 4));
+            HIP_TRY(mem.get(&sc->d_post, E * 4));   // the scatter's cells, then the postings
             HIP_TRY(launch_screen_sort(d_db, d_db_len, stride, n_db, hash_bytes, (uint32_t)E, sbits,
-                                       km.as<unsigned long long>(), hist.as<uint32_t>(),
-                                       start.as<uint32_t>(), scan_s.as<uint32_t>(),
-                                       skey.as<uint64_t>(), sc->d_post, okey.as<uint64_t>(),
-                                       ocell.as<uint32_t>(), st));
-            uint32_t *d_n = km.as<uint32_t>() + 2;
-            HIP_TRY(launch_screen_heads(okey.as<uint64_t>(), (uint32_t)E, head.as<uint32_t>(),
-                                        hx.as<uint32_t>(), scan_s.as<uint32_t>(), d_n, st));
-            HIP_TRY(hipMemcpyAsync(&kmax, km.p, 8, hipMemcpyDeviceToHost, st));
+                                       km, hist, start, scan_s, skey, sc->d_post, okey, ocell, st));
+            uint32_t *d_n = (uint32_t *)km + 2;
+            HIP_TRY(launch_screen_heads(okey, (uint32_t)E, head, hx, scan_s, d_n, st));
+            HIP_TRY(hipMemcpyAsync(&kmax, km, 8, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(&nU, d_n, 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
         }
@@ -131,16 +122,15 @@ int screen_build(fpm_ctx *ctx, const void *d_db, const uint32_t *d_db_len, uint6
         sc->tab.dbits = dbits;
         sc->tab.umax = kmax;
         sc->tab.shift = kmax ? (uint32_t)__builtin_clzll(kmax) : 63u;
-        HIP_TRY(hipMalloc((void **)&sc->tab.U, std::max<size_t>(nU, 1) * 8));
-        HIP_TRY(hipMalloc((void **)&sc->tab.count, std::max<size_t>(nU, 1) * 4));
-        HIP_TRY(hipMalloc((void **)&sc->d_owner, std::max<size_t>(nU, 1) * 4));
-        HIP_TRY(hipMalloc((void **)&sc->d_ustart, ((size_t)nU + 1) * 4));
-        HIP_TRY(hipMalloc((void **)&sc->tab.dir, ((size_t)(1u << dbits) + 1) * 4));
+        HIP_TRY(mem.get(&sc->tab.U, std::max<size_t>(nU, 1) * 8));
+        HIP_TRY(mem.get(&sc->tab.count, std::max<size_t>(nU, 1) * 4));
+        HIP_TRY(mem.get(&sc->d_owner, std::max<size_t>(nU, 1) * 4));
+        HIP_TRY(mem.get(&sc->d_ustart, ((size_t)nU + 1) * 4));
+        HIP_TRY(mem.get(&sc->tab.dir, ((size_t)(1u << dbits) + 1) * 4));
         HIP_TRY(hipMemsetAsync(sc->tab.count, 0, std::max<size_t>(nU, 1) * 4, st));
         HIP_TRY(hipMemsetAsync(sc->d_ustart, 0, ((size_t)nU + 1) * 4, st));
         HIP_TRY(hipMemsetAsync((void *)sc->tab.dir, 0, ((size_t)(1u << dbits) + 1) * 4, st));
-        HIP_TRY(launch_screen_compact(okey.as<uint64_t>(), ocell.as<uint32_t>(), head.as<uint32_t>(),
-                                      hx.as<uint32_t>(), (uint32_t)E, stride, nU, dbits,
+        HIP_TRY(launch_screen_compact(okey, ocell, head, hx, (uint32_t)E, stride, nU, dbits,
                                       sc->tab.shift, (uint64_t *)sc->tab.U, sc->d_ustart,
                                       sc->d_slot, sc->d_post, (uint32_t *)sc->tab.dir, st));
         HIP_TRY(hipStreamSynchronize(st));   // the build's buffers are released on return
@@ -195,14 +185,15 @@ int fpm_screen_create(fpm_ctx *ctx, const void *db, const uint32_t *db_len, uint
     if (int rc = set_device(ctx)) return rc;
     if (hash_bytes != 4 && hash_bytes != 8) return fail(FPM_EINVAL, "hash_bytes must be 4 or 8");
     if (n_db && (!db || !db_len)) return fail(FPM_EINVAL, "fpm_screen_create: null buffer");
-    DevBuf rows, len;
-    const size_t bytes = (size_t)n_db * stride * hash_bytes;
-    hipError_t e = rows.get(bytes);
-    if (e == hipSuccess) e = len.get((size_t)n_db * 4);
-    if (e == hipSuccess && bytes) e = copy_in(ctx, rows.p, db, bytes);
-    if (e == hipSuccess && n_db) e = copy_in(ctx, len.p, db_len, (size_t)n_db * 4);
+    DevBufs mem;
+    void *rows;
+    uint32_t *len;
+    hipError_t e = mem.get(&rows, (size_t)n_db * stride * hash_bytes);
+    if (e == hipSuccess) e = mem.get(&len, (size_t)n_db * 4);
+    if (e == hipSuccess) e = copy_in(ctx, rows, db, (size_t)n_db * stride * hash_bytes);
+    if (e == hipSuccess) e = copy_in(ctx, len, db_len, (size_t)n_db * 4);
     if (e != hipSuccess) return fail(FPM_ENOMEM, std::string("screen staging: ") + hipGetErrorString(e));
-    return screen_build(ctx, rows.p, len.as<uint32_t>(), stride, n_db, hash_bytes, sketch_size, out);
+    return screen_build(ctx, rows, len, stride, n_db, hash_bytes, sketch_size, out);
 }
 
 void fpm_screen_free(fpm_screen *sc) { screen_release(sc); }
@@ -297,14 +288,16 @@ int fpm_screen_rows_winner(fpm_screen *sc, const double *scores, const uint64_t 
     if (int rc = set_device(ctx)) return rc;
     HIP_TRY(hipDeviceSynchronize());
     if (!sc->n_db) return screen_rows(sc, nullptr, out_shared, out_median);
-    DevBuf ds, dl;
-    hipError_t e = ds.get((size_t)sc->n_db * 8);
-    if (e == hipSuccess) e = dl.get((size_t)sc->n_db * 8);
-    if (e == hipSuccess) e = copy_in(ctx, ds.p, scores, (size_t)sc->n_db * 8);
-    if (e == hipSuccess) e = copy_in(ctx, dl.p, lengths, (size_t)sc->n_db * 8);
+    DevBufs mem;
+    double *ds;
+    uint64_t *dl;
+    hipError_t e = mem.get(&ds, (size_t)sc->n_db * 8);
+    if (e == hipSuccess) e = mem.get(&dl, (size_t)sc->n_db * 8);
+    if (e == hipSuccess) e = copy_in(ctx, ds, scores, (size_t)sc->n_db * 8);
+    if (e == hipSuccess) e = copy_in(ctx, dl, lengths, (size_t)sc->n_db * 8);
     if (e != hipSuccess) return fail(FPM_ENOMEM, std::string("screen -w staging: ") + hipGetErrorString(e));
-    HIP_TRY(launch_screen_winner(sc->tab.count, sc->d_ustart, sc->d_post, sc->tab.n, ds.as<double>(),
-                                 dl.as<uint64_t>(), sc->d_owner, ctx->stream));
+    HIP_TRY(launch_screen_winner(sc->tab.count, sc->d_ustart, sc->d_post, sc->tab.n, ds, dl,
+                                 sc->d_owner, ctx->stream));
     return screen_rows(sc, sc->d_owner, out_shared, out_median);
 }
 
@@ -318,19 +311,20 @@ int fpm_screen_pvalues(fpm_screen *sc, const uint32_t *shared, double kmer_space
     if (!sc->n_db) return FPM_OK;
     double r = (double)set_size / kmer_space;
     r = std::max(0.0, std::min(1.0, r));
-    DevBuf dsh, dp;
-    hipError_t e = dsh.get((size_t)sc->n_db * 4);
-    if (e == hipSuccess) e = dp.get((size_t)sc->n_db * 8);
-    if (e == hipSuccess) e = copy_in(ctx, dsh.p, shared, (size_t)sc->n_db * 4);
+    DevBufs mem;
+    uint32_t *dsh;
+    double *dp;
+    hipError_t e = mem.get(&dsh, (size_t)sc->n_db * 4);
+    if (e == hipSuccess) e = mem.get(&dp, (size_t)sc->n_db * 8);
+    if (e == hipSuccess) e = copy_in(ctx, dsh, shared, (size_t)sc->n_db * 4);
     if (e != hipSuccess) return fail(FPM_ENOMEM, std::string("screen p-value staging: ") + hipGetErrorString(e));
     {
         TimedLaunch tl(ctx, FPM_K_FINALIZE, ctx->stream);
-        HIP_TRY(launch_screen_pvalues(dsh.as<uint32_t>(), sc->d_len, sc->n_db, r, dp.as<double>(),
-                                      ctx->stream));
+        HIP_TRY(launch_screen_pvalues(dsh, sc->d_len, sc->n_db, r, dp, ctx->stream));
         tl.done();
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(copy_out(ctx, out_p, dp.p, (size_t)sc->n_db * 8));
+    HIP_TRY(copy_out(ctx, out_p, dp, (size_t)sc->n_db * 8));
     return FPM_OK;
 }
 
@@ -378,31 +372,28 @@ int fpm_screen_tax(fpm_screen *sc, const uint32_t *parent, uint32_t n_nodes, uin
     hipStream_t st = ctx->stream;
     const uint32_t nU = sc->tab.n;
     const size_t nb = (size_t)n_nodes * 4;
-    DevBuf dpar, ddep, dref, dlca, dcnt, dtot;
-    hipError_t e = dpar.get(nb);
-    if (e == hipSuccess) e = ddep.get(nb);
-    if (e == hipSuccess) e = dref.get((size_t)sc->n_db * 4);
-    if (e == hipSuccess) e = dlca.get((size_t)nU * 4);
-    if (e == hipSuccess) e = dcnt.get(4 * nb);     // tax_hashes, tax_count, clade_hashes, clade_count
-    if (e == hipSuccess) e = dtot.get(16);         // totals[0], the wave's entries
-    if (e == hipSuccess && n_nodes) e = copy_in(ctx, dpar.p, parent, nb);
-    if (e == hipSuccess && n_nodes) e = copy_in(ctx, ddep.p, depth.data(), nb);
-    if (e == hipSuccess && sc->n_db) e = copy_in(ctx, dref.p, ref_node, (size_t)sc->n_db * 4);
+    DevBufs mem;
+    uint32_t *dpar, *ddep, *dref, *dlca, *c0;
+    unsigned long long *d_tot;
+    hipError_t e = mem.upload(ctx, &dpar, parent, nb);
+    if (e == hipSuccess) e = mem.upload(ctx, &ddep, depth.data(), nb);
+    if (e == hipSuccess) e = mem.upload(ctx, &dref, ref_node, (size_t)sc->n_db * 4);
+    if (e == hipSuccess) e = mem.get(&dlca, (size_t)nU * 4);
+    if (e == hipSuccess) e = mem.get(&c0, 4 * nb);     // tax_hashes, tax_count, clade_hashes, clade_count
+    if (e == hipSuccess) e = mem.get(&d_tot, 16);      // totals[0], the wave's entries
     if (e != hipSuccess) return fail(FPM_ENOMEM, std::string("taxscreen staging: ") + hipGetErrorString(e));
-    HIP_TRY(hipMemsetAsync(dcnt.p, 0, std::max<size_t>(4 * nb, 16), st));
-    HIP_TRY(hipMemsetAsync(dtot.p, 0, 16, st));
+    HIP_TRY(hipMemsetAsync(c0, 0, std::max<size_t>(4 * nb, 16), st));
+    HIP_TRY(hipMemsetAsync(d_tot, 0, 16, st));
     TaxTree t;
-    t.parent = dpar.as<uint32_t>();
-    t.depth = ddep.as<uint32_t>();
+    t.parent = dpar;
+    t.depth = ddep;
     t.n_nodes = n_nodes;
     t.top = top;
-    uint32_t *c0 = dcnt.as<uint32_t>(), *c1 = c0 + n_nodes, *c2 = c1 + n_nodes, *c3 = c2 + n_nodes;
-    unsigned long long *d_tot = dtot.as<unsigned long long>();
+    uint32_t *c1 = c0 + n_nodes, *c2 = c1 + n_nodes, *c3 = c2 + n_nodes;
     ctx->last_tax_kernel = FPM_TK_NONE;
     {
         TimedLaunch tl(ctx, FPM_K_COMPARE, st);
-        HIP_TRY(launch_tax_lca(sc->tab.count, sc->d_ustart, sc->d_post, nU, dref.as<uint32_t>(), t,
-                               dlca.as<uint32_t>(), c0, c1, d_tot, (uint32_t *)(d_tot + 1), st));
+        HIP_TRY(launch_tax_lca(sc->tab.count, sc->d_ustart, sc->d_post, nU, dref, t, dlca, c0, c1, d_tot, (uint32_t *)(d_tot + 1), st));
         tl.done();
     }
     {
@@ -416,7 +407,7 @@ int fpm_screen_tax(fpm_screen *sc, const uint32_t *parent, uint32_t n_nodes, uin
     if (nU) ctx->last_tax_kernel = (uint32_t)host[1] ? FPM_TK_WAVE : FPM_TK_THREAD;
     out_totals[0] = host[0];
     out_totals[1] = nU;
-    if (out_lca && nU) HIP_TRY(copy_out(ctx, out_lca, dlca.p, (size_t)nU * 4));
+    if (out_lca && nU) HIP_TRY(copy_out(ctx, out_lca, dlca, (size_t)nU * 4));
     uint32_t *outs[4] = {out_tax_hashes, out_tax_count, out_clade_hashes, out_clade_count};
     const uint32_t *srcs[4] = {c0, c1, c2, c3};
     for (int i = 0; i < 4; i++)

@@ -120,37 +120,23 @@ struct fpm_sketch_job {
     uint64_t *d_ttop = nullptr;
     // reads mode (fpm_sketch_job_set_min_copies, fpm_sketch_reads_run): the parameters and
     // records as staged (pos = offsets in d_seq), from which the widening rounds stage their
-    // wide jobs over this job's d_seq (borrowed_seq: such a job does not free it); the
+    // wide jobs over this job's d_seq (borrowed: such a job never adopts it); the
     // filtered rows, counts and T, allocated on first use
     fpm_sketch_params params{};
     StageRecords recs;
-    bool borrowed_seq = false;
     uint32_t min_copies = 1;
     uint64_t *d_rrows = nullptr, *d_rttop = nullptr;
     uint32_t *d_rcount = nullptr, *d_rmult = nullptr, *d_rdone = nullptr;
     std::vector<uint32_t> h_rdone;          // per group: the round that completed it
     int32_t reads_rounds = -1;              // rounds of the last reads run (-1: none yet)
     int32_t reads_sampled = -1;             // long groups its last round's wide job sampled
+    DevBufs mem;                            // owns every d_* buffer above but a borrowed d_seq
 };
 
 static void job_release(fpm_sketch_job *j)
 {
     if (!j) return;
     (void)hipSetDevice(j->ctx->device);
-    if (j->borrowed_seq) j->d_seq = nullptr;
-    for (void *p : {(void *)j->d_rrows, (void *)j->d_rttop, (void *)j->d_rcount,
-                    (void *)j->d_rmult, (void *)j->d_rdone})
-        (void)hipFree(p);
-    for (void *p : {(void *)j->d_seq, (void *)j->d_tiles, (void *)j->d_rows, (void *)j->d_count,
-                    (void *)j->d_merge, (void *)j->d_stiles, (void *)j->d_smerge, (void *)j->d_srow,
-                    (void *)j->d_thr, (void *)j->d_redo, (void *)j->d_redo_n, (void *)j->d_kt,
-                    (void *)j->d_slot_group, (void *)j->d_short, (void *)j->d_thr_safe,
-                    (void *)j->d_rtiles, (void *)j->d_rsel, (void *)j->d_sshort,
-                    (void *)j->d_sbound0, (void *)j->d_sel, (void *)j->d_sel_rows,
-                    (void *)j->d_sel_failed, (void *)j->d_fmerge, (void *)j->d_sfmerge,
-                    (void *)j->d_fb_rows, (void *)j->d_fb_count, (void *)j->d_mult,
-                    (void *)j->d_first, (void *)j->d_ttop})
-        (void)hipFree(p);
     if (j->h_sel_failed) (void)hipHostFree(j->h_sel_failed);
 }
 
@@ -545,26 +531,25 @@ int stage_core(fpm_ctx *ctx, const fpm_sketch_params *p, StageRecords &R,
     job->fround_small = fsmall;
 
     hipError_t e = hipSuccess;
-    auto alloc = [&](void **ptr, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc(ptr, bytes ? bytes : 16);
+    auto alloc = [&](auto **ptr, size_t bytes) {
+        if (e == hipSuccess) e = job->mem.get(ptr, bytes);
     };
-    if (R.host_seq) alloc((void **)&job->d_seq, packed.size() + 64);
-    else if (R.borrow) { job->d_seq = R.d_seq; job->borrowed_seq = true; }
-    else { job->d_seq = R.d_seq; R.d_seq = nullptr; }   // the parse's packed records
-    alloc((void **)&job->d_tiles, by_class.size() * sizeof(TileDesc));
-    alloc((void **)&job->d_rows, (size_t)n_core * s * sizeof(uint64_t));
-    alloc((void **)&job->d_count, (size_t)n_core * sizeof(uint32_t));
+    if (R.host_seq) alloc(&job->d_seq, packed.size() + 64);
+    else job->d_seq = R.d_seq;   // the parse's packed records, or borrowed (adopted below)
+    alloc(&job->d_tiles, by_class.size() * sizeof(TileDesc));
+    alloc(&job->d_rows, (size_t)n_core * s * sizeof(uint64_t));
+    alloc(&job->d_count, (size_t)n_core * sizeof(uint32_t));
     // groups without any k-mer keep count 0: zeroed once here (every run rewrites the count
     // of each group that has tiles: the tile kernel or the last merge of its group)
     if (e == hipSuccess) e = memset_sync(ctx, job->d_count, 0, (size_t)n_core * sizeof(uint32_t));
-    alloc((void **)&job->d_merge, mplan.size() * sizeof(MergeDesc));
-    alloc((void **)&job->d_stiles, sby_class.size() * sizeof(TileDesc));
-    alloc((void **)&job->d_smerge, splan.size() * sizeof(MergeDesc));
-    alloc((void **)&job->d_srow, srow.size() * sizeof(uint32_t));
-    alloc((void **)&job->d_thr, 2 * srow.size() * sizeof(uint64_t));   // main, then sample bounds
-    alloc((void **)&job->d_sel, sel.size() * sizeof(SelDesc));
-    alloc((void **)&job->d_sel_rows, sel_rows.size() * sizeof(uint32_t));
-    alloc((void **)&job->d_sel_failed, (sel.size() + 2) * sizeof(uint32_t));
+    alloc(&job->d_merge, mplan.size() * sizeof(MergeDesc));
+    alloc(&job->d_stiles, sby_class.size() * sizeof(TileDesc));
+    alloc(&job->d_smerge, splan.size() * sizeof(MergeDesc));
+    alloc(&job->d_srow, srow.size() * sizeof(uint32_t));
+    alloc(&job->d_thr, 2 * srow.size() * sizeof(uint64_t));   // main, then sample bounds
+    alloc(&job->d_sel, sel.size() * sizeof(SelDesc));
+    alloc(&job->d_sel_rows, sel_rows.size() * sizeof(uint32_t));
+    alloc(&job->d_sel_failed, (sel.size() + 2) * sizeof(uint32_t));
     if (e == hipSuccess && !sel.empty())
         e = hipHostMalloc((void **)&job->h_sel_failed, 3 * sizeof(uint32_t), hipHostMallocDefault);
     // tight bounds where every sampled group has a selection: kt = f s + 8 sqrt(f s) + 32 of
@@ -584,10 +569,10 @@ int stage_core(fpm_ctx *ctx, const fpm_sketch_params *p, StageRecords &R,
             kt[i] = (uint32_t)std::min<double>(s, std::ceil(fs + 8.0 * std::sqrt(fs) + 32.0));
         }
         job->tight = true;
-        alloc((void **)&job->d_kt, kt.size() * sizeof(uint32_t));
-        alloc((void **)&job->d_slot_group, slot_group.size() * sizeof(uint32_t));
-        alloc((void **)&job->d_short, (srow.size() + 1) * sizeof(uint32_t));
-        alloc((void **)&job->d_thr_safe, srow.size() * sizeof(uint64_t));
+        alloc(&job->d_kt, kt.size() * sizeof(uint32_t));
+        alloc(&job->d_slot_group, slot_group.size() * sizeof(uint32_t));
+        alloc(&job->d_short, (srow.size() + 1) * sizeof(uint32_t));
+        alloc(&job->d_thr_safe, srow.size() * sizeof(uint64_t));
         job->h_tiles = by_class;
         job->h_sel = sel;
         job->last_short = 0;
@@ -598,8 +583,8 @@ int stage_core(fpm_ctx *ctx, const fpm_sketch_params *p, StageRecords &R,
             job->h_stiles = sby_class;
             job->h_ssel_tag = ssel_tag;
             job->last_sample_short = 0;
-            alloc((void **)&job->d_sshort, (srow.size() + 1) * sizeof(uint32_t));
-            alloc((void **)&job->d_sbound0, srow.size() * sizeof(uint64_t));
+            alloc(&job->d_sshort, (srow.size() + 1) * sizeof(uint32_t));
+            alloc(&job->d_sbound0, srow.size() * sizeof(uint64_t));
         }
     }
     {
@@ -629,8 +614,8 @@ int stage_core(fpm_ctx *ctx, const fpm_sketch_params *p, StageRecords &R,
         job->thr4 = all;
         job->n4 = n4;
         if (all) {
-            alloc((void **)&job->d_redo, (size_t)n4 * sizeof(TileDesc));
-            alloc((void **)&job->d_redo_n, sizeof(uint32_t));
+            alloc(&job->d_redo, (size_t)n4 * sizeof(TileDesc));
+            alloc(&job->d_redo_n, sizeof(uint32_t));
         }
     }
     if (e != hipSuccess) {
@@ -671,6 +656,7 @@ int stage_core(fpm_ctx *ctx, const fpm_sketch_params *p, StageRecords &R,
         delete job;
         return fail(FPM_EHIP, std::string("sketch staging copy: ") + hipGetErrorString(e));
     }
+    if (!R.host_seq && !R.borrow) job->mem.adopt(R.d_seq);
     // kept for reads mode's widening rounds (moved, not copied: the callers are done with them)
     job->params = *p;
     job->recs.n_groups = n_groups;
@@ -689,8 +675,8 @@ static int fallback_descs(fpm_sketch_job *job)
     if (job->d_fmerge || job->d_sfmerge) return FPM_OK;
     const uint64_t s = job->kp.s;
     if (job->n_fb_rows) {
-        HIP_TRY(hipMalloc(&job->d_fb_rows, (size_t)job->n_fb_rows * s * sizeof(uint64_t)));
-        HIP_TRY(hipMalloc(&job->d_fb_count, (size_t)job->n_fb_rows * sizeof(uint32_t)));
+        HIP_TRY(job->mem.get(&job->d_fb_rows, (size_t)job->n_fb_rows * s * sizeof(uint64_t)));
+        HIP_TRY(job->mem.get(&job->d_fb_count, (size_t)job->n_fb_rows * sizeof(uint32_t)));
     }
     auto row = [&](uint32_t r) { return r < job->n_rows ? job->d_rows + r * s
                                                        : job->d_fb_rows + (r - job->n_rows) * s; };
@@ -701,9 +687,7 @@ static int fallback_descs(fpm_sketch_job *job)
         for (size_t i = 0; i < plan.size(); i++)
             md[i] = MergeDesc{row(plan[i][0]), cnt(plan[i][0]), row(plan[i][1]), cnt(plan[i][1]),
                               row(plan[i][2]), cnt(plan[i][2])};
-        HIP_TRY(hipMalloc(dst, std::max<size_t>(1, md.size()) * sizeof(MergeDesc)));
-        if (!md.empty())
-            HIP_TRY(copy_in(job->ctx, *dst, md.data(), md.size() * sizeof(MergeDesc)));
+        HIP_TRY(job->mem.upload(job->ctx, dst, md.data(), md.size() * sizeof(MergeDesc)));
         return FPM_OK;
     };
     if (int rc = upload(job->fplan, &job->d_fmerge)) return rc;
@@ -714,11 +698,9 @@ static int fallback_descs(fpm_sketch_job *job)
 static int redo_buffers(fpm_sketch_job *job)
 {
     if (!job->d_rtiles)
-        HIP_TRY(hipMalloc((void **)&job->d_rtiles,
-                          std::max<size_t>(1, std::max(job->h_tiles.size(), job->h_stiles.size())) *
-                              sizeof(TileDesc)));
-    if (!job->d_rsel)
-        HIP_TRY(hipMalloc((void **)&job->d_rsel, std::max<size_t>(1, job->h_sel.size()) * sizeof(SelDesc)));
+        HIP_TRY(job->mem.get(&job->d_rtiles,
+                             std::max(job->h_tiles.size(), job->h_stiles.size()) * sizeof(TileDesc)));
+    if (!job->d_rsel) HIP_TRY(job->mem.get(&job->d_rsel, job->h_sel.size() * sizeof(SelDesc)));
     return FPM_OK;
 }
 
@@ -1008,9 +990,9 @@ int fpm_sketch_mult(fpm_sketch_job *job, void *stream, uint32_t *out_mult)
     const uint64_t s = job->kp.s, ng = job->n_groups;
     if (!ng) return FPM_OK;
     if (!job->d_mult) {
-        HIP_TRY(hipMalloc(&job->d_mult, ng * s * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&job->d_first, ng * s * sizeof(unsigned long long)));
-        HIP_TRY(hipMalloc(&job->d_ttop, ng * sizeof(uint64_t)));
+        HIP_TRY(job->mem.get(&job->d_mult, ng * s * sizeof(uint32_t)));
+        HIP_TRY(job->mem.get(&job->d_first, ng * s * sizeof(unsigned long long)));
+        HIP_TRY(job->mem.get(&job->d_ttop, ng * sizeof(uint64_t)));
     }
     HIP_TRY(hipMemsetAsync(job->d_mult, 0, ng * s * sizeof(uint32_t), st));
     HIP_TRY(hipMemsetAsync(job->d_first, 0xff, ng * s * sizeof(unsigned long long), st));
@@ -1080,8 +1062,9 @@ static int reads_round(fpm_sketch_job *job, fpm_sketch_job *wide, uint32_t round
     const size_t n_ent = (size_t)ng * S;
     const size_t wcnt_bytes = n_ent * sizeof(uint32_t);
     const size_t slots_bytes = n_ent * m * sizeof(unsigned long long);
-    uint32_t *d_wcnt = nullptr;
-    unsigned long long *d_slots = nullptr;
+    DevBufs tmp(ctx);
+    uint32_t *d_wcnt;
+    unsigned long long *d_slots;
     auto body = [&]() -> int {
         size_t mem_free = 0, mem_total = 0;
         HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
@@ -1089,8 +1072,8 @@ static int reads_round(fpm_sketch_job *job, fpm_sketch_job *wide, uint32_t round
             return fail(FPM_ENOMEM, "reads mode: " + std::to_string((wcnt_bytes + slots_bytes) >> 20) +
                                         " MB of counts and position slots (groups x wide sketch x "
                                         "(4 + 8 min_copies) B) exceed the free device memory");
-        HIP_TRY(pool_alloc(ctx, (void **)&d_wcnt, wcnt_bytes));
-        HIP_TRY(pool_alloc(ctx, (void **)&d_slots, slots_bytes));
+        HIP_TRY(tmp.get_pooled(&d_wcnt, wcnt_bytes));
+        HIP_TRY(tmp.get_pooled(&d_slots, slots_bytes));
         HIP_TRY(hipMemsetAsync(d_wcnt, 0, n_ent * sizeof(uint32_t), st));
         HIP_TRY(hipMemsetAsync(d_slots, 0xff, n_ent * m * sizeof(unsigned long long), st));
         for (int c = 0; c < kTileClasses; c++) {
@@ -1120,9 +1103,7 @@ static int reads_round(fpm_sketch_job *job, fpm_sketch_job *wide, uint32_t round
         return FPM_OK;
     };
     const int rc = body();
-    if (rc) (void)hipStreamSynchronize(st);
-    pool_free(ctx, d_wcnt, wcnt_bytes);
-    pool_free(ctx, d_slots, slots_bytes);
+    if (rc) (void)hipStreamSynchronize(st);   // before `tmp` hands the two buffers back
     return rc;
 }
 
@@ -1137,20 +1118,19 @@ int fpm_sketch_reads_run(fpm_sketch_job *job, void *stream)
     if (!ng) return FPM_OK;
     if (!job->d_rrows) {
         // all five or none: a later run must not find some of them missing
-        hipError_t e = hipMalloc((void **)&job->d_rrows, ng * s * sizeof(uint64_t));
-        if (e == hipSuccess) e = hipMalloc((void **)&job->d_rmult, ng * s * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void **)&job->d_rcount, ng * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void **)&job->d_rdone, ng * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void **)&job->d_rttop, ng * sizeof(uint64_t));
+        DevBufs out;
+        hipError_t e = out.get(&job->d_rrows, ng * s * sizeof(uint64_t));
+        if (e == hipSuccess) e = out.get(&job->d_rmult, ng * s * sizeof(uint32_t));
+        if (e == hipSuccess) e = out.get(&job->d_rcount, ng * sizeof(uint32_t));
+        if (e == hipSuccess) e = out.get(&job->d_rdone, ng * sizeof(uint32_t));
+        if (e == hipSuccess) e = out.get(&job->d_rttop, ng * sizeof(uint64_t));
         if (e != hipSuccess) {
-            for (void *p : {(void *)job->d_rrows, (void *)job->d_rmult, (void *)job->d_rcount,
-                            (void *)job->d_rdone, (void *)job->d_rttop})
-                (void)hipFree(p);
             job->d_rrows = job->d_rttop = nullptr;
             job->d_rmult = job->d_rcount = job->d_rdone = nullptr;
             job->reads_rounds = -1;
             return fail(FPM_ENOMEM, std::string("reads mode output alloc: ") + hipGetErrorString(e));
         }
+        job->mem.absorb(std::move(out));
     }
     job->h_rdone.assign(ng, 0);
     HIP_TRY(hipMemsetAsync(job->d_rdone, 0, ng * sizeof(uint32_t), st));

@@ -31,23 +31,20 @@ int fpm_fp_hash_lines(fpm_ctx *ctx, const uint64_t *vals, const uint64_t *line_o
     if (n_lines == 0) return FPM_OK;
     const uint64_t nv = line_off[n_lines];
     const size_t ob = (use64 ? 8 : 4) * n_lines;
-    uint64_t *dv = nullptr, *doff = nullptr;
-    void *dout = nullptr;
-    hipError_t e = hipMalloc((void **)&dv, (nv ? nv : 1) * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&doff, (n_lines + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc(&dout, ob);
-    if (e == hipSuccess && nv) e = copy_in(ctx, dv, vals, nv * 8);
+    DevBufs mem;
+    uint64_t *dv, *doff;
+    void *dout;
+    hipError_t e = mem.get(&dv, std::max<uint64_t>(nv, 1) * 8);
+    if (e == hipSuccess) e = mem.get(&doff, (n_lines + 1) * 8);
+    if (e == hipSuccess) e = mem.get(&dout, ob);
+    if (e == hipSuccess) e = copy_in(ctx, dv, vals, nv * 8);
     if (e == hipSuccess) e = copy_in(ctx, doff, line_off, (n_lines + 1) * 8);
-    int rc = FPM_OK;
-    if (e != hipSuccess) rc = fail(FPM_EHIP, std::string("fp staging: ") + hipGetErrorString(e));
-    if (!rc) rc = fpm_fp_hash_lines_dev(ctx, dv, doff, n_lines, seed, use64, dout, nullptr);
-    if (!rc) {
-        e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = copy_out(ctx, out, dout, ob);
-        if (e != hipSuccess) rc = fail(FPM_EHIP, std::string("fp fetch: ") + hipGetErrorString(e));
-    }
-    (void)hipFree(dv); (void)hipFree(doff); (void)hipFree(dout);
-    return rc;
+    if (e != hipSuccess) return fail(FPM_EHIP, std::string("fp staging: ") + hipGetErrorString(e));
+    if (int rc = fpm_fp_hash_lines_dev(ctx, dv, doff, n_lines, seed, use64, dout, nullptr)) return rc;
+    e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = copy_out(ctx, out, dout, ob);
+    if (e != hipSuccess) return fail(FPM_EHIP, std::string("fp fetch: ") + hipGetErrorString(e));
+    return FPM_OK;
 }
 
 }  // extern "C"
@@ -72,14 +69,7 @@ struct fpm_fptext {
     uint64_t n_refs = 0;
     uint64_t *d_first = nullptr, *d_length = nullptr, *d_ref_id_off = nullptr;
     uint32_t *d_ref_id_len = nullptr;
-    std::vector<std::pair<void *, size_t>> bufs;   // every buffer above, with its size
-    template <typename T> hipError_t alloc(T **p, size_t bytes)
-    {
-        void *q = nullptr;
-        const hipError_t e = pool_alloc(ctx, &q, bytes);
-        if (e == hipSuccess) { bufs.push_back({q, bytes}); *p = static_cast<T *>(q); }
-        return e;
-    }
+    DevBufs mem;                                   // owns every buffer above, all pooled
 };
 
 static void fptext_release(fpm_fptext *j)
@@ -88,7 +78,6 @@ static void fptext_release(fpm_fptext *j)
     (void)hipSetDevice(j->ctx->device);
     // the job's kernels ran on the context stream: done before its buffers are handed out again
     (void)hipStreamSynchronize(j->ctx->stream);
-    for (auto &b : j->bufs) pool_free(j->ctx, b.first, b.second);
 }
 
 extern "C" {
@@ -102,13 +91,13 @@ int fpm_fp_text_stage(fpm_ctx *ctx, const char *text, uint64_t text_len, uint64_
     if (int rc = set_device(ctx)) return rc;
     std::unique_ptr<fpm_fptext, void (*)(fpm_fptext *)> j(new fpm_fptext,
         [](fpm_fptext *p) { fptext_release(p); delete p; });
-    j->ctx = ctx;
+    j->ctx = j->mem.ctx = ctx;
     j->use64 = use64;
     hipStream_t st = ctx->stream;
     const uint32_t nb = text_blocks(text_len);
     const uint64_t scan_w = scan_scratch_words(nb ? nb : 1);
-    HIP_TRY(j->alloc(&j->d_text, text_len + 16));
-    HIP_TRY(j->alloc(&j->d_blk, ((size_t)2 * nb + 2 + scan_w) * 4));
+    HIP_TRY(j->mem.get_pooled(&j->d_text, text_len + 16));
+    HIP_TRY(j->mem.get_pooled(&j->d_blk, ((size_t)2 * nb + 2 + scan_w) * 4));
     if (text_len) HIP_TRY(h2d_staged(ctx, j->d_text, text, text_len));
     uint32_t *blk_cnt = j->d_blk, *blk_off = j->d_blk + nb, *scan_s = j->d_blk + 2 * nb + 2;
     // newline count first: it sizes the line index
@@ -124,7 +113,7 @@ int fpm_fp_text_stage(fpm_ctx *ctx, const char *text, uint64_t text_len, uint64_
         if (int rc = read_counters(ctx, (const unsigned long long *)(blk_off + nb), 1, st)) return rc;
         n_nl = (uint32_t)ctx->host_counters[0];
     }
-    HIP_TRY(j->alloc(&j->d_line_start, (n_nl + 1) * 8));
+    HIP_TRY(j->mem.get_pooled(&j->d_line_start, (n_nl + 1) * 8));
     HIP_TRY(hipMemsetAsync(j->d_line_start, 0, 8, st));
     if (n_nl) {
         TimedLaunch tl(ctx, FPM_K_FPTEXT, st);
@@ -135,11 +124,11 @@ int fpm_fp_text_stage(fpm_ctx *ctx, const char *text, uint64_t text_len, uint64_
     const uint64_t nl = std::min(total, max_lines);
     j->n_lines = nl;
     if (nl) {
-        HIP_TRY(j->alloc(&j->d_id_off, nl * 8));
-        HIP_TRY(j->alloc(&j->d_id_len, nl * 4));
-        HIP_TRY(j->alloc(&j->d_n_vals, nl * 4));
-        HIP_TRY(j->alloc(&j->d_hash, nl * (use64 ? 8 : 4)));
-        HIP_TRY(j->alloc(&j->d_new_id, nl));
+        HIP_TRY(j->mem.get_pooled(&j->d_id_off, nl * 8));
+        HIP_TRY(j->mem.get_pooled(&j->d_id_len, nl * 4));
+        HIP_TRY(j->mem.get_pooled(&j->d_n_vals, nl * 4));
+        HIP_TRY(j->mem.get_pooled(&j->d_hash, nl * (use64 ? 8 : 4)));
+        HIP_TRY(j->mem.get_pooled(&j->d_new_id, nl));
         TimedLaunch tl(ctx, FPM_K_FPTEXT, st);
         HIP_TRY(launch_fp_lines(j->d_text, text_len, j->d_line_start, n_nl, nl, seed, use64,
                                 j->d_id_off, j->d_id_len, j->d_n_vals, j->d_hash, j->d_new_id, st));
@@ -180,7 +169,7 @@ int fpm_fp_text_refs(fpm_fptext *j, uint64_t cap, uint64_t *n_refs, uint64_t *fi
     if (!j->refs_done && n) {
         const uint32_t nb = fp_head_blocks(n);
         uint32_t *blk;
-        HIP_TRY(j->alloc(&blk, ((size_t)2 * nb + 2 + scan_scratch_words(nb)) * 4));
+        HIP_TRY(j->mem.get_pooled(&blk, ((size_t)2 * nb + 2 + scan_scratch_words(nb)) * 4));
         uint32_t *blk_cnt = blk, *blk_off = blk + nb, *scan_s = blk + 2 * nb + 2;
         {
             TimedLaunch tl(ctx, FPM_K_FPTEXT, st);
@@ -192,7 +181,7 @@ int fpm_fp_text_refs(fpm_fptext *j, uint64_t cap, uint64_t *n_refs, uint64_t *fi
         const uint32_t tot = (uint32_t)ctx->host_counters[0];
         j->n_refs = tot;
         uint64_t *blk4;
-        HIP_TRY(j->alloc(&blk4, (size_t)tot * 28 + 32));
+        HIP_TRY(j->mem.get_pooled(&blk4, (size_t)tot * 28 + 32));
         j->d_first = blk4;
         j->d_ref_id_off = blk4 + tot;
         j->d_length = blk4 + 2 * (size_t)tot;
@@ -256,40 +245,22 @@ struct fpm_seqtext {
     void *d_xf = nullptr, *d_cin = nullptr;
     uint64_t *d_rec = nullptr;                  // hdr_pos | hdr_end | kept_at | seq_off | seq_len
     uint64_t *d_totals = nullptr;
+    DevBufs mem;                                // owns every buffer above
 };
 
 static void seqtext_release(fpm_seqtext *j)
 {
-    if (!j) return;
-    (void)hipSetDevice(j->ctx->device);
-    for (void *p : {(void *)j->d_text, (void *)j->d_reset, (void *)j->d_out, j->d_xf, j->d_cin,
-                    (void *)j->d_rec, (void *)j->d_totals})
-        if (p) (void)hipFree(p);
+    if (j) (void)hipSetDevice(j->ctx->device);
 }
 
 // The FASTQ path of fpm_seq_parse (seqparse.hip: 4-line records verified against kseq_read):
 // newline index, lines per file, record table + packed bases.  *ok = false when a record does
 // not read the 4-line way (nothing of the job changed then).
-namespace {
-// device scratch freed on every return path
-struct TmpBufs {
-    std::vector<void *> p;
-    ~TmpBufs() { for (void *x : p) (void)hipFree(x); }
-    template <typename T> hipError_t get(T **out, size_t bytes)
-    {
-        void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
-        if (e == hipSuccess) { p.push_back(q); *out = static_cast<T *>(q); }
-        return e;
-    }
-};
-}  // namespace
-
 static int fastq_parse(fpm_ctx *ctx, fpm_seqtext *j, uint64_t text_bytes, hipStream_t st, bool *ok)
 {
     *ok = false;
     const uint32_t n_seg = (uint32_t)j->seg_off.size();
-    TmpBufs tmp;
+    DevBufs tmp;   // the scratch, and until the end the record table and the packed records
     const uint32_t nb = text_blocks(text_bytes);
     const uint64_t scan_w = scan_scratch_words(nb ? nb : 1);
     uint32_t *blk;
@@ -324,8 +295,7 @@ static int fastq_parse(fpm_ctx *ctx, fpm_seqtext *j, uint64_t text_bytes, hipStr
     uint64_t *d_base, *d_rec, *d_scan, *d_total;
     uint32_t *d_fail;
     HIP_TRY(tmp.get(&d_base, base.size() * 8));
-    HIP_TRY(hipMalloc((void **)&d_rec, (size_t)(n_rec ? n_rec : 1) * 5 * 8));
-    tmp.p.push_back(d_rec);
+    HIP_TRY(tmp.get(&d_rec, (size_t)(n_rec ? n_rec : 1) * 5 * 8));
     HIP_TRY(tmp.get(&d_scan, ((n_rec + 1023) / 1024 + 1) * 8));
     HIP_TRY(tmp.get(&d_total, 16));
     HIP_TRY(tmp.get(&d_fail, 4));
@@ -344,19 +314,15 @@ static int fastq_parse(fpm_ctx *ctx, fpm_seqtext *j, uint64_t text_bytes, hipStr
         return FPM_OK;
     }
     uint8_t *d_out;
-    HIP_TRY(hipMalloc((void **)&d_out, total + n_rec + 64));
-    if (hipError_t e = launch_fq_emit(j->d_text, n_rec, d_rec, d_out, st)) {
-        (void)hipFree(d_out);
-        return fail(FPM_EHIP, std::string("fastq emit: ") + hipGetErrorString(e));
+    HIP_TRY(tmp.get(&d_out, total + n_rec + 64));
+    hipError_t e = launch_fq_emit(j->d_text, n_rec, d_rec, d_out, st);
+    if (e == hipSuccess) {
+        tl.done();
+        e = hipStreamSynchronize(st);
     }
-    tl.done();
-    if (hipError_t e = hipStreamSynchronize(st)) {
-        (void)hipFree(d_out);
-        return fail(FPM_EHIP, std::string("fastq emit: ") + hipGetErrorString(e));
-    }
-    tmp.p.erase(std::find(tmp.p.begin(), tmp.p.end(), (void *)d_rec));   // the job keeps it
-    j->d_rec = d_rec;
-    j->d_out = d_out;
+    if (e != hipSuccess) return fail(FPM_EHIP, std::string("fastq emit: ") + hipGetErrorString(e));
+    j->mem.adopt(j->d_rec = tmp.release(d_rec));   // the job keeps these two
+    j->mem.adopt(j->d_out = tmp.release(d_out));
     j->n_rec = n_rec;
     j->total_kept = total;
     *ok = true;
@@ -390,11 +356,11 @@ int fpm_seq_parse(fpm_ctx *ctx, const char *const *seg_text, const uint64_t *seg
     const uint32_t n_chunks = (uint32_t)n_chunks64;
     hipStream_t st = ctx->stream;
     // 64 bytes of slack: the FASTQ emit reads whole 64-byte windows past a sequence line
-    HIP_TRY(hipMalloc(&j->d_text, text_bytes + 64));
-    HIP_TRY(hipMalloc(&j->d_reset, n_chunks ? n_chunks : 1));
-    HIP_TRY(hipMalloc(&j->d_xf, (size_t)(n_chunks ? n_chunks : 1) * seq_xf_bytes()));
-    HIP_TRY(hipMalloc(&j->d_cin, (size_t)(n_chunks ? n_chunks : 1) * seq_cin_bytes()));
-    HIP_TRY(hipMalloc(&j->d_totals, 3 * sizeof(uint64_t)));
+    HIP_TRY(j->mem.get(&j->d_text, text_bytes + 64));
+    HIP_TRY(j->mem.get(&j->d_reset, n_chunks ? n_chunks : 1));
+    HIP_TRY(j->mem.get(&j->d_xf, (size_t)(n_chunks ? n_chunks : 1) * seq_xf_bytes()));
+    HIP_TRY(j->mem.get(&j->d_cin, (size_t)(n_chunks ? n_chunks : 1) * seq_cin_bytes()));
+    HIP_TRY(j->mem.get(&j->d_totals, 3 * sizeof(uint64_t)));
     std::vector<uint8_t> reset(n_chunks ? n_chunks : 1, 0);
     for (uint32_t i = 0; i < n_seg; i++)
         if (j->seg_off[i] / kSpChunk < n_chunks) reset[j->seg_off[i] / kSpChunk] = 1;
@@ -405,8 +371,9 @@ int fpm_seq_parse(fpm_ctx *ctx, const char *const *seg_text, const uint64_t *seg
         HIP_TRY(h2d_staged(ctx, j->d_text + j->seg_off[i], seg_text[i], seg_len[i]));
     // the records are emitted: the text image and scan scratch are not needed past that point
     auto finish = [&]() {
-        for (void **p : {(void **)&j->d_text, (void **)&j->d_xf, (void **)&j->d_cin})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
+        j->mem.drop(j->d_text);
+        j->mem.drop(j->d_xf);
+        j->mem.drop(j->d_cin);
         *n_records = j->n_rec;
         *job = j.release();
         return FPM_OK;
@@ -430,8 +397,8 @@ int fpm_seq_parse(fpm_ctx *ctx, const char *const *seg_text, const uint64_t *seg
     j->n_rec = tot[0];
     j->total_kept = tot[1];
     if (quality_lines) *quality_lines = tot[2] ? 1 : 0;
-    HIP_TRY(hipMalloc(&j->d_out, j->total_kept + j->n_rec + 64));
-    HIP_TRY(hipMalloc(&j->d_rec, (size_t)(j->n_rec ? j->n_rec : 1) * 5 * sizeof(uint64_t)));
+    HIP_TRY(j->mem.get(&j->d_out, j->total_kept + j->n_rec + 64));
+    HIP_TRY(j->mem.get(&j->d_rec, (size_t)(j->n_rec ? j->n_rec : 1) * 5 * sizeof(uint64_t)));
     if (n_chunks) {
         const uint64_t n = j->n_rec ? j->n_rec : 1;
         TimedLaunch tl(ctx, FPM_K_SEQPARSE, st);
@@ -499,7 +466,7 @@ int seqtext_records(fpm_ctx *ctx, fpm_seqtext *seq, uint64_t *n_rec, std::vector
     HIP_TRY(d2h_staged(ctx, pos->data(), seq->d_rec + 3 * nn, n * 8));
     HIP_TRY(d2h_staged(ctx, len->data(), seq->d_rec + 4 * nn, n * 8));
     *n_rec = n;
-    *d_packed = seq->d_out;
+    *d_packed = seq->mem.release(seq->d_out);
     seq->d_out = nullptr;
     return FPM_OK;
 }
@@ -540,9 +507,10 @@ int fpm_sketch_stage_seq(fpm_ctx *ctx, const fpm_sketch_params *p, fpm_seqtext *
                      [&](uint32_t a, uint32_t b) { return R.group[a] < R.group[b]; });
     R.d_seq = seq->d_out;
     R.d_seq_bytes = seq->total_kept + seq->n_rec;
-    const int rc = stage_core(ctx, p, R, job_out);
-    if (!R.d_seq) seq->d_out = nullptr;   // the job owns the packed records now
-    return rc;
+    if (int rc = stage_core(ctx, p, R, job_out)) return rc;
+    seq->mem.release(seq->d_out);   // the job owns the packed records now
+    seq->d_out = nullptr;
+    return FPM_OK;
 }
 
 }  // extern "C"
