@@ -339,16 +339,91 @@ int sketchParameterSetup(Parameters &p, const Command &c)
     return 0;
 }
 
-void warnKmerSize(const Parameters &p, const Command &c, uint64_t lengthMax,
-                  const std::string &lengthMaxName, double randomChance, int kMin,
-                  int warningCount)
+bool containsSub(const std::vector<std::string> &v, const char *s)
 {
+    bool f = false;
+    for (const auto &x : v) f = x.find(s) != std::string::npos;
+    return f;
+}
+
+std::vector<std::string> inputFiles(const std::vector<std::string> &args, size_t first, bool list)
+{
+    std::vector<std::string> files;
+    for (size_t i = first; i < args.size(); i++) {
+        if (list) splitFile(args[i], files);
+        else files.push_back(args[i]);
+    }
+    return files;
+}
+
+bool checkInputArguments(const std::vector<std::string> &args, size_t first, const char *word)
+{
+    for (size_t f = first; f < args.size(); f++) {
+        if (args[f] == "-") {
+            if (f > first) {
+                std::cerr << "ERROR: '-' for stdin must be first " << word << std::endl;
+                return false;
+            }
+        } else if (FILE *fp = fopen(args[f].c_str(), "r")) {
+            fclose(fp);
+        } else {
+            std::cerr << "ERROR: could not open " << args[f] << std::endl;
+            return false;
+        }
+    }
+    return true;
+}
+
+bool refuseSketchOptions(const Command &c, const char *dash, bool allStop)
+{
+    for (const std::string o : {"kmer", "noncanonical", "protein", "alphabet"})
+        if (c.getOption(o).active) {
+            std::cerr << "ERROR: The option " << dash << c.getOption(o).identifier
+                      << " cannot be used when a sketch is provided; it is inherited from the "
+                         "sketch." << std::endl;
+            if (allStop || o == "kmer" || o == "noncanonical") return true;
+        }
+    return false;
+}
+
+void inheritFromSketch(Parameters &p, const Sketch &reference)
+{
+    p.minHashesPerWindow = (uint64_t)reference.getMinHashesPerWindow();
+    p.kmerSize = reference.getKmerSize();
+    p.noncanonical = reference.getNoncanonical();
+    p.preserveCase = reference.getPreserveCase();
+    p.seed = reference.getHashSeed();
+    std::string alphabet;
+    reference.getAlphabetAsString(alphabet);
+    setAlphabetFromString(p, alphabet.c_str());
+}
+
+void KmerWarning::scan(const Sketch &sketch, const Parameters &p)
+{
+    const double lengthThreshold = (p.warning * sketch.getKmerSpace()) / (1. - p.warning);
+    for (uint64_t i = 0; i < sketch.getReferenceCount(); i++) {
+        const uint64_t length = sketch.getReference(i).length;
+        if (length > lengthThreshold) {
+            if (count == 0 || length > lengthMax) {
+                lengthMax = length;
+                lengthMaxName = sketch.getReference(i).name;
+                randomChance = sketch.getRandomKmerChance(i);
+                kMin = sketch.getMinKmerSize(i);
+            }
+            count++;
+        }
+    }
+}
+
+void KmerWarning::print(const Parameters &p, const Command &c) const
+{
+    if (count == 0 || p.reads) return;
     std::cerr << "\nWARNING: For the k-mer size used (" << p.kmerSize
               << "), the random match probability (" << randomChance
               << ") is above the specified warning threshold (" << p.warning
               << ") for the sequence \"" << lengthMaxName << "\" of size " << lengthMax;
-    if (warningCount > 1) std::cerr << " (and " << (warningCount - 1) << " others)";
-    std::cerr << ". Distances to " << (warningCount == 1 ? "this sequence" : "these sequences")
+    if (count > 1) std::cerr << " (and " << (count - 1) << " others)";
+    std::cerr << ". Distances to " << (count == 1 ? "this sequence" : "these sequences")
               << " may be underestimated as a result. To meet the threshold of " << p.warning
               << ", a k-mer size of at least " << kMin << " is required. See: -"
               << c.getOption("kmer").identifier << ", -" << c.getOption("warning").identifier

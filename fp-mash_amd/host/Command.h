@@ -3,6 +3,7 @@
 // in main.cpp exactly as mash.cpp:23-37 does for the hot-path verbs.
 #pragma once
 
+#include <cstdint>
 #include <map>
 #include <string>
 #include <vector>
@@ -99,8 +100,32 @@ public:
 // sketchParameterSetup (sketchParameterSetup.cpp:9-126)
 struct Parameters;
 int sketchParameterSetup(Parameters &p, const Command &c);
-void warnKmerSize(const Parameters &p, const Command &c, uint64_t lengthMax,
-                  const std::string &lengthMaxName, double randomChance, int kMin,
-                  int warningCount);
+
+// What the verbs' run() functions share.
+class Sketch;
+// containsMSH / containsTXT (CommandDistance.cpp:454-476): substring test on the last file
+bool containsSub(const std::vector<std::string> &v, const char *s);
+// args[first..) as input files; with `list` (-l) each names a file of paths, one per line
+std::vector<std::string> inputFiles(const std::vector<std::string> &args, size_t first, bool list);
+// The pool / input arguments args[first..): "-" only in the first place, every other one a
+// file that opens.  false after the message, which calls the arguments `word`s.
+bool checkInputArguments(const std::vector<std::string> &args, size_t first, const char *word);
+// A sketch reference fixes -k, -n, -a and -z: the message for each one given, with `dash`
+// before the option's letter.  true where the run stops: at any of them (allStop), else at
+// -k and -n only.
+bool refuseSketchOptions(const Command &c, const char *dash, bool allStop);
+// the reference is a sketch: k, s, seed, case and alphabet come from it
+void inheritFromSketch(Parameters &p, const Sketch &reference);
+
+// The k-mer size warning (CommandDistance.cpp:146-170, 327-331): the sequences of a sketch
+// longer than p.warning allows, the longest named when the command ends.
+struct KmerWarning {
+    uint64_t lengthMax = 0;
+    std::string lengthMaxName;
+    double randomChance = 0;
+    int kMin = 0, count = 0;
+    void scan(const Sketch &sketch, const Parameters &p);
+    void print(const Parameters &p, const Command &c) const;   // nothing in reads mode
+};
 
 }  // namespace fpmhost

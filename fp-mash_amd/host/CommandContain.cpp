@@ -6,6 +6,8 @@
 #include "CommandContain.h"
 #include "Device.h"
 #include "Sketch.h"
+#include "SketchRows.h"
+#include "TextOut.h"
 
 #include <algorithm>
 #include <cmath>
@@ -38,31 +40,19 @@ CommandContain::CommandContain()
 
 namespace {
 
-// one sketch set as a dense row matrix (u64, or u32 when !use64) on the device
+// one packed sketch set on the device
 struct DeviceRows {
     void *rows = nullptr, *len = nullptr;
     uint64_t stride = 1;
     uint32_t n = 0;
-    void upload(const Sketch &s, bool use64)
+    void upload(const PackedRows &p)
     {
-        const uint32_t hb = use64 ? 8 : 4;
-        n = (uint32_t)s.getReferenceCount();
-        for (uint64_t i = 0; i < n; i++)
-            stride = std::max<uint64_t>(stride, s.getReference(i).hashes.size());
-        std::vector<uint8_t> M((size_t)n * stride * hb, 0);
-        std::vector<uint32_t> L(n);
-        for (uint64_t i = 0; i < n; i++) {
-            const Reference &r = s.getReference(i);
-            L[i] = (uint32_t)r.hashes.size();
-            for (uint64_t j = 0; j < r.hashes.size(); j++) {
-                if (use64) memcpy(&M[(i * stride + j) * 8], &r.hashes[j], 8);
-                else { const uint32_t v = (uint32_t)r.hashes[j]; memcpy(&M[(i * stride + j) * 4], &v, 4); }
-            }
-        }
-        check(fpm_malloc(device(), &rows, M.size()), "contain");
+        stride = p.width;
+        n = (uint32_t)p.n;
+        check(fpm_malloc(device(), &rows, p.bytes()), "contain");
         check(fpm_malloc(device(), &len, (size_t)n * 4), "contain");
-        check(fpm_memcpy_h2d(device(), rows, M.data(), M.size()), "contain");
-        check(fpm_memcpy_h2d(device(), len, L.data(), (size_t)n * 4), "contain");
+        check(fpm_memcpy_h2d(device(), rows, p.data(), p.bytes()), "contain");
+        check(fpm_memcpy_h2d(device(), len, p.len.data(), (size_t)n * 4), "contain");
     }
     void release()
     {
@@ -91,13 +81,7 @@ int CommandContain::run() const
     if (isSketch) {
         // (CommandContain.cpp:111-131: -k and -n stop the run; the -a / -z messages print and
         // the run goes on.  Unlike dist's, these name the option without its dash.)
-        for (const char *o : {"kmer", "noncanonical", "protein", "alphabet"})
-            if (options.at(o).active) {
-                std::cerr << "ERROR: The option " << options.at(o).identifier
-                          << " cannot be used when a sketch is provided; it is inherited from the "
-                             "sketch." << std::endl;
-                if (!strcmp(o, "kmer") || !strcmp(o, "noncanonical")) return 1;
-            }
+        if (refuseSketchOptions(*this, "", false)) return 1;
     } else {
         std::cerr << "Sketching " << fileReference
                   << " (provide sketch file made with \"mash sketch\" to skip)...";
@@ -106,22 +90,11 @@ int CommandContain::run() const
     std::vector<std::string> refArg{fileReference};
     sketchRef.initFromFiles(refArg, parameters);
     if (isSketch) {
-        parameters.minHashesPerWindow = (uint64_t)sketchRef.getMinHashesPerWindow();
-        parameters.kmerSize = sketchRef.getKmerSize();
-        parameters.noncanonical = sketchRef.getNoncanonical();
-        parameters.preserveCase = sketchRef.getPreserveCase();
-        parameters.seed = sketchRef.getHashSeed();
-        std::string alphabet;
-        sketchRef.getAlphabetAsString(alphabet);
-        setAlphabetFromString(parameters, alphabet.c_str());
+        inheritFromSketch(parameters, sketchRef);
     } else {
         std::cerr << "done.\n";
     }
-    std::vector<std::string> queryFiles;
-    for (size_t i = 1; i < arguments.size(); i++) {
-        if (list) splitFile(arguments[i], queryFiles);
-        else queryFiles.push_back(arguments[i]);
-    }
+    const std::vector<std::string> queryFiles = inputFiles(arguments, 1, list);
     Sketch sketchQuery;
     sketchQuery.initFromFiles(queryFiles, parameters, 0, true, true);
 
@@ -131,8 +104,8 @@ int CommandContain::run() const
     const double errorMax = (double)(float)parameters.error;
     const bool use64 = sketchRef.getUse64();
     DeviceRows R, Q;
-    R.upload(sketchRef, use64);
-    Q.upload(sketchQuery, use64);
+    R.upload(PackedRows(sketchRef.references, use64));
+    Q.upload(PackedRows(sketchQuery.references, use64));
     const uint32_t hb = use64 ? 8 : 4;
 
     // query-row blocks of at most 2^25 pairs: 8 B per pair on the device and on the host
@@ -142,8 +115,8 @@ int CommandContain::run() const
     check(fpm_malloc(device(), &dCommon, cells * 4), "contain");
     check(fpm_malloc(device(), &dSteps, cells * 4), "contain");
     std::vector<uint32_t> common(cells), steps(cells);
-    std::string out;
-    char num[80];
+    StdoutText text;
+    std::string &out = text.buf;
     for (uint64_t q0 = 0; q0 < nQ; q0 += qBlock) {
         const uint64_t nq = std::min(qBlock, nQ - q0);
         check(fpm_contain_dev(device(), R.rows, (const uint32_t *)R.len, R.stride, (uint32_t)nR,
@@ -160,18 +133,19 @@ int CommandContain::run() const
                 const double error = 1. / sqrt((double)j);
                 if (!(error <= errorMax)) continue;
                 const double score = double(common[q * nR + r]) / (double)j;
-                const int n = snprintf(num, sizeof num, "%g\t%g\t", score, error);
-                out.append(num, n);
+                putNum(out, score);
+                out += '\t';
+                putNum(out, error);
+                out += '\t';
                 out += sketchRef.getReference(r).name;
                 out += '\t';
                 out += qname;
                 out += '\n';
             }
-            if (out.size() > (1 << 22)) { fwrite(out.data(), 1, out.size(), stdout); out.clear(); }
+            text.flushIfLarge();
         }
     }
-    fwrite(out.data(), 1, out.size(), stdout);
-    fflush(stdout);
+    text.finish();
     fpm_free(device(), dCommon);
     fpm_free(device(), dSteps);
     R.release();

@@ -8,6 +8,7 @@
 // every other verb's; the inputs are streamed in slices of whole records bounded by bytes.
 #include "CommandKFinger.h"
 #include "Device.h"
+#include "ParsedFile.h"
 #include "SeqReader.h"
 #include "Sketch.h"
 #include "Timing.h"
@@ -185,43 +186,37 @@ struct Generator {
     {
         const size_t budget = kfingerSliceBytes();
         if (image.size() > budget) return hostWalk(image, budget);
-        fpm_seqtext *parsed = nullptr;
-        uint64_t nRec = 0;
-        int quality = 0;
-        const char *ptr = image.data();
-        const uint64_t len = image.size();
-        check(fpm_seq_parse(ctx, &ptr, &len, 1, &parsed, &nRec, &quality), "sequence parse");
-        if (quality) {
-            fpm_seq_free(parsed);
-            return hostWalk(image, budget);
-        }
-        std::vector<uint32_t> seg(nRec);
-        std::vector<uint64_t> ho(nRec), hl(nRec), sl(nRec);
-        check(fpm_seq_records(parsed, seg.data(), ho.data(), hl.data(), sl.data()), "sequence parse");
-        std::vector<uint8_t> take(nRec ? nRec : 1, 0);
-        std::vector<std::string> ids(nRec);
-        uint64_t found = 0;
-        for (uint64_t r = 0; r < nRec; r++) {
-            // a '>' / '@' as the last byte of a file starts no record (kseq_read returns -1)
-            if (ho[r] + 1 >= image.size()) continue;
-            found++;
-            take[r] = 1;
-            std::string name, comment;
-            splitHeader(image.data() + ho[r] + 1, hl[r] - 1, name, comment);
-            ids[r] = lineId(name, comment);
-        }
         bool ok = true;
-        if (found && !done()) {
-            fpm_kfinger *job = nullptr;
-            uint64_t n = 0;
-            check(fpm_kfinger_stage_seq(ctx, parsed, take.data(), window, linesLeft, &job, &n),
-                  "kfinger");
-            ok = consume(job, n, ids);
+        {
+            ParsedFile parsed;
+            if (parsed.parse(ctx, image)) {
+                std::vector<uint8_t> take(parsed.nRec ? parsed.nRec : 1, 0);
+                std::vector<std::string> ids(parsed.nRec);
+                uint64_t found = 0;
+                for (uint64_t r = 0; r < parsed.nRec; r++) {
+                    if (!parsed.isRecord(r)) continue;
+                    found++;
+                    take[r] = 1;
+                    std::string name, comment;
+                    splitHeader(image.data() + parsed.headOff[r] + 1, parsed.headLen[r] - 1, name,
+                                comment);
+                    ids[r] = lineId(name, comment);
+                }
+                if (found && !done()) {
+                    fpm_kfinger *job = nullptr;
+                    uint64_t n = 0;
+                    check(fpm_kfinger_stage_seq(ctx, parsed.text, take.data(), window, linesLeft, &job,
+                                                &n),
+                          "kfinger");
+                    ok = consume(job, n, ids);
+                }
+                if (ok) {
+                    records += found;
+                    return true;
+                }
+            }
         }
-        fpm_seq_free(parsed);
-        if (!ok) return hostWalk(image, budget);   // (counts the records itself)
-        records += found;
-        return true;
+        return hostWalk(image, budget);   // (counts the records itself)
     }
 };
 
@@ -278,19 +273,7 @@ int CommandKFinger::run() const
     setAlphabetFromString(parameters, "0123456789");
     // (the window's range was checked when the option was read)
     const uint32_t window = (uint32_t)options.at("window").getArgumentAsNumber();
-    for (size_t f = 0; f < arguments.size(); f++) {
-        if (arguments[f] == "-") {
-            if (f > 0) {
-                std::cerr << "ERROR: '-' for stdin must be first input" << std::endl;
-                return 1;
-            }
-        } else if (FILE *fp = fopen(arguments[f].c_str(), "r")) {
-            fclose(fp);
-        } else {
-            std::cerr << "ERROR: could not open " << arguments[f] << std::endl;
-            return 1;
-        }
-    }
+    if (!checkInputArguments(arguments, 0, "input")) return 1;
     warmDevices();
     Generator g;
     g.window = window;

@@ -10,6 +10,7 @@
 #include "Device.h"
 #include "ScreenPool.h"
 #include "Sketch.h"
+#include "TextOut.h"
 #include "Timing.h"
 
 #include <algorithm>
@@ -69,113 +70,20 @@ int CommandScreen::run() const
         print();
         return 0;
     }
-    if (!hasSuffix(arguments[0], suffixSketch)) {
-        std::cerr << "ERROR: " << arguments[0] << " does not look like a sketch (.msh)" << std::endl;
-        return 1;
-    }
     const bool winning = options.at("winning").active;
     const double pValueMax = options.at("pvalue").getArgumentAsNumber();
     const double identityMin = options.at("identity").getArgumentAsNumber();
 
-    Sketch sketch;
-    Parameters parameters;
-    sketch.initFromFiles({arguments[0]}, parameters);
-    phaseMark("load database");
-    std::string alphabet;
-    sketch.getAlphabetAsString(alphabet);
-    if (alphabet == alphabetProtein) {
-        std::cerr << "ERROR: " << arguments[0] << " is an amino acid sketch; translated screening "
-                     "is not supported" << std::endl;
-        return 1;
-    }
-    // (CommandTaxScreen.cpp:229-250; checked before any device work)
-    for (size_t f = 1; f < arguments.size(); f++) {
-        if (arguments[f] == "-") {
-            if (f > 1) {
-                std::cerr << "ERROR: '-' for stdin must be first query" << std::endl;
-                return 1;
-            }
-        } else if (FILE *fp = fopen(arguments[f].c_str(), "r")) {
-            fclose(fp);
-        } else {
-            std::cerr << "ERROR: could not open " << arguments[f] << std::endl;
-            return 1;
-        }
-    }
+    ScreenRun db{"screen", arguments};
+    if (!db.loadDatabase() || !db.checkPoolArguments()) return 1;
     warmDevices();
+    if (!db.openTable() || !db.streamPool()) return 1;
+    const Sketch &sketch = db.sketch;
+    fpm_screen *sc = db.sc;
     const int kmerSize = sketch.getKmerSize();
-    const bool use64 = sketch.getUse64();
-    const uint32_t hb = use64 ? 8 : 4;
     const uint64_t nRef = sketch.getReferenceCount();
-
-    std::cerr << "Loading " << arguments[0] << "..." << std::endl;
-    uint64_t stride = 1;
-    for (uint64_t i = 0; i < nRef; i++)
-        stride = std::max<uint64_t>(stride, sketch.getReference(i).hashes.size());
-    std::vector<uint8_t> M((size_t)nRef * stride * hb, 0);
-    std::vector<uint32_t> L(nRef);
-    std::vector<uint64_t> lengths(nRef);
-    for (uint64_t i = 0; i < nRef; i++) {
-        const Reference &r = sketch.getReference(i);
-        L[i] = (uint32_t)r.hashes.size();
-        lengths[i] = r.length;
-        for (uint64_t j = 0; j < r.hashes.size(); j++) {
-            if (use64) memcpy(&M[(i * stride + j) * 8], &r.hashes[j], 8);
-            else { const uint32_t v = (uint32_t)r.hashes[j]; memcpy(&M[(i * stride + j) * 4], &v, 4); }
-        }
-    }
-    fpm_ctx *ctx = device();
-    fpm_screen *sc = nullptr;
-    const uint32_t s = (uint32_t)std::max<uint64_t>(1, sketch.parameters.minHashesPerWindow);
-    const int rc = fpm_screen_create(ctx, M.data(), L.data(), stride, (uint32_t)nRef, hb, s, &sc);
-    if (rc == FPM_EINVAL) {
-        std::cerr << "ERROR: " << arguments[0] << ": screen needs sketches whose hashes are in "
-                     "strictly ascending order (" << fpm_last_error() << ")" << std::endl;
-        return 1;
-    }
-    check(rc, "screen");
-    std::vector<uint8_t>().swap(M);
-    uint64_t nDistinct = 0;
-    check(fpm_screen_counts(sc, nullptr, nullptr, &nDistinct), "screen");
-    std::cerr << "   " << nDistinct << " distinct hashes." << std::endl;
-    phaseMark("database table");
-
-    const size_t queryCount = arguments.size() - 1;
-    std::cerr << "Streaming from ";
-    if (queryCount == 1) std::cerr << arguments[1];
-    else std::cerr << queryCount << " inputs";
-    std::cerr << "..." << std::endl;
-
-    Pool pool{ctx, sc, {}};
-    pool.fp.kmer_size = (uint32_t)kmerSize;
-    pool.fp.sketch_size = s;
-    pool.fp.seed = sketch.getHashSeed();
-    pool.fp.use64 = use64;
-    pool.fp.noncanonical = sketch.getNoncanonical();
-    pool.fp.preserve_case = sketch.getPreserveCase();
-    for (int c = 0; c < 256; c++) pool.fp.alphabet[c] = sketch.parameters.alphabet[c] ? 1 : 0;
-
-    // one file image at a time: device and host memory follow the largest file's slices
-    for (size_t f = 1; f < arguments.size(); f++) {
-        std::string image;
-        if (!loadSequenceFile(arguments[f], image)) {
-            std::cerr << "ERROR: could not open " << arguments[f] << std::endl;
-            return 1;
-        }
-        if (!pool.file(image)) {
-            std::cerr << "\nERROR: reading inputs" << std::endl;
-            return 1;
-        }
-    }
-    phaseMark("pool (read + parse + sketch + count)");
-    if (pool.records == 0) {
-        std::cerr << "\nERROR: Did not find sequence records in inputs" << std::endl;
-        return 1;
-    }
-    uint64_t setSize = 0;
-    check(fpm_screen_set_size(sc, &setSize), "screen");
-    std::cerr << "   Estimated distinct k-mers in pool: " << setSize << std::endl;
-    if (setSize == 0) std::cerr << "WARNING: no valid k-mers in input." << std::endl;
+    const std::vector<uint32_t> &L = db.rows.len;
+    const std::vector<uint64_t> &lengths = db.rows.length;
 
     std::vector<uint32_t> shared(nRef), median(nRef);
     check(fpm_screen_rows(sc, shared.data(), median.data()), "screen");
@@ -193,7 +101,8 @@ int CommandScreen::run() const
     phaseMark("rows + p-values");
 
     std::cerr << "Writing output..." << std::endl;
-    std::string out;
+    StdoutText text;
+    std::string &out = text.buf;
     char num[160];
     for (uint64_t i = 0; i < nRef; i++) {
         if (!(shared[i] != 0 || identityMin < 0.0)) continue;
@@ -202,17 +111,24 @@ int CommandScreen::run() const
         const double pValue = pValues[i];
         if (pValue > pValueMax) continue;
         const Reference &r = sketch.getReference(i);
-        const int n = snprintf(num, sizeof num, "%g\t%u/%u\t%u\t%g\t", identity, shared[i], L[i],
-                               median[i], pValue);
-        out.append(num, n);
+        char *p = numTo(num, identity);
+        *p++ = '\t';
+        p = uTo(p, shared[i]);
+        *p++ = '/';
+        p = uTo(p, L[i]);
+        *p++ = '\t';
+        p = uTo(p, median[i]);
+        *p++ = '\t';
+        p = numTo(p, pValue);
+        *p++ = '\t';
+        out.append(num, (size_t)(p - num));
         out += r.name;
         out += '\t';
         out += r.comment;
         out += '\n';
-        if (out.size() > (1 << 22)) { fwrite(out.data(), 1, out.size(), stdout); out.clear(); }
+        text.flushIfLarge();
     }
-    fwrite(out.data(), 1, out.size(), stdout);
-    fflush(stdout);
+    text.finish();
     fpm_screen_free(sc);
     phaseMark("output");
     return 0;

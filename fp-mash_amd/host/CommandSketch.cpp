@@ -51,11 +51,7 @@ int CommandSketch::run() const
     Parameters parameters;
     parameters.counts = options.at("counts").active;
     if (sketchParameterSetup(parameters, *this)) return 1;
-    std::vector<std::string> files;
-    for (const auto &a : arguments) {
-        if (list) splitFile(a, files);
-        else files.push_back(a);
-    }
+    const std::vector<std::string> files = inputFiles(arguments, 0, list);
     // heap-held: main leaves with _exit once the .msh is written, so the 80 MB of rows and the
     // per-reference strings of a C2 sketch are returned with the process (~3 ms of frees)
     // instead of one by one; FPMASH_CLEAN_EXIT=1 destroys it

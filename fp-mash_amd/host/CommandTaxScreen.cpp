@@ -66,24 +66,12 @@ int CommandTaxScreen::run() const
         print();
         return 0;
     }
-    if (!hasSuffix(arguments[0], suffixSketch)) {
-        std::cerr << "ERROR: " << arguments[0] << " does not look like a sketch (.msh)" << std::endl;
-        return 1;
-    }
     const std::string taxonomyDir = options.at("taxonomy-dir").argument;
     const std::string mappingFileName = options.at("mapping-file").argument;
 
-    Sketch sketch;
-    Parameters parameters;
-    sketch.initFromFiles({arguments[0]}, parameters);
-    phaseMark("load database");
-    std::string alphabet;
-    sketch.getAlphabetAsString(alphabet);
-    if (alphabet == alphabetProtein) {
-        std::cerr << "ERROR: " << arguments[0] << " is an amino acid sketch; translated screening "
-                     "is not supported" << std::endl;
-        return 1;
-    }
+    ScreenRun db{"taxscreen", arguments};
+    if (!db.loadDatabase()) return 1;
+    const Sketch &sketch = db.sketch;
     const std::string namesDumpFile = taxonomyDir + "/names.dmp";
     const std::string nodesDumpFile = taxonomyDir + "/nodes.dmp";
     if (!fileExists(namesDumpFile) || !fileExists(nodesDumpFile)) {   // (:114-122)
@@ -91,20 +79,7 @@ int CommandTaxScreen::run() const
                   << taxonomyDir << std::endl;
         return 1;
     }
-    // (:229-250; checked before any device work)
-    for (size_t f = 1; f < arguments.size(); f++) {
-        if (arguments[f] == "-") {
-            if (f > 1) {
-                std::cerr << "ERROR: '-' for stdin must be first query" << std::endl;
-                return 1;
-            }
-        } else if (FILE *fp = fopen(arguments[f].c_str(), "r")) {
-            fclose(fp);
-        } else {
-            std::cerr << "ERROR: could not open " << arguments[f] << std::endl;
-            return 1;
-        }
-    }
+    if (!db.checkPoolArguments()) return 1;
 
     std::cerr << "Loading taxonomy files ..." << std::endl;
     TaxDB taxdb;
@@ -139,76 +114,8 @@ int CommandTaxScreen::run() const
     }
 
     warmDevices();
-    const int kmerSize = sketch.getKmerSize();
-    const bool use64 = sketch.getUse64();
-    const uint32_t hb = use64 ? 8 : 4;
-
-    std::cerr << "Loading " << arguments[0] << "..." << std::endl;
-    uint64_t stride = 1;
-    for (uint64_t i = 0; i < nRef; i++)
-        stride = std::max<uint64_t>(stride, sketch.getReference(i).hashes.size());
-    std::vector<uint8_t> M((size_t)nRef * stride * hb, 0);
-    std::vector<uint32_t> L(nRef);
-    for (uint64_t i = 0; i < nRef; i++) {
-        const Reference &r = sketch.getReference(i);
-        L[i] = (uint32_t)r.hashes.size();
-        for (uint64_t j = 0; j < r.hashes.size(); j++) {
-            if (use64) memcpy(&M[(i * stride + j) * 8], &r.hashes[j], 8);
-            else { const uint32_t v = (uint32_t)r.hashes[j]; memcpy(&M[(i * stride + j) * 4], &v, 4); }
-        }
-    }
-    fpm_ctx *ctx = device();
-    fpm_screen *sc = nullptr;
-    const uint32_t s = (uint32_t)std::max<uint64_t>(1, sketch.parameters.minHashesPerWindow);
-    const int rc = fpm_screen_create(ctx, M.data(), L.data(), stride, (uint32_t)nRef, hb, s, &sc);
-    if (rc == FPM_EINVAL) {
-        std::cerr << "ERROR: " << arguments[0] << ": taxscreen needs sketches whose hashes are in "
-                     "strictly ascending order (" << fpm_last_error() << ")" << std::endl;
-        return 1;
-    }
-    check(rc, "taxscreen");
-    std::vector<uint8_t>().swap(M);
-    uint64_t nDistinct = 0;
-    check(fpm_screen_counts(sc, nullptr, nullptr, &nDistinct), "taxscreen");
-    std::cerr << "   " << nDistinct << " distinct hashes." << std::endl;          // (:201)
-    phaseMark("database table");
-
-    const size_t queryCount = arguments.size() - 1;                               // (:207-219)
-    std::cerr << "Streaming from ";
-    if (queryCount == 1) std::cerr << arguments[1];
-    else std::cerr << queryCount << " inputs";
-    std::cerr << "..." << std::endl;
-
-    Pool pool{ctx, sc, {}};
-    pool.fp.kmer_size = (uint32_t)kmerSize;
-    pool.fp.sketch_size = s;
-    pool.fp.seed = sketch.getHashSeed();
-    pool.fp.use64 = use64;
-    pool.fp.noncanonical = sketch.getNoncanonical();
-    pool.fp.preserve_case = sketch.getPreserveCase();
-    for (int c = 0; c < 256; c++) pool.fp.alphabet[c] = sketch.parameters.alphabet[c] ? 1 : 0;
-
-    // one file image at a time: device and host memory follow the largest file's slices
-    for (size_t f = 1; f < arguments.size(); f++) {
-        std::string image;
-        if (!loadSequenceFile(arguments[f], image)) {
-            std::cerr << "ERROR: could not open " << arguments[f] << std::endl;
-            return 1;
-        }
-        if (!pool.file(image)) {
-            std::cerr << "\nERROR: reading inputs" << std::endl;
-            return 1;
-        }
-    }
-    phaseMark("pool (read + parse + sketch + count)");
-    if (pool.records == 0) {                                                      // (:363-368)
-        std::cerr << "\nERROR: Did not find sequence records in inputs" << std::endl;
-        return 1;
-    }
-    uint64_t setSize = 0;
-    check(fpm_screen_set_size(sc, &setSize), "taxscreen");
-    std::cerr << "   Estimated distinct k-mers in pool: " << setSize << std::endl;   // (:371-376)
-    if (setSize == 0) std::cerr << "WARNING: no valid k-mers in input." << std::endl;
+    if (!db.openTable() || !db.streamPool()) return 1;
+    fpm_screen *sc = db.sc;
 
     std::cerr << "Assigning LCA taxIDs to hashes ..." << std::endl;               // (:378)
     const size_t nNodes = taxdb.ids.size();

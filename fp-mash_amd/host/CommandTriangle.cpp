@@ -7,6 +7,8 @@
 #include "Command.h"
 #include "Device.h"
 #include "Sketch.h"
+#include "SketchRows.h"
+#include "TextOut.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -44,21 +46,6 @@ CommandTriangle::CommandTriangle()
     useSketchOptions();
 }
 
-// containsExtensionMSH / TXT (CommandTriangle.cpp:...): substring test on the last file
-static bool containsSub(const std::vector<std::string> &v, const char *s)
-{
-    bool f = false;
-    for (const auto &x : v) f = x.find(s) != std::string::npos;
-    return f;
-}
-
-static void putNum(std::string &o, double x)   // ostream default: %g, precision 6
-{
-    char t[64];
-    const int n = snprintf(t, sizeof t, "%g", x);
-    o.append(t, n);
-}
-
 int CommandTriangle::run() const
 {
     if (arguments.empty() || options.at("help").active) {
@@ -79,39 +66,20 @@ int CommandTriangle::run() const
     if (sketchParameterSetup(parameters, *this)) return 1;
     if (arguments.size() == 1 && !list) parameters.concatenated = false;
 
-    std::vector<std::string> files;
-    for (const auto &a : arguments) {
-        if (list) splitFile(a, files);
-        else files.push_back(a);
-    }
+    const std::vector<std::string> files = inputFiles(arguments, 0, list);
     Sketch sketch;
     if (fingerprint && containsSub(files, ".msh")) sketch.initFromFiles(files, parameters);
     else if (fingerprint) sketch.initFromFingerprints(files, parameters);
     else sketch.initFromFiles(files, parameters);
 
     const uint64_t n = sketch.getReferenceCount();
-    uint64_t lengthMax = 0;
-    double randomChance = 0;
-    int kMin = 0, warningCount = 0;
-    std::string lengthMaxName;
-    const double lengthThreshold =
-        (parameters.warning * sketch.getKmerSpace()) / (1. - parameters.warning);
-    for (uint64_t i = 0; i < n; i++) {
-        const uint64_t length = sketch.getReference(i).length;
-        if (length > lengthThreshold) {
-            if (warningCount == 0 || length > lengthMax) {
-                lengthMax = length;
-                lengthMaxName = sketch.getReference(i).name;
-                randomChance = sketch.getRandomKmerChance(i);
-                kMin = sketch.getMinKmerSize(i);
-            }
-            warningCount++;
-        }
-    }
+    KmerWarning warning;
+    warning.scan(sketch, parameters);
     auto label = [&](uint64_t i) -> const std::string & {
         return comment ? sketch.getReference(i).comment : sketch.getReference(i).name;
     };
-    std::string out;
+    StdoutText text;
+    std::string &out = text.buf;
     if (!edge) {
         out += '\t';
         out += std::to_string(n);
@@ -120,35 +88,23 @@ int CommandTriangle::run() const
     }
     if (n > 1) {
         // the whole set as one dense matrix; row block [q0, q1) x all refs per device call
-        const bool use64 = sketch.getUse64();
-        const uint32_t hb = use64 ? 8 : 4;
-        uint64_t width = 1;
-        for (uint64_t i = 0; i < n; i++) width = std::max<uint64_t>(width, sketch.getReference(i).hashes.size());
-        std::vector<uint8_t> M(n * width * hb, 0);
-        std::vector<uint32_t> len(n);
-        std::vector<uint64_t> L(n);
-        for (uint64_t i = 0; i < n; i++) {
-            const Reference &r = sketch.getReference(i);
-            len[i] = (uint32_t)r.hashes.size();
-            L[i] = r.length;
-            for (uint64_t j = 0; j < r.hashes.size(); j++) {
-                if (use64) memcpy(&M[(i * width + j) * 8], &r.hashes[j], 8);
-                else { const uint32_t v = (uint32_t)r.hashes[j]; memcpy(&M[(i * width + j) * 4], &v, 4); }
-            }
-        }
+        const PackedRows rows(sketch.references, sketch.getUse64());
+        const uint8_t *M = rows.data();
+        const uint32_t *len = rows.len.data();
+        const uint64_t *L = rows.length.data();
         const uint64_t sketchSize = (uint64_t)sketch.getMinHashesPerWindow();
         std::vector<uint32_t> nu(n * n), de(n * n);
         std::vector<double> di(n * n), pv(n * n);
         std::vector<uint8_t> pa(n * n);
         if (fingerprint)
-            check(fpm_fp_positional_grid(device(), M.data(), len.data(), width, (uint32_t)n,
-                                         M.data(), len.data(), width, (uint32_t)n, hb, distanceMax,
+            check(fpm_fp_positional_grid(device(), M, len, rows.width, (uint32_t)n, M, len,
+                                         rows.width, (uint32_t)n, rows.hashBytes, distanceMax,
                                          pValueMax, nu.data(), de.data(), di.data(), pv.data(),
                                          pa.data()),
                   "triangle");
         else
-            check(fpm_dist(device(), M.data(), len.data(), L.data(), width, (uint32_t)n, M.data(),
-                           len.data(), L.data(), width, (uint32_t)n, hb, (uint32_t)sketchSize,
+            check(fpm_dist(device(), M, len, L, rows.width, (uint32_t)n, M, len, L, rows.width,
+                           (uint32_t)n, rows.hashBytes, (uint32_t)sketchSize,
                            (uint32_t)sketch.getKmerSize(), sketch.getKmerSpace(), distanceMax,
                            pValueMax, nu.data(), de.data(), di.data(), pv.data(), pa.data()),
                   "triangle");
@@ -162,7 +118,7 @@ int CommandTriangle::run() const
                     if (pa[k]) {
                         out += label(i); out += '\t'; out += label(j); out += '\t';
                         putNum(out, di[k]); out += '\t'; putNum(out, pv[k]); out += '\t';
-                        out += std::to_string(nu[k]); out += '/'; out += std::to_string(de[k]);
+                        putU(out, nu[k]); out += '/'; putU(out, de[k]);
                         out += '\n';
                     }
                 } else {
@@ -172,14 +128,12 @@ int CommandTriangle::run() const
                 if (pv[k] > pValuePeak) pValuePeak = pv[k];
             }
             if (!edge) out += '\n';
-            if (out.size() > (1 << 22)) { fwrite(out.data(), 1, out.size(), stdout); out.clear(); }
+            text.flushIfLarge();
         }
     }
-    fwrite(out.data(), 1, out.size(), stdout);
-    fflush(stdout);
+    text.finish();
     if (!edge) std::cerr << "Max p-value: " << pValuePeak << std::endl;
-    if (warningCount > 0 && !parameters.reads)
-        warnKmerSize(parameters, *this, lengthMax, lengthMaxName, randomChance, kMin, warningCount);
+    warning.print(parameters, *this);
     return 0;
 }
 

@@ -1,4 +1,5 @@
 #include "Device.h"
+#include "Sketch.h"
 #include "Timing.h"
 
 #include <atomic>
@@ -116,6 +117,19 @@ void check(int rc, const char *what)
         std::cerr << "ERROR: " << what << ": " << fpm_last_error() << std::endl;
         fatalExit();
     }
+}
+
+fpm_sketch_params sketchParams(const Parameters &p)
+{
+    fpm_sketch_params fp{};
+    fp.kmer_size = (uint32_t)p.kmerSize;
+    fp.sketch_size = (uint32_t)p.minHashesPerWindow;
+    fp.seed = p.seed;
+    fp.use64 = p.use64;
+    fp.noncanonical = p.noncanonical;
+    fp.preserve_case = p.preserveCase;
+    for (int c = 0; c < 256; c++) fp.alphabet[c] = p.alphabet[c] ? 1 : 0;
+    return fp;
 }
 
 int deviceCount()

@@ -23,5 +23,8 @@ void check(int rc, const char *what);
 [[noreturn]] void fatalExit();
 // fatalExit first cuts file `fd` back to `at` bytes (an output sized ahead of its text)
 void fatalCutsOutput(int fd, off_t at);
+// the host's Parameters as the C ABI takes them
+struct Parameters;
+fpm_sketch_params sketchParams(const Parameters &p);
 
 }  // namespace fpmhost

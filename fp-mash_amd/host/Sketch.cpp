@@ -374,14 +374,7 @@ static void sketchFiles(fpm_ctx *ctx, const Parameters &parameters,
     }
 
     if (nGroups) {
-        fpm_sketch_params fp{};
-        fp.kmer_size = (uint32_t)parameters.kmerSize;
-        fp.sketch_size = (uint32_t)parameters.minHashesPerWindow;
-        fp.seed = parameters.seed;
-        fp.use64 = parameters.use64;
-        fp.noncanonical = parameters.noncanonical;
-        fp.preserve_case = parameters.preserveCase;
-        for (int c = 0; c < 256; c++) fp.alphabet[c] = parameters.alphabet[c] ? 1 : 0;
+        const fpm_sketch_params fp = sketchParams(parameters);
         const uint64_t s = fp.sketch_size;
         // the output rows' pages (80 MB for C2: ~4 ms of page allocation and zeroing) are
         // populated on a thread beside the staging and the sketch kernels

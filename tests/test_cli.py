@@ -622,6 +622,79 @@ def test_dist_resident_blocks_text_exact(tmp_path, oracle, block_pairs, to_file,
     assert got == exp
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("comment", [False, True])
+def test_dist_lines_at_the_line_buffer(tmp_path, oracle, comment):
+    """The formatter assembles a list line in a 512-byte stack buffer when reference tag +
+    "\\t<query tag>\\t" + 108 (the numbers' room) fit in it, and appends the line piecewise
+    otherwise.  Tags (name, or name:comment with -C) of 201, 201 and 202 bytes: the pair
+    201 + 201 = 402 lands exactly on the limit, 201 + 202 = 403 one byte over, 202 + 202 two."""
+    from fpmash import datagen
+    seqs = datagen.family_dna(1, 3, 2000, sub_rate=(0.01, 0.05), seed=77)
+    tags = ["a" * 200 + "1", "a" * 200 + "2", "b" * 202]
+    if comment:
+        heads = [t[:-11] + " " + t[-10:] for t in tags]      # name:comment is as long as the tag
+    else:
+        heads = [t + " c" for t in tags]
+    (tmp_path / "x.fa").write_bytes(b"".join(b">" + h.encode() + b"\n" + s + b"\n"
+                                             for h, s in zip(heads, seqs)))
+    run(["sketch", "-i", "-o", "x", "x.fa"], cwd=tmp_path)
+    refs = mshfmt.read_msh(str(tmp_path / "x.msh"))["references"]
+    size = [len(r["name"]) + (1 + len(r["comment"]) if comment else 0) for r in refs]
+    assert size == [201, 201, 202]
+    room = [a + b + 2 + 108 for a in size for b in size]
+    assert 512 in room and 513 in room
+    got = run(["dist"] + (["-C"] if comment else []) + ["x.msh", "x.msh"],
+              cwd=tmp_path).stdout.decode().splitlines()
+    assert got == _oracle_dist_lines(oracle, refs, refs, 1000, 21, 4.0 ** 21, comment=comment)
+
+
+def _u32_sketch(tmp_path, oracle, k=12):
+    """`sketch -i -k 12 -s 400` of 8 short records, one with fewer k-mers than s (as
+    test_sketch_then_dist_u32_hashes builds it): names, lengths and the oracle's u32 rows"""
+    from fpmash import datagen
+    seqs = datagen.family_dna(2, 4, 1500, sub_rate=(0.0, 0.08), seed=40 + k)
+    seqs[5] = seqs[2][:200]
+    ids = datagen.lyn2vec_ids(len(seqs), seed=k)
+    (tmp_path / "u.fa").write_bytes(datagen.fasta_bytes(seqs, ids))
+    run(["sketch", "-i", "-k", str(k), "-s", "400", "-o", "u", "u.fa"], cwd=tmp_path)
+    got = mshfmt.read_msh(str(tmp_path / "u.msh"))["references"]
+    rows = [h.astype(np.uint32) for h in oracle.sketch_batch(oracle.params(k=k, s=400), seqs)]
+    assert [len(h) < 400 for h in rows] == [i == 5 for i in range(8)]
+    for r, h in zip(got, rows):
+        assert r["hashes64"] is None or len(r["hashes64"]) == 0
+        assert np.array_equal(r["hashes32"], h)
+    return [r["name"].decode() for r in got], [len(s) for s in seqs], rows
+
+
+@pytest.mark.gpu
+def test_triangle_edges_u32_hashes(tmp_path, oracle):
+    """`triangle -E` over u32 rows (hash_bytes = 4), one of them short: every line of the
+    lower triangle equals the oracle's grid cell (query i, reference j)."""
+    names, lengths, rows = _u32_sketch(tmp_path, oracle)
+    nu, de, di, pv = oracle.dist_grid(rows, lengths, rows, lengths, 400, 12, 4.0 ** 12, use64=False)
+    assert (nu > 0).any()
+    n = len(names)
+    exp = [f"{names[i]}\t{names[j]}\t{di[o]:g}\t{pv[o]:g}\t{nu[o]}/{de[o]}"
+           for i in range(1, n) for j in range(i) for o in [i * n + j]]
+    assert run(["triangle", "-E", "u.msh"], cwd=tmp_path).stdout.decode().splitlines() == exp
+
+
+@pytest.mark.gpu
+def test_contain_u32_hashes(tmp_path, oracle):
+    """`contain -e 1` over u32 rows, the short row's set packed at its own width"""
+    import contain_model
+    names, _, rows = _u32_sketch(tmp_path, oracle)
+    (tmp_path / "short.fa").write_bytes(b">short only\n" + b"ACGTTGCATGGA" * 20 + b"\n")
+    run(["sketch", "-i", "-k", "12", "-s", "400", "-o", "short", "short.fa"], cwd=tmp_path)
+    short = mshfmt.read_msh(str(tmp_path / "short.msh"))["references"]
+    assert len(short) == 1 and 0 < len(short[0]["hashes32"]) < 400
+    for ref, rn, rr in (("u.msh", names, rows), ("short.msh", ["short"], [short[0]["hashes32"]])):
+        got = run(["contain", "-e", "1", ref, "u.msh"], cwd=tmp_path).stdout.decode()
+        assert got == contain_model.lines(rr, rows, rn, names, 1)
+        assert got.count("\n") > 0
+
+
 def _bgzf(data: bytes, block=65280) -> bytes:
     """BGZF (SAM spec 4.1): raw-deflate blocks of <= 64 KiB, each a gzip member whose extra
     field 'BC' holds the member's size - 1, then the 28-byte empty EOF member."""
