@@ -435,6 +435,33 @@ __global__ __launch_bounds__(64 * kRankWaves) void rank_rows_kernel(
     const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t lb = qry_len[q];
     const uint64_t *B = qry + (uint64_t)q * qry_stride;
+    // Batch-in: a wave ranks the row's candidates wave, wave + kRankWaves, ... and takes them
+    // in batches of 64, one candidate per lane: lane l of the batch at b0 owns the wave's
+    // (b0 + l)-th.  Everything that is the same arithmetic for every candidate (the id, the
+    // row's lengths, its address, the exit rank) is loaded and computed once per batch with
+    // vector instructions; the candidate loop reads its lane (v_readlane) and holds no scalar
+    // load.  A lane past the wave's last candidate takes the row's last one (valid loads, no
+    // divergence), and its values are never read.
+    const uint64_t pair_row = (uint64_t)q * n_ref;
+    struct BatchRaw { uint32_t rr, la, lc; };
+    // the ids' low dwords (the row index is o - pair_row, below 2^32)
+    auto cand_lo = [&](uint32_t b0) -> uint32_t {
+        const uint32_t c = min(wave + (b0 + lane) * (uint32_t)kRankWaves, n - 1);
+        return ((const uint32_t *)cand)[2 * (base + c)];
+    };
+    auto gather_len = [&](uint32_t olo) -> BatchRaw {
+        BatchRaw T;
+        T.rr = olo - (uint32_t)pair_row;
+        T.la = ref_len[T.rr];
+        T.lc = CMP ? cm.len[T.rr] : T.la;
+        return T;
+    };
+    // the wave's candidates; the first batch's loads go out before B's (they depend on
+    // nothing staged here) and land while the directory is built, the second batch's ids too
+    const uint32_t nw = wave < n ? (n - wave + kRankWaves - 1) / kRankWaves : 0;
+    const uint32_t o_first = cand_lo(0);
+    const uint32_t o_second = nw > 64 ? cand_lo(64) : 0u;
+    BatchRaw raw_first;
     if (threadIdx.x == 0) { s_maxn = 0; s_keydup = 0; s_unsorted = 0; }
     {
         // stage B: every load of the row issued before the first LDS store (4 in flight per
@@ -447,6 +474,7 @@ __global__ __launch_bounds__(64 * kRankWaves) void rank_rows_kernel(
             const uint32_t t = threadIdx.x + u * 64 * kRankWaves;
             v[u] = t < lb ? B[t] : 0;
         }
+        raw_first = gather_len(o_first);
 #pragma unroll
         for (int u = 0; u < kStage; u++) {
             const uint32_t t = threadIdx.x + u * 64 * kRankWaves;
@@ -512,7 +540,6 @@ __global__ __launch_bounds__(64 * kRankWaves) void rank_rows_kernel(
                       : maxn <= (uint32_t)kRankProbeMax ? (uint32_t)kRankProbeMax : 0u;
 
     const uint32_t ld = ref_stride < (uint64_t)CAP ? (uint32_t)ref_stride : (uint32_t)CAP;
-    const uint64_t pair_row = (uint64_t)q * n_ref;
     // A rows are read in chunks of 128 values, two 8-B loads per lane (lane l holds A[i0 + l]
     // and A[i0 + 64 + l]: neighbouring lanes then probe neighbouring directory words and keys
     // of B, about half the LDS bank conflicts of one 16-B load of A[i0 + 2l], A[i0 + 2l + 1]
@@ -527,21 +554,35 @@ __global__ __launch_bounds__(64 * kRankWaves) void rank_rows_kernel(
     // CMP: the row's block of the compacted rows, values then positions, under one descriptor
     // (the positions of chunk t: one dword per lane at byte ld * 8 + (64 t + lane) * 4, the
     // block's own stride being ref_stride = ld); lc = the entries to stream, none on the diagonal
-    struct Row { __amdgpu_buffer_rsrc_t rsrc; uint32_t la, lc; uint64_t o; };
+    // A batch as the candidate loop reads it, one candidate per lane: the row's index and
+    // address, its length la, the entries to stream lc and the union rank that ends the
+    // candidate (S, or none where denom depends on #shared: need_all).
+    // (la, at most 2048, rides in the 16 bits above the 48-bit address: the descriptor's
+    // second word is masked to the address bits anyway)
+    struct Batch { uint32_t rr, alo, ahi_la, lc, sx; };
+    struct Row { __amdgpu_buffer_rsrc_t rsrc; uint32_t lc, sx; };
     const uint32_t row_bytes = CMP ? (uint32_t)cmp_row_bytes(ref_stride) : ld * 8u;
-    auto open_row = [&](uint64_t o) -> Row {
-        const uint32_t rr = __builtin_amdgcn_readfirstlane((uint32_t)(o - pair_row));
-        const uintptr_t Ar = CMP ? (uintptr_t)cm.rows + (uint64_t)rr * row_bytes
-                                 : (uintptr_t)(ref + (uint64_t)rr * ref_stride);
-        const uint32_t plo = __builtin_amdgcn_readfirstlane((uint32_t)Ar);
-        const uint32_t phi = __builtin_amdgcn_readfirstlane((uint32_t)(Ar >> 32));
+    auto make_batch = [&](const BatchRaw &W) -> Batch {
+        const uintptr_t Ar = CMP ? (uintptr_t)cm.rows + (uint64_t)W.rr * row_bytes
+                                 : (uintptr_t)(ref + (uint64_t)W.rr * ref_stride);
+        Batch T;
+        T.rr = W.rr;
+        T.alo = (uint32_t)Ar;
+        T.ahi_la = ((uint32_t)(Ar >> 32) & 0xFFFFu) | (W.la << 16);
+        T.lc = CMP ? (W.rr == q ? 0u : W.lc) : W.la;
+        T.sx = (W.la < S && lb < S) ? 0xFFFFFFFFu : S;
+        return T;
+    };
+    // the k-th candidate of a batch: its lane's values, the descriptor assembled from them
+    auto open_row = [&](const Batch &T, uint32_t k) -> Row {
+        const uint32_t plo = (uint32_t)__builtin_amdgcn_readlane((int)T.alo, (int)k);
+        const uint32_t phi = (uint32_t)__builtin_amdgcn_readlane((int)T.ahi_la, (int)k) & 0xFFFFu;
         Row R;
         R.rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(((uintptr_t)phi << 32) | plo), 0,
                                                    (int)__builtin_amdgcn_readfirstlane(row_bytes),
                                                    0x00020000);
-        R.la = ref_len[rr];
-        R.lc = CMP ? (rr == q ? 0u : cm.len[rr]) : R.la;
-        R.o = o;
+        R.lc = (uint32_t)__builtin_amdgcn_readlane((int)T.lc, (int)k);
+        R.sx = (uint32_t)__builtin_amdgcn_readlane((int)T.sx, (int)k);
         return R;
     };
     struct PairV { uint64_t e0, e1; };
@@ -560,9 +601,6 @@ __global__ __launch_bounds__(64 * kRankWaves) void rank_rows_kernel(
                 dst[u].pp = __builtin_amdgcn_raw_buffer_load_b32(R.rsrc, (t * 64 + lane) * 4u,
                                                                  (int)(ld * 8u), 0);
         }
-    };
-    auto cand_at = [&](uint32_t cc) -> uint64_t {
-        return cand[base + __builtin_amdgcn_readfirstlane(cc)];
     };
     // one chunk (kGroup = 1): shared-hash count below the union rank S (cnt), shared values
     // so far (shared_below); returns the union rank of the chunk's largest value (full chunks)
@@ -613,34 +651,59 @@ __global__ __launch_bounds__(64 * kRankWaves) void rank_rows_kernel(
         shared_below += p0 + p1;
         return u_last;
     };
+    // Batch-out: the finished candidate's count and shared total go into its lane of one
+    // result register (both are at most the row length, 16 bits each); the owning lanes
+    // compute denom and store the batch with vector stores.
+    auto flush = [&](const Batch &T, uint32_t res, uint32_t b0, uint32_t nb) {
+        if (b0 + lane < nw) {
+            uint32_t cnt = res & 0xFFFFu, shared = res >> 16;
+            if constexpr (CMP) {
+                // the diagonal (nothing streamed: lc = 0): every value is shared
+                if (T.rr == q) { shared = lb; cnt = lb < S ? lb : S; }
+            }
+            const uint32_t la = T.ahi_la >> 16;
+            const bool need_all = la < S && lb < S;       // denom depends on #shared
+            const uint64_t un = (uint64_t)la + lb - shared;
+            const uint32_t dn = need_all ? (un < S ? (uint32_t)un : S) : S;
+            if (cnum) {          // compact: the candidate finalize scatters (and mirrors)
+                // (through descriptors made here, bounded to the batch's entries: as plain
+                // stores the lanes' addresses are hoisted out of the batch loop, four registers
+                // held through the candidate loop)
+                const uint64_t c0 = base + wave + (uint64_t)b0 * kRankWaves;
+                const int bytes = (int)((nb - 1) * kRankWaves * 4u + 4u);
+                const auto rn = __builtin_amdgcn_make_buffer_rsrc((void *)(cnum + c0), 0, bytes,
+                                                                  0x00020000);
+                const auto rd = __builtin_amdgcn_make_buffer_rsrc((void *)(cden + c0), 0, bytes,
+                                                                  0x00020000);
+                __builtin_amdgcn_raw_buffer_store_b32(cnt, rn, lane * (kRankWaves * 4u), 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(dn, rd, lane * (kRankWaves * 4u), 0, 0);
+            } else {
+                const uint64_t o = pair_row + T.rr;
+                numer[o] = (C)cnt;
+                denom[o] = (C)dn;
+                if (sym && T.rr != q) {                   // mirror cell (r, q)
+                    const uint64_t o2 = (uint64_t)T.rr * n_ref + q;
+                    numer[o2] = (C)cnt;
+                    denom[o2] = (C)dn;
+                }
+            }
+        }
+    };
+    // the wave's first batch (loaded above)
+    const Batch first = make_batch(raw_first);
     auto run = [&](auto probe, bool fast) {
         Pair cur[kGroup], nxt[kGroup], pf[kGroup];
-        Row Rc{};
-        if (wave < n) { Rc = open_row(cand_at(wave)); load_group(Rc, 0, pf); }
-        for (uint32_t c = wave; c < n; c += kRankWaves) {
-            const Row R = Rc;
-#pragma unroll
-            for (int u = 0; u < kGroup; u++) cur[u] = pf[u];
-            if (c + kRankWaves < n) { Rc = open_row(cand_at(c + kRankWaves)); load_group(Rc, 0, pf); }
-            const uint32_t la = R.la;
-            const uint64_t o = R.o;
-            const bool need_all = la < S && lb < S;       // denom depends on #shared
+        // one candidate: the chunk `cur` in registers, the rest of row R streamed -> its count
+        // and shared total, packed
+        auto rank_one = [&](const Row &R) -> uint32_t {
             const uint32_t ls = R.lc;                     // the entries streamed
             const uint32_t nch = (ls + kChunk - 1) / kChunk;
             const uint32_t ngr = (nch + kGroup - 1) / kGroup;
             static_assert(kGroup == 1, "the last-chunk masks assume one chunk per group");
-            // values past la (row padding) count nothing: in the last chunk (lane l holds
-            // A[i0 + l], A[i0 + 64 + l]) the lanes below r0 / r1 hold row values.  Computed once
-            // per candidate, selected per chunk (computed in the chunk loop they cost ~20 scalar
-            // instructions per chunk: the compiler turns a branch around them into selects)
-            const int rl = (int)ls - (int)(nch - 1) * (int)kChunk;          // 1 .. 128
-            const int r0 = min(rl, 64), r1 = rl - 64;
-            const uint64_t vl0 = r0 >= 64 ? ~0ULL : r0 > 0 ? (1ULL << r0) - 1 : 0ULL;
-            const uint64_t vl1 = r1 >= 64 ? ~0ULL : r1 > 0 ? (1ULL << r1) - 1 : 0ULL;
             uint32_t shared_below = 0, cnt = 0;
             // the early exit: after a chunk whose last value's union rank reaches S no later
             // value can count (need_all: the denom needs every shared value, no exit)
-            const uint32_t s_exit = need_all ? 0xFFFFFFFFu : S;
+            const uint32_t s_exit = R.sx;
             // the full chunks, then the row's last chunk with its masks (peeled: the loop
             // carries no per-chunk mask selects).  (Chunks loaded two ahead instead of one:
             // 0.345 -> 0.375 ms.)
@@ -655,32 +718,50 @@ __global__ __launch_bounds__(64 * kRankWaves) void rank_rows_kernel(
                 for (int u = 0; u < kGroup; u++) cur[u] = nxt[u];
             }
             if (!exited && ngr) {
+                // values past ls (row padding) count nothing: in the last chunk lane l holds
+                // A[i0 + l], A[i0 + 64 + l], row values where that index is below ls (two
+                // vector compares; as scalar shifts and selects per candidate the masks cost a
+                // dozen scalar instructions)
+                const uint32_t i0 = gi * kChunk + lane;
+                const uint64_t vl0 = __builtin_amdgcn_ballot_w64(i0 < ls);
+                const uint64_t vl1 = __builtin_amdgcn_ballot_w64(i0 + 64 < ls);
                 // fast-path rows: B holds no ~0 value (its key would equal the sentinel's), and
                 // an A value ~0 (only ever A's last) would match the sentinel: not shared
                 const uint64_t x0 = fast ? __builtin_amdgcn_ballot_w64(cur[0].e0 == ~0ULL) : 0;
                 const uint64_t x1 = fast ? __builtin_amdgcn_ballot_w64(cur[0].e1 == ~0ULL) : 0;
                 rank_group(probe, gi * kGroup, true, vl0 & ~x0, vl1 & ~x1, cur, shared_below, cnt);
             }
-            if constexpr (CMP) {
-                // the diagonal (nothing streamed: lc = 0): every value is shared
-                if ((uint32_t)(o - pair_row) == q) { shared_below = lb; cnt = lb < S ? lb : S; }
+            return cnt | (shared_below << 16);
+        };
+        Batch T = first;
+        uint32_t o_next = o_second;
+        Row Rc{};
+        if (nw) { Rc = open_row(T, 0); load_group(Rc, 0, pf); }
+        for (uint32_t b0 = 0; b0 < nw; b0 += 64) {
+            const uint32_t nb = min(nw - b0, 64u);
+            const bool more = nw - b0 > 64;
+            // the next batch's lengths are gathered now, from the ids loaded a batch ago (the
+            // ids of the batch after it at this batch's end): nothing of a batch's set-up waits
+            // on memory at the batch edge, and the candidate loop carries none of it
+            BatchRaw raw_next{};
+            if (more) raw_next = gather_len(o_next);
+            // a finished candidate's result goes into its lane (a vector select: this
+            // toolchain has no writelane builtin)
+            uint32_t res = 0;
+            for (uint32_t k = 0; k < nb; k++) {
+                const Row R = Rc;
+#pragma unroll
+                for (int u = 0; u < kGroup; u++) cur[u] = pf[u];
+                if (k + 1 < nb) { Rc = open_row(T, k + 1); load_group(Rc, 0, pf); }
+                const uint32_t v = rank_one(R);
+                res = lane == k ? v : res;
             }
-            if (lane == 0) {
-                const uint64_t un = (uint64_t)la + lb - shared_below;
-                const uint32_t dn = need_all ? (un < S ? (uint32_t)un : S) : S;
-                if (cnum) {      // compact: the candidate finalize scatters (and mirrors)
-                    cnum[base + c] = cnt;
-                    cden[base + c] = dn;
-                    continue;
-                }
-                numer[o] = (C)cnt;
-                denom[o] = (C)dn;
-                const uint32_t r = (uint32_t)(o - pair_row);
-                if (sym && r != q) {                      // mirror cell (r, q)
-                    const uint64_t o2 = (uint64_t)r * n_ref + q;
-                    numer[o2] = (C)cnt;
-                    denom[o2] = (C)dn;
-                }
+            flush(T, res, b0, nb);
+            if (more) {
+                T = make_batch(raw_next);
+                Rc = open_row(T, 0);
+                load_group(Rc, 0, pf);
+                if (nw - b0 > 128) o_next = cand_lo(b0 + 128);
             }
         }
     };

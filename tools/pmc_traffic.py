@@ -141,7 +141,13 @@ def main():
     ap.add_argument("--leg", choices=["c2", "c3", "c4", "c5"], default="c2",
                     help="c2: the bench step, kernels grouped as bench.py reports them; "
                          "c3 / c4 / c5: tools/leg_run.py --leg, per kernel, with durations")
+    ap.add_argument("--passes", default="fetch,write,sq,l2",
+                    help="the counter passes to run (a same-visit A/B of instruction counts "
+                         "needs `sq` alone: one bench run per build instead of four)")
     a = ap.parse_args()
+    passes = set(a.passes.split(","))
+    if a.leg != "c2" and passes != {"fetch", "write", "sq", "l2"}:
+        ap.error("--passes selects passes of the c2 leg only")
     a.work = a.work + ("" if a.leg == "c2" else "_" + a.leg)
     os.makedirs(a.work, exist_ok=True)
     if a.leg == "c2":
@@ -157,32 +163,40 @@ def main():
             # five passes regenerates the genomes on the host)
             bench_args += ["--c5-genomes", "250"]
         GROUP_BY["fn"] = kernel_key
-    fetch = run_pass("FETCH_SIZE", os.path.join(a.work, "fetch"), bench_args)
-    write = run_pass("WRITE_SIZE", os.path.join(a.work, "write"), bench_args)
-    # one "launch" of a group that is several kernels (the index build) is one step's worth
-    launches = dict(LAUNCHES)
+    fetch = run_pass("FETCH_SIZE", os.path.join(a.work, "fetch"), bench_args) \
+        if "fetch" in passes else {}
+    write = run_pass("WRITE_SIZE", os.path.join(a.work, "write"), bench_args) \
+        if "write" in passes else {}
     sq = run_pass(("SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_LDS", "SQ_WAVE_CYCLES",
                    "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_ANY"),
-                  os.path.join(a.work, "sq"), bench_args)
+                  os.path.join(a.work, "sq"), bench_args) if "sq" in passes else {}
+    # one "launch" of a group that is several kernels (the index build) is one step's worth
+    launches = dict(LAUNCHES)
     sqk = {c: per_launch(v, launches) for c, v in sq.items()}
     # fourth pass: L2 hit / miss requests and LDS bank-conflict cycles
     l2 = run_pass(("SQ_LDS_BANK_CONFLICT", "TCC_HIT_sum", "TCC_MISS_sum"),
-                  os.path.join(a.work, "l2"), bench_args)
+                  os.path.join(a.work, "l2"), bench_args) if "l2" in passes else {}
     l2k = {c: per_launch(v, launches) for c, v in l2.items()}
     f = per_launch(fetch, launches)
     w = per_launch(write, launches)
     res = {}
-    for g in sorted(set(f) | set(w)):
-        fb = 2.0 * f.get(g, 0.0)          # gfx950: FETCH_SIZE = half the streamed bytes
-        wb = w.get(g, 0.0)
-        res[g] = {"fetch_bytes": fb, "write_bytes": wb, "traffic_bytes": fb + wb}
-        # SQ counters per launch (per_launch scales by 1024: undo); wave-state split
-        sqg = {c.replace("SQ_", "").lower(): v.get(g, 0.0) / 1024.0 for c, v in sqk.items()}
-        wc = sqg.get("wave_cycles") or 1.0
-        res[g]["sq"] = sqg
-        res[g]["wave_state_frac"] = {"active": sqg.get("active_inst_any", 0) / wc,
-                                     "issue_stall": sqg.get("wait_inst_any", 0) / wc,
-                                     "waiting": sqg.get("wait_any", 0) / wc}
+    for g in sorted(set(f) | set(w) | {g for v in (*sqk.values(), *l2k.values()) for g in v}):
+        # (a pass that did not run leaves its keys out: no zeros that read as measured)
+        res[g] = {}
+        if {"fetch", "write"} <= passes:
+            fb = 2.0 * f.get(g, 0.0)      # gfx950: FETCH_SIZE = half the streamed bytes
+            wb = w.get(g, 0.0)
+            res[g] = {"fetch_bytes": fb, "write_bytes": wb, "traffic_bytes": fb + wb}
+        if "sq" in passes:
+            # SQ counters per launch (per_launch scales by 1024: undo); wave-state split
+            sqg = {c.replace("SQ_", "").lower(): v.get(g, 0.0) / 1024.0 for c, v in sqk.items()}
+            wc = sqg.get("wave_cycles") or 1.0
+            res[g]["sq"] = sqg
+            res[g]["wave_state_frac"] = {"active": sqg.get("active_inst_any", 0) / wc,
+                                         "issue_stall": sqg.get("wait_inst_any", 0) / wc,
+                                         "waiting": sqg.get("wait_any", 0) / wc}
+        if "l2" not in passes:
+            continue
         hit = l2k.get("TCC_HIT_sum", {}).get(g, 0.0) / 1024.0
         miss = l2k.get("TCC_MISS_sum", {}).get(g, 0.0) / 1024.0
         res[g]["l2"] = {"hit_req": hit, "miss_req": miss,
@@ -219,6 +233,7 @@ def main():
                   "L2 (TCC) hit / miss requests and LDS bank-conflict cycles; side legs add a "
                   "--kernel-trace --stats pass for each kernel's average launch time, the "
                   "achieved traffic rate and the VALU-issue fraction",
+        "passes": sorted(passes),
         "kernels": res,
     }
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
