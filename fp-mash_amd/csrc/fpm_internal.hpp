@@ -384,9 +384,22 @@ struct StageRecords {
                                         // wide jobs over the staged job's buffer)
 };
 
-// fpm_sketch_api.cpp: the staging behind fpm_sketch_stage and fpm_sketch_stage_seq
+// fpm_sketch_api.cpp: the staging behind fpm_sketch_stage and fpm_sketch_stage_seq (pack,
+// plan_sketch of sketch_plan.hpp, allocate and upload)
 FPM_HIDDEN int stage_core(fpm_ctx *ctx, const fpm_sketch_params *p, StageRecords &R,
                           fpm_sketch_job **job_out);
+
+// fn(c, begin, n) for each tile class c that has tiles, class_begin[c] .. class_begin[c + 1] of a
+// tile array ordered by class; stops at the first status that is not FPM_OK and returns it
+template <typename Fn> int for_each_class(const uint32_t *class_begin, Fn fn)
+{
+    for (int c = 0; c < kTileClasses; c++) {
+        const uint32_t b = class_begin[c], n = class_begin[c + 1] - b;
+        if (!n) continue;
+        if (int rc = fn(c, b, n)) return rc;
+    }
+    return FPM_OK;
+}
 
 // fpm_text_api.cpp: the records of a device parse for a job that adopts them (fpm_kfinger_stage_seq):
 // each record's offset and length in the packed buffer, and the buffer itself, which leaves the

@@ -113,12 +113,14 @@ hipError_t launch_sketch_short(const uint32_t *d_slot_group, uint32_t n_slots,
                                const uint32_t *d_count, uint32_t s, uint64_t *d_thr,
                                const uint64_t *d_thr_safe, uint32_t *d_n_short,
                                uint32_t *d_short_slots, bool raise, hipStream_t st);
-uint32_t merge_small_cap();   // list length merge_small_kernel stages in LDS
+// list length merge_small_kernel stages in LDS (kSCap, sketch.hip)
+constexpr uint32_t kMergeSmallCap = 2048;
 // one long group's sketch selected from its bounded tile lists (rows row_ids[row_begin ..
 // row_begin + n_rows)) into out_row; slot: its bound thr[slot] (0xFFFFFFFF: none, the
 // sample pass of long groups)
 struct SelDesc { uint32_t row_begin, n_rows, out_row, slot; };
-uint32_t group_select_cap();   // keys one selection stages in LDS (sketch sizes up to ~0.85 x)
+// keys one selection stages in LDS (kSelCap, sketch.hip; sketch sizes up to ~0.85 x)
+constexpr uint32_t kGroupSelectCap = 15360;
 // *failed |= 1 when a group's keys below the cut do not fit (the caller merges instead)
 hipError_t launch_group_select(const SelDesc *d_desc, uint32_t n, const uint32_t *d_row_ids,
                                uint64_t *d_rows, uint32_t *d_count, uint32_t s,

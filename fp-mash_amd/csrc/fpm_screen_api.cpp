@@ -221,14 +221,12 @@ int fpm_screen_add_job(fpm_screen *sc, fpm_sketch_job *job, void *stream)
         return rc;
     HIP_TRY(hipMemcpyAsync(sc->d_pair, sc->d_pair + 2 * (size_t)sc->s, rb, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(sc->d_pcnt, sc->d_pcnt + 2, 4, hipMemcpyDeviceToDevice, st));
-    for (int c = 0; c < kTileClasses; c++) {
-        const uint32_t b = v.class_begin[c], n = v.class_begin[c + 1] - b;
-        if (!n) continue;
+    return for_each_class(v.class_begin, [&](int c, uint32_t b, uint32_t n) -> int {
         TimedLaunch tl(ctx, FPM_K_SCREEN, st);
         HIP_TRY(launch_screen_count(c, v.d_seq, v.d_tiles + b, n, v.kp, sc->tab, st));
         tl.done();
-    }
-    return FPM_OK;
+        return FPM_OK;
+    });
 }
 
 int fpm_screen_add_hashes_dev(fpm_screen *sc, const uint64_t *d_keys, uint64_t n, void *stream)

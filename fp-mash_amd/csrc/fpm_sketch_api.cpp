@@ -1,10 +1,9 @@
 // fpm_sketch_api.cpp — the sketch part of the C ABI declared in include/fpmash.h: host-side
-// staging (record packing, tile plan, merge schedule), the run and its redo / fallback
-// passes, the device min-merge and the -M pass, over the kernels in sketch.hip.
+// staging (record packing, the plan of sketch_plan.cpp, its upload), the run and its redo /
+// fallback passes, the device min-merge and the -M pass, over the kernels in sketch.hip.
 #include "fpm_internal.hpp"
+#include "sketch_plan.hpp"
 
-#include <array>
-#include <cmath>
 #include <cstdlib>
 
 namespace {
@@ -12,23 +11,9 @@ namespace {
 // Reference complement table for 'A'..'Z' (Sketch.cpp:1223-1250); other bytes 'N'.
 const char kComplAZ[26] = {'T', 'V', 'G', 'H', 'N', 'N', 'C', 'D', 'N', 'N', 'M', 'N', 'K',
                            'N', 'N', 'N', 'N', 'Y', 'S', 'A', 'A', 'B', 'W', 'N', 'R', 'N'};
-
-// Tile sizing: small records are packed up to kPackKmers k-mer starts per tile,
-// long records are cut into kChunkKmers-start chunks (k-1 bytes of halo).
-constexpr uint32_t kPackKmers = 2048;
-// (2048-start chunks: the tile kernel 1.3 ms faster on C5, the group selection 1.3 ms slower)
-constexpr uint32_t kChunkKmers = 4096;
-
-int tile_class(uint32_t nstarts)
-{
-    for (int c = 0; c < kTileClasses; c++)
-        if (nstarts <= kTileCap[c]) return c;
-    return -1;
-}
-
 }  // namespace
 
-// merge rounds whose estimated input lists are at most merge_small_cap() long use
+// merge rounds whose estimated input lists are at most kMergeSmallCap long use
 // merge_small_kernel; FPM_MERGE_SMALL=0 turns it off (A/B), =2 uses it for every round
 // (tests: its global-memory search past the LDS cap)
 static const int g_merge_small_env = [] {
@@ -36,83 +21,64 @@ static const int g_merge_small_env = [] {
     return v ? atoi(v) : 1;
 }();
 
+// whether round r of a schedule runs through merge_small_kernel
+static bool round_is_small(const MergeSchedule &m, size_t r)
+{
+    return g_merge_small_env == 2 ||
+           (g_merge_small_env != 0 && r < m.round_small.size() && m.round_small[r]);
+}
+
 // ----------------------------------------------------------------------------
 // Sketch job: packing + tile plan + merge schedule
 // ----------------------------------------------------------------------------
 // Rows of one device matrix d_rows[n_rows][s]: rows [0, n_groups) are the final
 // sketches, rows >= n_groups hold per-tile / intermediate lists of groups whose
-// records span several tiles; those are reduced by pairwise merge rounds.
+// records span several tiles; those are reduced by selections and pairwise merge rounds
+// (sketch_plan.hpp states which row is whose).
 
 struct fpm_sketch_job {
     fpm_ctx *ctx = nullptr;
     SketchKParams kp{};
-    uint32_t n_groups = 0;
-    uint32_t n_rows = 0;
+    SketchPlan plan;               // what the device buffers below were filled from
     uint64_t seq_bytes = 0;
-    uint64_t n_kmers = 0;
-    uint64_t n_tiles = 0;
     uint8_t *d_seq = nullptr;
-    TileDesc *d_tiles = nullptr;
+    TileDesc *d_tiles = nullptr;   // plan.tiles
     uint64_t *d_rows = nullptr;
     uint32_t *d_count = nullptr;
-    MergeDesc *d_merge = nullptr;
-    uint32_t class_begin[kTileClasses + 1] = {0};
-    std::vector<uint32_t> round_begin;
-    std::vector<uint8_t> round_small, sround_small;   // per round: merge_small_kernel
-    // long groups: a 1-in-kSampleEvery sample of their tiles is sketched first; its s-th
-    // smallest hash bounds what every tile of the group keeps
-    uint32_t n_slots = 0;
+    MergeDesc *d_merge = nullptr;  // plan.merge
+    // long groups' sample pass: plan.stiles, plan.smerge, plan.srow; d_thr: the groups' bounds
+    // (main pass), then the samples' a-priori bounds
     TileDesc *d_stiles = nullptr;
     MergeDesc *d_smerge = nullptr;
     uint32_t *d_srow = nullptr;
     uint64_t *d_thr = nullptr;
-    uint32_t sclass_begin[kTileClasses + 1] = {0};
-    std::vector<uint32_t> sround_begin;
-    // sampled groups: one-workgroup selection from their bounded tile lists
-    // (group_select_kernel); a pairwise merge plan of the same lists is kept as the fallback
-    // for groups whose keys below the cut do not fit in LDS
-    uint32_t n_sel = 0;
+    // sampled groups' selections (plan.sel, plan.sel_rows); the fallback merges of plan.fmerge /
+    // plan.sfmerge for groups whose keys below the cut do not fit in LDS, their descriptors and
+    // rows (>= plan.n_rows: d_fb_rows) allocated on first use
     SelDesc *d_sel = nullptr;
     uint32_t *d_sel_rows = nullptr, *d_sel_failed = nullptr, *h_sel_failed = nullptr;
-    MergeDesc *d_fmerge = nullptr;
-    std::vector<uint32_t> fround_begin;
-    std::vector<uint8_t> fround_small;
-    uint32_t n_ssel = 0;                      // sample selections (first n_ssel of d_sel)
-    std::vector<uint32_t> ssel_begin, sel_begin;   // d_sel offsets of each level
-    // fallback merge plans (rows >= n_rows live in d_fb_rows, allocated on first use)
-    std::vector<std::array<uint32_t, 3>> fplan, sfplan;
-    uint32_t n_fb_rows = 0;
+    MergeDesc *d_fmerge = nullptr, *d_sfmerge = nullptr;
     uint64_t *d_fb_rows = nullptr;
     uint32_t *d_fb_count = nullptr;
-    MergeDesc *d_sfmerge = nullptr;
-    std::vector<uint32_t> sfround_begin;
-    std::vector<uint8_t> sfround_small;
-    // class-4 tiles all bounded (C5's genomes): the survivors-only tile kernel, whose
-    // overflowing tiles (d_redo, count d_redo_n) run again through the plain one
-    bool thr4 = false;
+    // plan.thr4: the survivors-only tile kernel, whose overflowing tiles (d_redo, count
+    // d_redo_n) run again through the plain one
     TileDesc *d_redo = nullptr;
     uint32_t *d_redo_n = nullptr;
-    uint32_t n4 = 0;                 // class-4 tiles (the redo list's capacity)
-    // tight bounds (groups with a selection): each slot's bound is the sample's kt-th smallest
-    // hash instead of its s-th (d_kt), the s-th kept as d_thr_safe; a group left with fewer
-    // than s hashes (sketch_short_kernel: d_short = count, then the slots) is redone with the
-    // safe bound: its tiles and selections again, from the host copies below
-    bool tight = false;
+    // plan.tight: each slot's bound is the sample's kt-th smallest hash instead of its s-th
+    // (d_kt), the s-th kept as d_thr_safe; a group left with fewer than s hashes
+    // (sketch_short_kernel: d_short = count, then the slots) is redone with the safe bound: its
+    // tiles and selections again, from the plan
     uint32_t *d_kt = nullptr, *d_slot_group = nullptr, *d_short = nullptr;
     uint64_t *d_thr_safe = nullptr;
-    std::vector<TileDesc> h_tiles;          // the main tiles by class (class_begin)
-    std::vector<SelDesc> h_sel;             // the selections (sample levels, then main)
     TileDesc *d_rtiles = nullptr;           // the redo's subsets (allocated on first use)
     SelDesc *d_rsel = nullptr;
     int32_t last_short = -1;                // groups redone by the last run (-1: no tight bounds)
-    // a-priori sample bounds (d_thr[n_slots ..]): a sample left short is redone unbounded
-    bool sbounded = false;
+    // plan.sbounded (a-priori sample bounds, d_thr[n_slots ..]): a sample left short is redone
+    // unbounded
     uint32_t *d_sshort = nullptr;           // count, then the slots
     uint64_t *d_sbound0 = nullptr;          // the a-priori sample bounds as staged: restored
                                             // into d_thr at every run (a short sample's redo
                                             // lifts its bound in d_thr)
-    std::vector<TileDesc> h_stiles;         // the sample tiles by class (sclass_begin)
-    std::vector<uint32_t> h_ssel_tag;       // each sample selection's slot
     int32_t last_sample_short = -1;
     // -M pass (allocated on first use)
     uint32_t *d_mult = nullptr;
@@ -142,8 +108,8 @@ static void job_release(fpm_sketch_job *j)
 
 void job_view(const fpm_sketch_job *j, JobView *out)
 {
-    *out = JobView{j->ctx, j->kp, j->n_groups, j->d_seq, j->d_tiles, j->class_begin, j->d_rows,
-                   j->d_count};
+    *out = JobView{j->ctx, j->kp, j->plan.n_groups, j->d_seq, j->d_tiles, j->plan.class_begin,
+                   j->d_rows, j->d_count};
 }
 
 extern "C" {
@@ -183,16 +149,10 @@ int fpm_sketch_stage(fpm_ctx *ctx, const fpm_sketch_params *p, const char *seq,
 
 }  // extern "C"
 
-int stage_core(fpm_ctx *ctx, const fpm_sketch_params *p, StageRecords &R,
-               fpm_sketch_job **job_out)
+static SketchKParams kernel_params(const fpm_sketch_params *p)
 {
-    if (p->kmer_size < 1 || p->kmer_size > 32) return fail(FPM_EINVAL, "kmer_size must be 1..32");
-    if (p->sketch_size < 1) return fail(FPM_EINVAL, "sketch_size must be >= 1");
-    const uint32_t k = p->kmer_size, s = p->sketch_size;
-    const uint32_t n_groups = R.n_groups;
-    const std::vector<uint32_t> &order = R.order;
     SketchKParams kp{};
-    kp.k = k; kp.s = s; kp.seed = p->seed; kp.use64 = p->use64 ? 1 : 0;
+    kp.k = p->kmer_size; kp.s = p->sketch_size; kp.seed = p->seed; kp.use64 = p->use64 ? 1 : 0;
     kp.canonical = p->noncanonical ? 0 : 1; kp.preserve_case = p->preserve_case ? 1 : 0;
     for (int c = 0; c < 256; c++) {
         kp.alphabet[c] = p->alphabet[c] ? 1 : 0;
@@ -202,464 +162,151 @@ int stage_core(fpm_ctx *ctx, const fpm_sketch_params *p, StageRecords &R,
     kp.compl_acgt = 1;
     for (int c = 0; c < 256; c++)
         if (kp.alphabet[c] && c != 'A' && c != 'C' && c != 'G' && c != 'T') kp.compl_acgt = 0;
+    return kp;
+}
 
-    // host path: pack records >= k (each followed by 0x00) in group order
-    std::vector<uint8_t> packed;
-    if (R.host_seq) {
-        uint64_t total = 0;
-        for (uint32_t r : order)
-            if (R.len[r] >= k) total += R.len[r] + 1;
-        packed.resize(total);
-        uint64_t at = 0;
-        for (uint32_t r : order) {
-            if (R.len[r] < k) continue;
-            memcpy(packed.data() + at, R.host_seq + R.pos[r], R.len[r]);
-            packed[at + R.len[r]] = 0;
-            R.pos[r] = at;                      // now the packed offset
-            at += R.len[r] + 1;
-        }
+// host path: the records >= k (each followed by 0x00) packed in group order; R.pos becomes
+// each packed record's offset
+static std::vector<uint8_t> pack_records(StageRecords &R, uint32_t k)
+{
+    uint64_t total = 0;
+    for (uint32_t r : R.order)
+        if (R.len[r] >= k) total += R.len[r] + 1;
+    std::vector<uint8_t> packed(total);
+    uint64_t at = 0;
+    for (uint32_t r : R.order) {
+        if (R.len[r] < k) continue;
+        memcpy(packed.data() + at, R.host_seq + R.pos[r], R.len[r]);
+        packed[at + R.len[r]] = 0;
+        R.pos[r] = at;
+        at += R.len[r] + 1;
     }
-    // cut tiles: a tile covers [byte_off, byte_off + n_bytes) of the packed buffer, records of
-    // one group only; short records share a tile while its k-mer starts fit (bytes between
-    // them, separators or records shorter than k, hold no valid window)
-    std::vector<TileDesc> tiles;
-    std::vector<uint32_t> tile_group;
-    uint64_t n_kmers = 0;
-    uint32_t cur_group = UINT32_MAX;
-    bool open = false;
-    TileDesc cur{};
-    auto close = [&]() {
-        if (open) { tiles.push_back(cur); tile_group.push_back(cur_group); open = false; }
-    };
-    for (uint32_t r : order) {
-        const uint64_t l = R.len[r];
-        const uint32_t g = R.group[r];
-        if (g != cur_group) { close(); cur_group = g; }
-        if (l < k) continue;
-        const uint64_t poff = R.pos[r];
-        const uint64_t nk = l - k + 1;
-        n_kmers += nk;
-        if (nk > kPackKmers) {
-            close();
-            for (uint64_t c0 = 0; c0 < nk; c0 += kChunkKmers) {
-                uint64_t cn = std::min<uint64_t>(kChunkKmers, nk - c0);
-                tiles.push_back(TileDesc{poff + c0, (uint32_t)(cn + k - 1), 0});
-                tile_group.push_back(g);
-            }
-        } else if (open && poff > cur.byte_off + cur.n_bytes &&
-                   poff + l - cur.byte_off - k + 1 <= kPackKmers) {
-            cur.n_bytes = (uint32_t)(poff + l - cur.byte_off);   // through this record
-        } else {
-            close();
-            cur = TileDesc{poff, (uint32_t)l, 0};
-            open = true;
-        }
-    }
-    close();
-    for (size_t t = 0; t < tiles.size(); t++) tiles[t].pad = tile_group[t];
+    return packed;
+}
 
-    // rows: single-tile groups write their final row, others get temp rows
-    std::vector<uint32_t> ntile_of(n_groups, 0);
-    for (uint32_t g : tile_group) ntile_of[g]++;
-    std::vector<std::vector<uint32_t>> lists(n_groups);
-    uint32_t n_rows = n_groups;
-    for (size_t t = 0; t < tiles.size(); t++) {
-        uint32_t g = tile_group[t];
-        if (ntile_of[g] == 1) tiles[t].out_row = g;
-        else { tiles[t].out_row = n_rows; lists[g].push_back(n_rows); n_rows++; }
-    }
-    // long groups (many 4096-k-mer chunks: C5 genomes): every kSampleEvery-th tile is also
-    // sketched in a sample pass (own temp rows and merge plan); the sample's s-th smallest
-    // hash is >= the group's s-th smallest, so the full pass drops every hash above it and
-    // its merges move ~kSampleEvery*s hashes per group instead of every tile's bottom-s.
-    // The sample rate per group: every E-th tile, E = the group's k-mers / 8 s within
-    // [16, 64], so a sample holds ~8 s k-mers: enough for its s-th smallest (the safe bound)
-    // and a tight kt-th one.  C5's 5 Mb genomes: E = 61, C5 23.6 -> 21.9 ms against E = 16
-    // (22.8 ms at 16 s k-mers, E = 31), same box, r05x / r05y.
-    constexpr uint32_t kSampleEvery = 16;
-    std::vector<uint32_t> every(n_groups, kSampleEvery);
-    for (uint32_t g = 0; g < n_groups; g++)
-        every[g] = (uint32_t)std::min<uint64_t>(
-            64, std::max<uint64_t>(kSampleEvery, (uint64_t)ntile_of[g] * kChunkKmers / (8ULL * s)));
-    std::vector<uint32_t> slot_of(n_groups, 0);          // 0: not sampled, else slot + 1
-    std::vector<TileDesc> stiles;
-    std::vector<std::vector<uint32_t>> slists(n_groups);
-    std::vector<uint32_t> srow, sgroup;                  // sgroup: each sample tile's group
-    {
-        std::vector<uint32_t> seen(n_groups, 0);
-        for (size_t t = 0; t < tiles.size(); t++) {
-            const uint32_t g = tile_group[t];
-            const uint64_t sample_kmers = (uint64_t)(ntile_of[g] / every[g]) * kChunkKmers;
-            if (ntile_of[g] < 2 * every[g] || sample_kmers < 4ULL * s) continue;
-            if (!slot_of[g]) { srow.push_back(0); slot_of[g] = (uint32_t)srow.size(); }
-            if (seen[g]++ % every[g] == 0) {
-                TileDesc st = tiles[t];
-                st.out_row = n_rows;
-                st.thr_slot = 0;
-                slists[g].push_back(n_rows++);
-                stiles.push_back(st);
-                sgroup.push_back(g);
-            }
-        }
-        for (size_t t = 0; t < tiles.size(); t++) tiles[t].thr_slot = slot_of[tile_group[t]];
-    }
-    // list-length estimate per row (steers merge_small_kernel only; results do not depend
-    // on it): a tile keeps at most its k-mers and s; a tile of a sampled (thresholded) group
-    // keeps ~kSampleEvery * s / tiles of the group's hashes (2x margin)
-    std::vector<uint64_t> est(n_rows, s);
-    for (size_t t = 0; t < tiles.size(); t++) {
-        const uint32_t g = tile_group[t];
-        uint64_t e = std::min<uint64_t>(s, tiles[t].n_bytes >= k ? tiles[t].n_bytes - k + 1 : 0);
-        if (slot_of[g]) e = std::min<uint64_t>(e, 2ULL * every[g] * s / ntile_of[g] + 64);
-        if (tiles[t].out_row < est.size()) est[tiles[t].out_row] = e;
-    }
-    for (auto &st : stiles)
-        if (st.out_row < est.size())
-            est[st.out_row] = std::min<uint64_t>(s, st.n_bytes >= k ? st.n_bytes - k + 1 : 0);
-    struct Plan { uint32_t a, b, c; };
-    // pairwise merge rounds of each group's lists; the last merge writes final_row(g)
-    auto plan_rounds = [&](std::vector<std::vector<uint32_t>> &L_of, auto final_row,
-                           std::vector<Plan> &plan, std::vector<uint32_t> &rounds,
-                           std::vector<uint8_t> &small) {
-        rounds.assign(1, 0);
-        small.clear();
-        for (;;) {
-            bool any = false;
-            uint64_t round_max = 0;
-            for (uint32_t g = 0; g < n_groups; g++) {
-                auto &L = L_of[g];
-                if (L.size() < 2) continue;
-                any = true;
-                std::vector<uint32_t> next;
-                for (size_t i = 0; i + 1 < L.size(); i += 2) {
-                    uint32_t c = (L.size() == 2) ? final_row(g) : n_rows++;
-                    plan.push_back({L[i], L[i + 1], c});
-                    next.push_back(c);
-                    if (est.size() <= c) est.resize(c + 1, s);
-                    const uint64_t ea = est[L[i]], eb = est[L[i + 1]];
-                    est[c] = std::min<uint64_t>(s, ea + eb);
-                    round_max = std::max(round_max, std::max(ea, eb));
-                }
-                if (L.size() % 2) next.push_back(L.back());
-                if (next.size() == 1) next.clear();   // reached the final row
-                L.swap(next);
-            }
-            if (!any) break;
-            rounds.push_back((uint32_t)plan.size());
-            small.push_back(round_max <= merge_small_cap() ? 1 : 0);
-        }
-    };
-    std::vector<Plan> splan, mplan, fplan;
-    std::vector<uint32_t> srb, rb, frb;
-    std::vector<uint8_t> ssmall, msmall, fsmall;
-    for (uint32_t g = 0; g < n_groups; g++)
-        if (slot_of[g]) srow[slot_of[g] - 1] = slists[g].size() == 1 ? slists[g][0] : 0;
-    // sampled groups select their sketch (and their sample's) with group_select_kernel; their
-    // lists leave the merge plans for fallback plans (pairwise merges only: C5 17.6 vs 2.6 ms).
-    // A group with more keys than one workgroup should read (~2^19: a 1 Gb genome's sample
-    // holds 62 M) is split into chunks of rows selected in parallel, then the chunks' sketches
-    // are selected again (a tree of levels, one launch per level).
-    std::vector<uint32_t> sel_rows;
-    std::vector<std::vector<SelDesc>> ssel_lv, sel_lv;
-    const bool use_sel = (uint64_t)s + s / 8 + 64 <= group_select_cap();
-    // A sample's tiles keep only the hashes below an a-priori bound: hash values are uniform,
-    // so of a sample's N windows ~frac N lie below frac of the hash range, and frac =
-    // (1.25 s + 16 sqrt(s)) / N leaves >= s of them (C5: ~14k of a sample's 82k) with ~40
-    // standard deviations to spare.  The sample's selection then reads ~6x fewer keys.  A
-    // sample left with fewer than s (values repeated across its tiles) gives its group no
-    // bound, as a sample shorter than s always did (the sketches do not depend on it).
-    std::vector<uint64_t> sbound(srow.size(), ~0ULL);
-    if (use_sel && !srow.empty()) {
-        std::vector<uint64_t> ns(srow.size(), 0);
-        for (size_t i = 0; i < stiles.size(); i++)
-            ns[slot_of[sgroup[i]] - 1] += stiles[i].n_bytes >= k ? stiles[i].n_bytes - k + 1 : 0;
-        const double range = kp.use64 ? 18446744073709551616.0 : 4294967296.0;
-        for (size_t i = 0; i < srow.size(); i++) {
-            const double frac = (1.25 * s + 16.0 * std::sqrt((double)s)) / std::max<double>(1, ns[i]);
-            if (frac < 0.5) sbound[i] = (uint64_t)(frac * range);
-        }
-        const uint32_t n_sl = (uint32_t)srow.size();
-        for (size_t i = 0; i < stiles.size(); i++) {
-            const uint32_t sl = slot_of[sgroup[i]];
-            if (sbound[sl - 1] != ~0ULL) {
-                stiles[i].thr_slot = n_sl + sl;              // d_thr[n_slots + slot]
-                if (stiles[i].out_row < est.size())
-                    est[stiles[i].out_row] = std::min<uint64_t>(
-                        est[stiles[i].out_row], (uint64_t)(2.0 * (double)sbound[sl - 1] / range *
-                                                           stiles[i].n_bytes) + 64);
-            }
-        }
-    }
-    // tags (optional): per level, the slot of each descriptor (sample selections carry slot
-    // 0xFFFFFFFF on the device; the host finds a group's descriptors by the tag)
-    auto build_sel = [&](const std::vector<uint32_t> &rows0, uint32_t final_row, uint32_t slot,
-                         std::vector<std::vector<SelDesc>> &lv,
-                         std::vector<std::vector<uint32_t>> *tags = nullptr, uint32_t tag = 0) {
-        constexpr uint64_t kKeysPerWG = 1u << 19;
-        constexpr size_t kRowsPerWG = 4096;
-        std::vector<uint32_t> cur = rows0;
-        for (size_t level = 0;; level++) {
-            if (lv.size() <= level) lv.resize(level + 1);
-            if (tags && tags->size() <= level) tags->resize(level + 1);
-            std::vector<std::pair<size_t, size_t>> ch;
-            size_t a = 0;
-            uint64_t acc = 0;
-            for (size_t i = 0; i < cur.size(); i++) {
-                const uint64_t e = est[cur[i]];
-                if (i > a && (acc + e > kKeysPerWG || i - a >= kRowsPerWG)) {
-                    ch.push_back({a, i});
-                    a = i;
-                    acc = 0;
-                }
-                acc += e;
-            }
-            ch.push_back({a, cur.size()});
-            if (ch.size() == 1) {
-                lv[level].push_back(SelDesc{(uint32_t)sel_rows.size(), (uint32_t)cur.size(),
-                                            final_row, slot});
-                if (tags) (*tags)[level].push_back(tag);
-                sel_rows.insert(sel_rows.end(), cur.begin(), cur.end());
-                return;
-            }
-            std::vector<uint32_t> next;
-            for (auto &c : ch) {
-                const uint32_t r = n_rows++;
-                if (est.size() <= r) est.resize(r + 1, s);
-                uint64_t sum = 0;
-                for (size_t i = c.first; i < c.second; i++) sum += est[cur[i]];
-                est[r] = std::min<uint64_t>(s, sum);
-                lv[level].push_back(SelDesc{(uint32_t)sel_rows.size(),
-                                            (uint32_t)(c.second - c.first), r, slot});
-                if (tags) (*tags)[level].push_back(tag);
-                sel_rows.insert(sel_rows.end(), cur.begin() + c.first, cur.begin() + c.second);
-                next.push_back(r);
-            }
-            cur.swap(next);
-        }
-    };
-    std::vector<Plan> sfplan;
-    std::vector<uint32_t> sfrb;
-    std::vector<uint8_t> sfsmall;
-    std::vector<std::vector<uint32_t>> sflists(n_groups), flists(n_groups);
-    std::vector<std::vector<uint32_t>> ssel_tag_lv;
-    if (use_sel)
-        for (uint32_t g = 0; g < n_groups; g++) {
-            if (!slot_of[g] || slists[g].size() < 2) continue;
-            const uint32_t r = n_rows++;                    // the sample's sketch row
-            srow[slot_of[g] - 1] = r;
-            build_sel(slists[g], r, 0xFFFFFFFFu, ssel_lv, &ssel_tag_lv, slot_of[g] - 1);
-            sflists[g].swap(slists[g]);
-        }
-    plan_rounds(slists, [&](uint32_t g) {
-        const uint32_t r = n_rows++;
-        srow[slot_of[g] - 1] = r;
-        return r;
-    }, splan, srb, ssmall);
-    if (use_sel)
-        for (uint32_t g = 0; g < n_groups; g++) {
-            if (!slot_of[g] || lists[g].size() < 2) continue;
-            build_sel(lists[g], g, slot_of[g] - 1, sel_lv);
-            flists[g].swap(lists[g]);
-        }
-    plan_rounds(lists, [](uint32_t g) { return g; }, mplan, rb, msmall);
-    // d_sel: the sample levels, then the main levels; level boundaries for the launches
-    std::vector<SelDesc> sel;
-    std::vector<uint32_t> ssel_begin{0}, sel_begin, ssel_tag;
-    for (auto &l : ssel_lv) {
-        sel.insert(sel.end(), l.begin(), l.end());
-        ssel_begin.push_back((uint32_t)sel.size());
-    }
-    for (auto &l : ssel_tag_lv) ssel_tag.insert(ssel_tag.end(), l.begin(), l.end());
-    sel_begin.push_back((uint32_t)sel.size());
-    for (auto &l : sel_lv) {
-        sel.insert(sel.end(), l.begin(), l.end());
-        sel_begin.push_back((uint32_t)sel.size());
-    }
-    // the fallback plans' intermediate rows come last: they are allocated only if a selection
-    // fails (a C5 share holds ~1.2 M tile rows of s u64: the fallback rows would double that)
-    const uint32_t n_core = n_rows;
-    if (use_sel) {
-        plan_rounds(sflists, [&](uint32_t g) { return srow[slot_of[g] - 1]; }, sfplan, sfrb,
-                    sfsmall);
-        plan_rounds(flists, [](uint32_t g) { return g; }, fplan, frb, fsmall);
-    }
+// merge steps as descriptors; row(r) / count(r): where row r and its count live
+template <typename Row, typename Count>
+static std::vector<MergeDesc> merge_descs(const std::vector<MergeStep> &steps, Row row, Count count)
+{
+    std::vector<MergeDesc> md(steps.size());
+    for (size_t i = 0; i < steps.size(); i++)
+        md[i] = MergeDesc{row(steps[i].a), count(steps[i].a), row(steps[i].b), count(steps[i].b),
+                          row(steps[i].c), count(steps[i].c)};
+    return md;
+}
 
-    // tiles ordered by capacity class
-    auto order_by_class = [&](const std::vector<TileDesc> &in, std::vector<TileDesc> &out,
-                              uint32_t *begin) {
-        out.clear();
-        out.reserve(in.size());
-        begin[0] = 0;
-        for (int c = 0; c < kTileClasses; c++) {
-            for (auto &t : in)
-                if (tile_class(t.n_bytes - k + 1) == c) out.push_back(t);
-            begin[c + 1] = (uint32_t)out.size();
-        }
-        return out.size() == in.size();
-    };
-    std::vector<TileDesc> by_class, sby_class;
-    uint32_t class_begin[kTileClasses + 1] = {0}, sclass_begin[kTileClasses + 1] = {0};
-    if (!order_by_class(tiles, by_class, class_begin) ||
-        !order_by_class(stiles, sby_class, sclass_begin))
-        return fail(FPM_EINVAL, "internal: tile exceeds capacity");
-
-    auto *job = new fpm_sketch_job();
-    job->ctx = ctx;
-    job->kp = kp;
-    job->n_groups = n_groups;
-    job->n_rows = n_core;
-    job->n_fb_rows = n_rows - n_core;
-    for (auto &pl : fplan) job->fplan.push_back({pl.a, pl.b, pl.c});
-    for (auto &pl : sfplan) job->sfplan.push_back({pl.a, pl.b, pl.c});
-    job->seq_bytes = R.host_seq ? packed.size() : R.d_seq_bytes;
-    job->n_kmers = n_kmers;
-    job->n_tiles = tiles.size();
-    memcpy(job->class_begin, class_begin, sizeof(class_begin));
-    memcpy(job->sclass_begin, sclass_begin, sizeof(sclass_begin));
-    job->round_begin = rb;
-    job->sround_begin = srb;
-    job->round_small = msmall;
-    job->sround_small = ssmall;
-    job->n_slots = (uint32_t)srow.size();
-    job->ssel_begin = ssel_begin;
-    job->sel_begin = sel_begin;
-    job->n_ssel = ssel_begin.back();
-    job->n_sel = sel_begin.back() - sel_begin.front();
-    job->sfround_begin = sfrb;
-    job->sfround_small = sfsmall;
-    job->fround_begin = frb;
-    job->fround_small = fsmall;
-
+// the device buffers job->plan asks for
+static hipError_t alloc_plan(fpm_sketch_job *job, const StageRecords &R, size_t packed_bytes)
+{
+    const SketchPlan &P = job->plan;
+    const size_t s = job->kp.s, n_slots = P.n_slots;
     hipError_t e = hipSuccess;
     auto alloc = [&](auto **ptr, size_t bytes) {
         if (e == hipSuccess) e = job->mem.get(ptr, bytes);
     };
-    if (R.host_seq) alloc(&job->d_seq, packed.size() + 64);
-    else job->d_seq = R.d_seq;   // the parse's packed records, or borrowed (adopted below)
-    alloc(&job->d_tiles, by_class.size() * sizeof(TileDesc));
-    alloc(&job->d_rows, (size_t)n_core * s * sizeof(uint64_t));
-    alloc(&job->d_count, (size_t)n_core * sizeof(uint32_t));
+    if (R.host_seq) alloc(&job->d_seq, packed_bytes + 64);
+    else job->d_seq = R.d_seq;   // the parse's packed records, or borrowed (adopted after upload)
+    alloc(&job->d_tiles, P.tiles.size() * sizeof(TileDesc));
+    alloc(&job->d_rows, (size_t)P.n_rows * s * sizeof(uint64_t));
+    alloc(&job->d_count, (size_t)P.n_rows * sizeof(uint32_t));
     // groups without any k-mer keep count 0: zeroed once here (every run rewrites the count
     // of each group that has tiles: the tile kernel or the last merge of its group)
-    if (e == hipSuccess) e = memset_sync(ctx, job->d_count, 0, (size_t)n_core * sizeof(uint32_t));
-    alloc(&job->d_merge, mplan.size() * sizeof(MergeDesc));
-    alloc(&job->d_stiles, sby_class.size() * sizeof(TileDesc));
-    alloc(&job->d_smerge, splan.size() * sizeof(MergeDesc));
-    alloc(&job->d_srow, srow.size() * sizeof(uint32_t));
-    alloc(&job->d_thr, 2 * srow.size() * sizeof(uint64_t));   // main, then sample bounds
-    alloc(&job->d_sel, sel.size() * sizeof(SelDesc));
-    alloc(&job->d_sel_rows, sel_rows.size() * sizeof(uint32_t));
-    alloc(&job->d_sel_failed, (sel.size() + 2) * sizeof(uint32_t));
-    if (e == hipSuccess && !sel.empty())
+    if (e == hipSuccess)
+        e = memset_sync(job->ctx, job->d_count, 0, (size_t)P.n_rows * sizeof(uint32_t));
+    alloc(&job->d_merge, P.merge.steps.size() * sizeof(MergeDesc));
+    alloc(&job->d_stiles, P.stiles.size() * sizeof(TileDesc));
+    alloc(&job->d_smerge, P.smerge.steps.size() * sizeof(MergeDesc));
+    alloc(&job->d_srow, n_slots * sizeof(uint32_t));
+    alloc(&job->d_thr, 2 * n_slots * sizeof(uint64_t));   // main, then sample bounds
+    alloc(&job->d_sel, P.sel.size() * sizeof(SelDesc));
+    alloc(&job->d_sel_rows, P.sel_rows.size() * sizeof(uint32_t));
+    alloc(&job->d_sel_failed, (P.sel.size() + 2) * sizeof(uint32_t));
+    if (e == hipSuccess && !P.sel.empty())
         e = hipHostMalloc((void **)&job->h_sel_failed, 3 * sizeof(uint32_t), hipHostMallocDefault);
-    // tight bounds where every sampled group has a selection: kt = f s + 8 sqrt(f s) + 32 of
-    // the sample's hashes (f = the group's sampled share of tiles), so ~kt / f >= s of the
-    // group's distinct hashes lie below it with ~8 standard deviations to spare (C5 at E = 61:
-    // ~300 of the sample's 10,000; the group keeps ~18k hashes instead of ~160k)
-    std::vector<uint32_t> kt, slot_group;
-    if (use_sel && !srow.empty() && !sel.empty()) {
-        kt.assign(srow.size(), s);
-        slot_group.assign(srow.size(), 0);
-        for (uint32_t g = 0; g < n_groups; g++) {
-            if (!slot_of[g]) continue;
-            const uint32_t i = slot_of[g] - 1;
-            slot_group[i] = g;
-            const double f = (double)((ntile_of[g] + every[g] - 1) / every[g]) / ntile_of[g];
-            const double fs = f * s;
-            kt[i] = (uint32_t)std::min<double>(s, std::ceil(fs + 8.0 * std::sqrt(fs) + 32.0));
-        }
-        job->tight = true;
-        alloc(&job->d_kt, kt.size() * sizeof(uint32_t));
-        alloc(&job->d_slot_group, slot_group.size() * sizeof(uint32_t));
-        alloc(&job->d_short, (srow.size() + 1) * sizeof(uint32_t));
-        alloc(&job->d_thr_safe, srow.size() * sizeof(uint64_t));
-        job->h_tiles = by_class;
-        job->h_sel = sel;
+    if (P.tight) {
+        alloc(&job->d_kt, n_slots * sizeof(uint32_t));
+        alloc(&job->d_slot_group, n_slots * sizeof(uint32_t));
+        alloc(&job->d_short, (n_slots + 1) * sizeof(uint32_t));
+        alloc(&job->d_thr_safe, n_slots * sizeof(uint64_t));
         job->last_short = 0;
-        bool any_sb = false;
-        for (uint64_t b : sbound) any_sb = any_sb || b != ~0ULL;
-        if (any_sb) {
-            job->sbounded = true;
-            job->h_stiles = sby_class;
-            job->h_ssel_tag = ssel_tag;
-            job->last_sample_short = 0;
-            alloc(&job->d_sshort, (srow.size() + 1) * sizeof(uint32_t));
-            alloc(&job->d_sbound0, srow.size() * sizeof(uint64_t));
-        }
     }
-    {
-        // the survivors-only tile kernel for the class-4 tiles when every one carries its
-        // group's bound and that bound leaves few survivors per tile: a group's main pass keeps
-        // about kSampleEvery * s of its hashes (the sample's s-th smallest bounds them), so a
-        // tile keeps ~kSampleEvery * s / (the group's tiles); est (2x margin + 64, above) must
-        // stay within half of what one tile holds, or most tiles would be hashed twice (their
-        // survivors overflow and the plain kernel redoes them).  (C5 one GPU: 31.2 -> 25.8 ms,
-        // same box, r04; C5 tiles: est 326 of 1,024)
-        const uint32_t b4 = class_begin[4], n4 = class_begin[5] - b4;
-        // (tight bounds: ~kt / f survivors per group; a short group's redo under the safe bound
-        // keeps ~E s per group, and its tiles that overflow are redone by the plain kernel)
-        std::vector<uint64_t> slot_est(srow.size() + 1, ~0ULL);
-        for (uint32_t g = 0; g < n_groups; g++) {
-            if (!slot_of[g]) continue;
-            const double f = (double)((ntile_of[g] + every[g] - 1) / every[g]) / ntile_of[g];
-            slot_est[slot_of[g]] = job->tight
-                                       ? (uint64_t)(2.0 * kt[slot_of[g] - 1] / f / ntile_of[g]) + 64
-                                       : 2ULL * every[g] * s / ntile_of[g] + 64;
-        }
-        bool all = n4 > 0;
-        for (uint32_t i = 0; all && i < n4; i++) {
-            const uint32_t sl = by_class[b4 + i].thr_slot;
-            all = sl != 0 && slot_est[sl] <= kThrTileKeys / 2;
-        }
-        job->thr4 = all;
-        job->n4 = n4;
-        if (all) {
-            alloc(&job->d_redo, (size_t)n4 * sizeof(TileDesc));
-            alloc(&job->d_redo_n, sizeof(uint32_t));
-        }
+    if (P.sbounded) {
+        alloc(&job->d_sshort, (n_slots + 1) * sizeof(uint32_t));
+        alloc(&job->d_sbound0, n_slots * sizeof(uint64_t));
+        job->last_sample_short = 0;
     }
-    if (e != hipSuccess) {
-        job_release(job);
-        delete job;
-        return fail(FPM_ENOMEM, std::string("sketch staging alloc: ") + hipGetErrorString(e));
+    if (P.thr4) {
+        alloc(&job->d_redo, (size_t)P.n4 * sizeof(TileDesc));
+        alloc(&job->d_redo_n, sizeof(uint32_t));
     }
-    auto descs = [&](const std::vector<Plan> &plan) {
-        std::vector<MergeDesc> md(plan.size());
-        for (size_t i = 0; i < plan.size(); i++) {
-            md[i].a = job->d_rows + (uint64_t)plan[i].a * s;
-            md[i].alen = job->d_count + plan[i].a;
-            md[i].b = job->d_rows + (uint64_t)plan[i].b * s;
-            md[i].blen = job->d_count + plan[i].b;
-            md[i].c = job->d_rows + (uint64_t)plan[i].c * s;
-            md[i].clen = job->d_count + plan[i].c;
-        }
-        return md;
-    };
-    const std::vector<MergeDesc> md = descs(mplan), smd = descs(splan);
+    return e;
+}
+
+// job->plan and the packed records (host path) into the buffers of alloc_plan
+static hipError_t copy_plan(fpm_sketch_job *job, const std::vector<uint8_t> &packed)
+{
+    const SketchPlan &P = job->plan;
+    fpm_ctx *ctx = job->ctx;
+    const uint64_t s = job->kp.s;
+    auto row = [&](uint32_t r) { return job->d_rows + r * s; };
+    auto cnt = [&](uint32_t r) { return job->d_count + r; };
+    hipError_t e = hipSuccess;
     if (!packed.empty()) e = h2d_staged(ctx, job->d_seq, packed.data(), packed.size());
     auto put = [&](void *dst, const auto &v) {      // (an empty vector copies nothing)
         if (e == hipSuccess) e = copy_in(ctx, dst, v.data(), v.size() * sizeof(v[0]));
     };
-    put(job->d_tiles, by_class);
-    put(job->d_merge, md);
-    put(job->d_stiles, sby_class);
-    put(job->d_smerge, smd);
-    put(job->d_srow, srow);
-    put(job->d_sel, sel);
-    put(job->d_sel_rows, sel_rows);
-    put(job->d_thr + srow.size(), sbound);
-    if (job->d_sbound0) put(job->d_sbound0, sbound);
-    put(job->d_kt, kt);
-    put(job->d_slot_group, slot_group);
-    if (e != hipSuccess) {
+    put(job->d_tiles, P.tiles);
+    put(job->d_merge, merge_descs(P.merge.steps, row, cnt));
+    put(job->d_stiles, P.stiles);
+    put(job->d_smerge, merge_descs(P.smerge.steps, row, cnt));
+    put(job->d_srow, P.srow);
+    put(job->d_sel, P.sel);
+    put(job->d_sel_rows, P.sel_rows);
+    put(job->d_thr + P.n_slots, P.sbound);
+    if (job->d_sbound0) put(job->d_sbound0, P.sbound);
+    put(job->d_kt, P.kt);
+    put(job->d_slot_group, P.slot_group);
+    return e;
+}
+
+static int upload_plan(fpm_sketch_job *job, const StageRecords &R, const std::vector<uint8_t> &packed)
+{
+    hipError_t e = alloc_plan(job, R, packed.size());
+    if (e != hipSuccess)
+        return fail(FPM_ENOMEM, std::string("sketch staging alloc: ") + hipGetErrorString(e));
+    e = copy_plan(job, packed);
+    if (e != hipSuccess)
+        return fail(FPM_EHIP, std::string("sketch staging copy: ") + hipGetErrorString(e));
+    if (!R.host_seq && !R.borrow) job->mem.adopt(R.d_seq);
+    return FPM_OK;
+}
+
+// parameters, pack, plan (sketch_plan.cpp), allocate and upload
+int stage_core(fpm_ctx *ctx, const fpm_sketch_params *p, StageRecords &R,
+               fpm_sketch_job **job_out)
+{
+    if (p->kmer_size < 1 || p->kmer_size > 32) return fail(FPM_EINVAL, "kmer_size must be 1..32");
+    if (p->sketch_size < 1) return fail(FPM_EINVAL, "sketch_size must be >= 1");
+    const SketchKParams kp = kernel_params(p);
+    std::vector<uint8_t> packed;
+    if (R.host_seq) packed = pack_records(R, kp.k);
+    SketchPlan plan;
+    if (!plan_sketch(PlanRecords{R.order, R.pos, R.len, R.group, R.n_groups},
+                     PlanParams{kp.k, kp.s, kp.use64 != 0}, &plan))
+        return fail(FPM_EINVAL, "internal: tile exceeds capacity");
+    auto *job = new fpm_sketch_job();
+    job->ctx = ctx;
+    job->kp = kp;
+    job->plan = std::move(plan);
+    job->seq_bytes = R.host_seq ? packed.size() : R.d_seq_bytes;
+    if (int rc = upload_plan(job, R, packed)) {
         job_release(job);
         delete job;
-        return fail(FPM_EHIP, std::string("sketch staging copy: ") + hipGetErrorString(e));
+        return rc;
     }
-    if (!R.host_seq && !R.borrow) job->mem.adopt(R.d_seq);
     // kept for reads mode's widening rounds (moved, not copied: the callers are done with them)
     job->params = *p;
-    job->recs.n_groups = n_groups;
+    job->recs.n_groups = R.n_groups;
     job->recs.order = std::move(R.order);
     job->recs.pos = std::move(R.pos);
     job->recs.len = std::move(R.len);
@@ -673,34 +320,31 @@ int stage_core(fpm_ctx *ctx, const fpm_sketch_params *p, StageRecords &R,
 static int fallback_descs(fpm_sketch_job *job)
 {
     if (job->d_fmerge || job->d_sfmerge) return FPM_OK;
+    const SketchPlan &P = job->plan;
     const uint64_t s = job->kp.s;
-    if (job->n_fb_rows) {
-        HIP_TRY(job->mem.get(&job->d_fb_rows, (size_t)job->n_fb_rows * s * sizeof(uint64_t)));
-        HIP_TRY(job->mem.get(&job->d_fb_count, (size_t)job->n_fb_rows * sizeof(uint32_t)));
+    if (P.n_fb_rows) {
+        HIP_TRY(job->mem.get(&job->d_fb_rows, (size_t)P.n_fb_rows * s * sizeof(uint64_t)));
+        HIP_TRY(job->mem.get(&job->d_fb_count, (size_t)P.n_fb_rows * sizeof(uint32_t)));
     }
-    auto row = [&](uint32_t r) { return r < job->n_rows ? job->d_rows + r * s
-                                                       : job->d_fb_rows + (r - job->n_rows) * s; };
-    auto cnt = [&](uint32_t r) { return r < job->n_rows ? job->d_count + r
-                                                       : job->d_fb_count + (r - job->n_rows); };
-    auto upload = [&](const std::vector<std::array<uint32_t, 3>> &plan, MergeDesc **dst) -> int {
-        std::vector<MergeDesc> md(plan.size());
-        for (size_t i = 0; i < plan.size(); i++)
-            md[i] = MergeDesc{row(plan[i][0]), cnt(plan[i][0]), row(plan[i][1]), cnt(plan[i][1]),
-                              row(plan[i][2]), cnt(plan[i][2])};
-        HIP_TRY(job->mem.upload(job->ctx, dst, md.data(), md.size() * sizeof(MergeDesc)));
-        return FPM_OK;
-    };
-    if (int rc = upload(job->fplan, &job->d_fmerge)) return rc;
-    return upload(job->sfplan, &job->d_sfmerge);
+    auto row = [&](uint32_t r) { return r < P.n_rows ? job->d_rows + r * s
+                                                     : job->d_fb_rows + (r - P.n_rows) * s; };
+    auto cnt = [&](uint32_t r) { return r < P.n_rows ? job->d_count + r
+                                                     : job->d_fb_count + (r - P.n_rows); };
+    const std::vector<MergeDesc> md = merge_descs(P.fmerge.steps, row, cnt),
+                                 smd = merge_descs(P.sfmerge.steps, row, cnt);
+    HIP_TRY(job->mem.upload(job->ctx, &job->d_fmerge, md.data(), md.size() * sizeof(MergeDesc)));
+    HIP_TRY(job->mem.upload(job->ctx, &job->d_sfmerge, smd.data(), smd.size() * sizeof(MergeDesc)));
+    return FPM_OK;
 }
 
 // device room for a redo's tile and selection subsets (allocated on first use)
 static int redo_buffers(fpm_sketch_job *job)
 {
+    const SketchPlan &P = job->plan;
     if (!job->d_rtiles)
         HIP_TRY(job->mem.get(&job->d_rtiles,
-                             std::max(job->h_tiles.size(), job->h_stiles.size()) * sizeof(TileDesc)));
-    if (!job->d_rsel) HIP_TRY(job->mem.get(&job->d_rsel, job->h_sel.size() * sizeof(SelDesc)));
+                             std::max(P.tiles.size(), P.stiles.size()) * sizeof(TileDesc)));
+    if (!job->d_rsel) HIP_TRY(job->mem.get(&job->d_rsel, P.sel.size() * sizeof(SelDesc)));
     return FPM_OK;
 }
 
@@ -719,26 +363,63 @@ static int select_levels(fpm_sketch_job *job, const SelDesc *d_sel,
     return FPM_OK;
 }
 
+// the tile kernels over d_t, a tile array ordered by class; `main`: the main pass, whose class-4
+// tiles take the survivors-only kernel when the plan says so
+static int tiles_pass(fpm_sketch_job *job, const TileDesc *d_t, const uint32_t *begin, bool main,
+                      hipStream_t st)
+{
+    return for_each_class(begin, [&](int c, uint32_t b, uint32_t n) -> int {
+        TimedLaunch tl(job->ctx, FPM_K_SKETCH, st);
+        if (main && c == 4 && job->plan.thr4) {
+            HIP_TRY(hipMemsetAsync(job->d_redo_n, 0, sizeof(uint32_t), st));
+            HIP_TRY(launch_sketch_tiles_thr(job->d_seq, d_t + b, n, job->kp, job->d_thr,
+                                            job->d_rows, job->d_count, job->d_redo,
+                                            job->d_redo_n, st));
+            // the tiles whose survivors did not fit, again through the plain kernel; the
+            // count stays on the device (the list holds at most n: one entry per tile)
+            HIP_TRY(launch_sketch_redo(job->d_seq, job->d_redo, job->d_redo_n, n, job->kp,
+                                       job->d_thr, job->d_rows, job->d_count, st));
+        } else {
+            HIP_TRY(launch_sketch_tiles(c, job->d_seq, d_t + b, n, job->kp, job->d_thr,
+                                        job->d_rows, job->d_count, st));
+        }
+        tl.done();
+        return FPM_OK;
+    });
+}
+
+// one launch per round of a merge schedule over its descriptors d_m
+static int merge_pass(fpm_sketch_job *job, const MergeDesc *d_m, const MergeSchedule &m,
+                      hipStream_t st)
+{
+    for (size_t r = 0; r < m.rounds(); r++) {
+        const uint32_t b = m.round_begin[r], n = m.round_begin[r + 1] - b;
+        TimedLaunch tl(job->ctx, FPM_K_MERGE, st);
+        HIP_TRY(launch_merge(d_m + b, n, job->kp.s, round_is_small(m, r), st));
+        tl.done();
+    }
+    return FPM_OK;
+}
+
 // The groups a bound left short, their tiles and selections once more.  Main pass: the tight
 // bound (slots in d_short[1 ..], bounds already raised to the safe ones by
 // sketch_short_kernel).  Sample pass: the a-priori bound (slots in d_sshort[1 ..], bounds
 // lifted by sketch_sample_short_kernel), the sample tiles and sample selections.
-template <typename TilesPass>
-static int redo_short(fpm_sketch_job *job, bool sample, uint32_t n_short, hipStream_t st,
-                      TilesPass &tiles_pass)
+static int redo_short(fpm_sketch_job *job, bool sample, uint32_t n_short, hipStream_t st)
 {
     fpm_ctx *ctx = job->ctx;
+    const SketchPlan &P = job->plan;
     std::vector<uint32_t> slots(n_short);
     HIP_TRY(hipMemcpyAsync(slots.data(), (sample ? job->d_sshort : job->d_short) + 1,
                            n_short * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    std::vector<uint8_t> is_short(job->n_slots + 1, 0);
+    std::vector<uint8_t> is_short(P.n_slots + 1, 0);
     for (uint32_t i : slots)
-        if (i < job->n_slots) is_short[i] = 1;
+        if (i < P.n_slots) is_short[i] = 1;
     // a main tile carries slot + 1 (0: none), a bounded sample tile n_slots + slot + 1
-    const uint32_t *cb = sample ? job->sclass_begin : job->class_begin;
-    const std::vector<TileDesc> &tiles = sample ? job->h_stiles : job->h_tiles;
-    const uint32_t base = sample ? job->n_slots : 0;
+    const uint32_t *cb = sample ? P.sclass_begin : P.class_begin;
+    const std::vector<TileDesc> &tiles = sample ? P.stiles : P.tiles;
+    const uint32_t base = sample ? P.n_slots : 0;
     std::vector<TileDesc> sub;
     uint32_t begin[kTileClasses + 1] = {0};
     for (int c = 0; c < kTileClasses; c++) {
@@ -749,21 +430,21 @@ static int redo_short(fpm_sketch_job *job, bool sample, uint32_t n_short, hipStr
         begin[c + 1] = (uint32_t)sub.size();
     }
     // a main selection carries its slot, a sample selection's slot is its host-side tag
-    const std::vector<uint32_t> &lv = sample ? job->ssel_begin : job->sel_begin;
+    const std::vector<uint32_t> &lv = sample ? P.ssel_begin : P.sel_begin;
     std::vector<SelDesc> rsel;
     std::vector<uint32_t> rbegin{0};
     for (size_t l = 0; l + 1 < lv.size(); l++) {
         for (uint32_t i = lv[l]; i < lv[l + 1]; i++) {
-            const uint32_t slot = !sample ? job->h_sel[i].slot
-                                  : i < job->h_ssel_tag.size() ? job->h_ssel_tag[i] : UINT32_MAX;
-            if (slot < job->n_slots && is_short[slot]) rsel.push_back(job->h_sel[i]);
+            const uint32_t slot = !sample ? P.sel[i].slot
+                                  : i < P.ssel_tag.size() ? P.ssel_tag[i] : UINT32_MAX;
+            if (slot < P.n_slots && is_short[slot]) rsel.push_back(P.sel[i]);
         }
         rbegin.push_back((uint32_t)rsel.size());
     }
     if (int rc = redo_buffers(job)) return rc;
     if (!sub.empty()) HIP_TRY(copy_in(ctx, job->d_rtiles, sub.data(), sub.size() * sizeof(TileDesc)));
     if (!rsel.empty()) HIP_TRY(copy_in(ctx, job->d_rsel, rsel.data(), rsel.size() * sizeof(SelDesc)));
-    if (int rc = tiles_pass(job->d_rtiles, begin, !sample)) return rc;
+    if (int rc = tiles_pass(job, job->d_rtiles, begin, !sample, st)) return rc;
     return select_levels(job, job->d_rsel, rbegin, job->d_sel_failed + (sample ? 1 : 0), st);
 }
 
@@ -775,48 +456,15 @@ int fpm_sketch_run(fpm_sketch_job *job, void *stream)
     fpm_ctx *ctx = job->ctx;
     if (int rc = set_device(ctx)) return rc;
     hipStream_t st = pick_stream(ctx, stream);
-    auto tiles_pass = [&](const TileDesc *d_t, const uint32_t *begin, bool main) -> int {
-        for (int c = 0; c < kTileClasses; c++) {
-            uint32_t b = begin[c], n = begin[c + 1] - b;
-            if (!n) continue;
-            TimedLaunch tl(ctx, FPM_K_SKETCH, st);
-            if (main && c == 4 && job->thr4) {
-                HIP_TRY(hipMemsetAsync(job->d_redo_n, 0, sizeof(uint32_t), st));
-                HIP_TRY(launch_sketch_tiles_thr(job->d_seq, d_t + b, n, job->kp, job->d_thr,
-                                                job->d_rows, job->d_count, job->d_redo,
-                                                job->d_redo_n, st));
-                // the tiles whose survivors did not fit, again through the plain kernel; the
-                // count stays on the device (the list holds at most n: one entry per tile)
-                HIP_TRY(launch_sketch_redo(job->d_seq, job->d_redo, job->d_redo_n, n, job->kp,
-                                           job->d_thr, job->d_rows, job->d_count, st));
-            } else {
-                HIP_TRY(launch_sketch_tiles(c, job->d_seq, d_t + b, n, job->kp, job->d_thr,
-                                            job->d_rows, job->d_count, st));
-            }
-            tl.done();
-        }
-        return FPM_OK;
-    };
-    auto merge_pass = [&](const MergeDesc *d_m, const std::vector<uint32_t> &rounds,
-                          const std::vector<uint8_t> &small) -> int {
-        for (size_t r = 0; r + 1 < rounds.size(); r++) {
-            uint32_t b = rounds[r], n = rounds[r + 1] - b;
-            TimedLaunch tl(ctx, FPM_K_MERGE, st);
-            const bool sm = g_merge_small_env == 2 ||
-                            (g_merge_small_env != 0 && r < small.size() && small[r]);
-            HIP_TRY(launch_merge(d_m + b, n, job->kp.s, sm, st));
-            tl.done();
-        }
-        return FPM_OK;
-    };
+    const SketchPlan &P = job->plan;
     // failure flags: [0] main selections, [1] sample selections, [2..] per selection
     uint32_t *fail_main = job->d_sel_failed, *fail_samp = job->d_sel_failed + 1;
     // a selection that did not fit (more repeated values below the cut than LDS holds):
     // the pairwise merges of every sampled group's lists (rare; one host round trip)
     auto fallback = [&](bool sample) -> int {
         if (int rc = fallback_descs(job)) return rc;
-        return sample ? merge_pass(job->d_sfmerge, job->sfround_begin, job->sfround_small)
-                      : merge_pass(job->d_fmerge, job->fround_begin, job->fround_small);
+        return sample ? merge_pass(job, job->d_sfmerge, P.sfmerge, st)
+                      : merge_pass(job, job->d_fmerge, P.fmerge, st);
     };
     // After a pass's selections and merges.  The groups its bound left short (`bounded`) are
     // counted before the one host read that also fetches the selections' failure flag (a
@@ -842,64 +490,63 @@ int fpm_sketch_run(fpm_sketch_job *job, void *stream)
         if (!n_short) return FPM_OK;
         if (int rc = list(true)) return rc;   // the same list, raised
         HIP_TRY(hipMemsetAsync(d_fail, 0, sizeof(uint32_t), st));
-        if (int rc = redo_short(job, sample, n_short, st, tiles_pass)) return rc;
+        if (int rc = redo_short(job, sample, n_short, st)) return rc;
         HIP_TRY(hipMemcpyAsync(h_fail, d_fail, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         return *h_fail ? fallback(sample) : FPM_OK;
     };
-    if (job->n_ssel + job->n_sel)
-        HIP_TRY(hipMemsetAsync(job->d_sel_failed, 0, (job->n_ssel + job->n_sel + 2) * sizeof(uint32_t),
-                               st));
-    if (job->n_slots) {   // sample pass of long groups -> per-group hash bounds
-        if (job->sbounded)   // the bounds as staged (a previous run's redo lifted some)
-            HIP_TRY(hipMemcpyAsync(job->d_thr + job->n_slots, job->d_sbound0,
-                                   job->n_slots * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-        if (int rc = tiles_pass(job->d_stiles, job->sclass_begin, false)) return rc;
-        if (job->n_ssel) {
-            if (int rc = select_levels(job, job->d_sel, job->ssel_begin, fail_samp, st)) return rc;
+    if (!P.sel.empty())
+        HIP_TRY(hipMemsetAsync(job->d_sel_failed, 0, (P.sel.size() + 2) * sizeof(uint32_t), st));
+    if (P.n_slots) {   // sample pass of long groups -> per-group hash bounds
+        if (P.sbounded)   // the bounds as staged (a previous run's redo lifted some)
+            HIP_TRY(hipMemcpyAsync(job->d_thr + P.n_slots, job->d_sbound0,
+                                   P.n_slots * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+        if (int rc = tiles_pass(job, job->d_stiles, P.sclass_begin, false, st)) return rc;
+        if (P.n_ssel()) {
+            if (int rc = select_levels(job, job->d_sel, P.ssel_begin, fail_samp, st)) return rc;
             HIP_TRY(hipMemcpyAsync(job->h_sel_failed + 1, fail_samp, sizeof(uint32_t),
                                    hipMemcpyDeviceToHost, st));
         }
-        if (int rc = merge_pass(job->d_smerge, job->sround_begin, job->sround_small)) return rc;
-        if (job->n_ssel) {
+        if (int rc = merge_pass(job, job->d_smerge, P.smerge, st)) return rc;
+        if (P.n_ssel()) {
             // samples their a-priori bound left short: redone unbounded
             auto list_sample_short = [&](bool raise) -> int {
                 HIP_TRY(hipMemsetAsync(job->d_sshort, 0, sizeof(uint32_t), st));
-                HIP_TRY(launch_sketch_sample_short(job->d_srow, job->n_slots, job->d_count,
-                                                   job->kp.s, job->d_thr + job->n_slots,
-                                                   job->d_sshort, job->d_sshort + 1, raise, st));
+                HIP_TRY(launch_sketch_sample_short(job->d_srow, P.n_slots, job->d_count, job->kp.s,
+                                                   job->d_thr + P.n_slots, job->d_sshort,
+                                                   job->d_sshort + 1, raise, st));
                 HIP_TRY(hipMemcpyAsync(job->h_sel_failed + 2, job->d_sshort, sizeof(uint32_t),
                                        hipMemcpyDeviceToHost, st));
                 return FPM_OK;
             };
-            if (int rc = settle(true, job->sbounded, list_sample_short, job->last_sample_short))
+            if (int rc = settle(true, P.sbounded, list_sample_short, job->last_sample_short))
                 return rc;
         }
-        HIP_TRY(launch_sketch_threshold(job->d_srow, job->n_slots, job->d_rows, job->d_count,
-                                        job->kp.s, job->tight ? job->d_kt : nullptr, job->d_thr,
-                                        job->tight ? job->d_thr_safe : nullptr, st));
+        HIP_TRY(launch_sketch_threshold(job->d_srow, P.n_slots, job->d_rows, job->d_count,
+                                        job->kp.s, P.tight ? job->d_kt : nullptr, job->d_thr,
+                                        P.tight ? job->d_thr_safe : nullptr, st));
     }
     // (the selections of each batch of genomes on a side stream beside the next batch's
     // tiles measured a wash on C5: the 120 KB-LDS selection workgroups take the tiles' CUs)
-    if (int rc = tiles_pass(job->d_tiles, job->class_begin, true)) return rc;
-    if (job->n_sel) {
-        if (int rc = select_levels(job, job->d_sel, job->sel_begin, fail_main, st)) return rc;
+    if (int rc = tiles_pass(job, job->d_tiles, P.class_begin, true, st)) return rc;
+    if (P.n_sel()) {
+        if (int rc = select_levels(job, job->d_sel, P.sel_begin, fail_main, st)) return rc;
         HIP_TRY(hipMemcpyAsync(job->h_sel_failed, fail_main, sizeof(uint32_t),
                                hipMemcpyDeviceToHost, st));
     }
-    if (int rc = merge_pass(job->d_merge, job->round_begin, job->round_small)) return rc;
-    if (job->n_sel) {
+    if (int rc = merge_pass(job, job->d_merge, P.merge, st)) return rc;
+    if (P.n_sel()) {
         // the groups the tight bound left short: redone under the safe bound
         auto list_short = [&](bool raise) -> int {
             HIP_TRY(hipMemsetAsync(job->d_short, 0, sizeof(uint32_t), st));
-            HIP_TRY(launch_sketch_short(job->d_slot_group, job->n_slots, job->d_count, job->kp.s,
+            HIP_TRY(launch_sketch_short(job->d_slot_group, P.n_slots, job->d_count, job->kp.s,
                                         job->d_thr, job->d_thr_safe, job->d_short, job->d_short + 1,
                                         raise, st));
             HIP_TRY(hipMemcpyAsync(job->h_sel_failed + 2, job->d_short, sizeof(uint32_t),
                                    hipMemcpyDeviceToHost, st));
             return FPM_OK;
         };
-        return settle(false, job->tight && job->n_slots, list_short, job->last_short);
+        return settle(false, P.tight && P.n_slots, list_short, job->last_short);
     }
     return FPM_OK;
 }
@@ -914,7 +561,7 @@ int fpm_sketch_job_short_groups(fpm_sketch_job *job, int32_t *n_short)
 int fpm_sketch_job_sample_short(fpm_sketch_job *job, int32_t *n_short)
 {
     if (!job || !n_short) return fail(FPM_EINVAL, "null argument");
-    *n_short = job->sbounded ? job->last_sample_short : -1;
+    *n_short = job->plan.sbounded ? job->last_sample_short : -1;
     return FPM_OK;
 }
 
@@ -924,24 +571,22 @@ int fpm_sketch_job_plan(fpm_sketch_job *job, fpm_sketch_plan *out)
     static_assert(FPM_TILE_CLASSES == kTileClasses, "fpmash.h states the tile classes");
     *out = fpm_sketch_plan{};
     for (int c = 0; c < kTileClasses; c++) {
-        out->tiles[c] = job->class_begin[c + 1] - job->class_begin[c];
-        out->sample_tiles[c] = job->sclass_begin[c + 1] - job->sclass_begin[c];
+        out->tiles[c] = job->plan.class_begin[c + 1] - job->plan.class_begin[c];
+        out->sample_tiles[c] = job->plan.sclass_begin[c + 1] - job->plan.sclass_begin[c];
     }
-    out->thr4 = job->thr4 ? 1 : 0;
-    out->n_slots = job->n_slots;
-    out->tight = job->tight ? 1 : 0;
-    out->n_ssel = job->n_ssel;
-    out->n_sel = job->n_sel;
+    out->thr4 = job->plan.thr4 ? 1 : 0;
+    out->n_slots = job->plan.n_slots;
+    out->tight = job->plan.tight ? 1 : 0;
+    out->n_ssel = job->plan.n_ssel();
+    out->n_sel = job->plan.n_sel();
     // as merge_pass (fpm_sketch_run) routes each round
-    auto rounds = [](const std::vector<uint32_t> &begin, const std::vector<uint8_t> &small,
-                     uint32_t *n, uint32_t *n_small) {
-        *n = begin.empty() ? 0 : (uint32_t)begin.size() - 1;
+    auto rounds = [](const MergeSchedule &m, uint32_t *n, uint32_t *n_small) {
+        *n = (uint32_t)m.rounds();
         for (size_t r = 0; r < *n; r++)
-            if (g_merge_small_env == 2 || (g_merge_small_env != 0 && r < small.size() && small[r]))
-                ++*n_small;
+            if (round_is_small(m, r)) ++*n_small;
     };
-    rounds(job->round_begin, job->round_small, &out->rounds, &out->rounds_small);
-    rounds(job->sround_begin, job->sround_small, &out->sample_rounds, &out->sample_rounds_small);
+    rounds(job->plan.merge, &out->rounds, &out->rounds_small);
+    rounds(job->plan.smerge, &out->sample_rounds, &out->sample_rounds_small);
     out->merge_kernel = job->kp.s <= kMergeLdsKeys ? FPM_MK_LDS : FPM_MK_GLOBAL;
     return FPM_OK;
 }
@@ -961,7 +606,7 @@ int fpm_sketch_device_output(fpm_sketch_job *job, uint64_t **d_hashes, uint32_t 
     if (!job) return fail(FPM_EINVAL, "null job");
     if (d_hashes) *d_hashes = job->d_rows;
     if (d_count) *d_count = job->d_count;
-    if (n_groups) *n_groups = job->n_groups;
+    if (n_groups) *n_groups = job->plan.n_groups;
     if (row_stride) *row_stride = job->kp.s;
     return FPM_OK;
 }
@@ -973,11 +618,11 @@ int fpm_sketch_fetch(fpm_sketch_job *job, uint64_t *out_hashes, uint32_t *out_co
     if (int rc = set_device(ctx)) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(hipDeviceSynchronize());
-    if (out_hashes && job->n_groups)
+    if (out_hashes && job->plan.n_groups)
         HIP_TRY(d2h_staged(ctx, out_hashes, job->d_rows,
-                           (size_t)job->n_groups * job->kp.s * sizeof(uint64_t)));
-    if (out_count && job->n_groups)
-        HIP_TRY(copy_out(ctx, out_count, job->d_count, (size_t)job->n_groups * sizeof(uint32_t)));
+                           (size_t)job->plan.n_groups * job->kp.s * sizeof(uint64_t)));
+    if (out_count && job->plan.n_groups)
+        HIP_TRY(copy_out(ctx, out_count, job->d_count, (size_t)job->plan.n_groups * sizeof(uint32_t)));
     return FPM_OK;
 }
 
@@ -987,7 +632,7 @@ int fpm_sketch_mult(fpm_sketch_job *job, void *stream, uint32_t *out_mult)
     fpm_ctx *ctx = job->ctx;
     if (int rc = set_device(ctx)) return rc;
     hipStream_t st = pick_stream(ctx, stream);
-    const uint64_t s = job->kp.s, ng = job->n_groups;
+    const uint64_t s = job->kp.s, ng = job->plan.n_groups;
     if (!ng) return FPM_OK;
     if (!job->d_mult) {
         HIP_TRY(job->mem.get(&job->d_mult, ng * s * sizeof(uint32_t)));
@@ -998,17 +643,18 @@ int fpm_sketch_mult(fpm_sketch_job *job, void *stream, uint32_t *out_mult)
     HIP_TRY(hipMemsetAsync(job->d_first, 0xff, ng * s * sizeof(unsigned long long), st));
     for (int pass = 0; pass < 2; pass++) {
         if (pass == 1)
-            HIP_TRY(launch_mult_ttop(job->d_count, job->n_groups, job->kp.s, job->d_first,
+            HIP_TRY(launch_mult_ttop(job->d_count, job->plan.n_groups, job->kp.s, job->d_first,
                                      job->d_ttop, st));
-        for (int c = 0; c < kTileClasses; c++) {
-            const uint32_t b = job->class_begin[c], n = job->class_begin[c + 1] - b;
-            if (!n) continue;
+        const uint32_t *cb = job->plan.class_begin;
+        const int rc = for_each_class(cb, [&](int c, uint32_t b, uint32_t n) -> int {
             TimedLaunch tl(ctx, FPM_K_SKETCH, st);
             HIP_TRY(launch_sketch_mult(c, pass, job->d_seq, job->d_tiles + b, n, job->kp,
                                        job->d_rows, job->d_count, job->d_mult, job->d_first,
                                        job->d_ttop, st));
             tl.done();
-        }
+            return FPM_OK;
+        });
+        if (rc) return rc;
     }
     if (out_mult) {
         HIP_TRY(hipStreamSynchronize(st));
@@ -1022,8 +668,8 @@ int fpm_sketch_job_info(fpm_sketch_job *job, uint64_t *seq_bytes, uint64_t *n_ti
 {
     if (!job) return fail(FPM_EINVAL, "null job");
     if (seq_bytes) *seq_bytes = job->seq_bytes;
-    if (n_tiles) *n_tiles = job->n_tiles;
-    if (n_kmers) *n_kmers = job->n_kmers;
+    if (n_tiles) *n_tiles = job->plan.tiles.size();
+    if (n_kmers) *n_kmers = job->plan.n_kmers;
     return FPM_OK;
 }
 
@@ -1031,7 +677,7 @@ int fpm_sketch_job_redo_tiles(fpm_sketch_job *job, int32_t *n_redo)
 {
     if (!job || !n_redo) return fail(FPM_EINVAL, "null argument");
     *n_redo = -1;
-    if (!job->thr4 || !job->d_redo_n) return FPM_OK;
+    if (!job->plan.thr4 || !job->d_redo_n) return FPM_OK;
     if (int rc = set_device(job->ctx)) return rc;
     uint32_t v = 0;
     HIP_TRY(hipDeviceSynchronize());
@@ -1054,9 +700,9 @@ int fpm_sketch_job_set_min_copies(fpm_sketch_job *job, uint32_t min_copies)
 static int reads_round(fpm_sketch_job *job, fpm_sketch_job *wide, uint32_t round, hipStream_t st)
 {
     fpm_ctx *ctx = job->ctx;
-    const uint32_t m = job->min_copies, s = job->kp.s, S = wide->kp.s, ng = job->n_groups;
+    const uint32_t m = job->min_copies, s = job->kp.s, S = wide->kp.s, ng = job->plan.n_groups;
     if (int rc = fpm_sketch_run(wide, st)) return rc;
-    job->reads_sampled = (int32_t)wide->n_slots;
+    job->reads_sampled = (int32_t)wide->plan.n_slots;
     // per wide-row entry: a u32 count and min_copies u64 position slots, from the context's
     // pool of released buffers (no device-wide allocation per round once it is warm)
     const size_t n_ent = (size_t)ng * S;
@@ -1076,26 +722,27 @@ static int reads_round(fpm_sketch_job *job, fpm_sketch_job *wide, uint32_t round
         HIP_TRY(tmp.get_pooled(&d_slots, slots_bytes));
         HIP_TRY(hipMemsetAsync(d_wcnt, 0, n_ent * sizeof(uint32_t), st));
         HIP_TRY(hipMemsetAsync(d_slots, 0xff, n_ent * m * sizeof(unsigned long long), st));
-        for (int c = 0; c < kTileClasses; c++) {
-            const uint32_t b = wide->class_begin[c], n = wide->class_begin[c + 1] - b;
-            if (!n) continue;
-            TimedLaunch tl(ctx, FPM_K_SKETCH, st);
-            HIP_TRY(launch_reads_count(c, wide->d_seq, wide->d_tiles + b, n, wide->kp, wide->d_rows,
-                                       wide->d_count, m, d_wcnt, d_slots, st));
-            tl.done();
-        }
+        const uint32_t *cb = wide->plan.class_begin;
+        if (int rc = for_each_class(cb, [&](int c, uint32_t b, uint32_t n) -> int {
+                TimedLaunch tl(ctx, FPM_K_SKETCH, st);
+                HIP_TRY(launch_reads_count(c, wide->d_seq, wide->d_tiles + b, n, wide->kp,
+                                           wide->d_rows, wide->d_count, m, d_wcnt, d_slots, st));
+                tl.done();
+                return FPM_OK;
+            }))
+            return rc;
         HIP_TRY(launch_reads_filter(wide->d_rows, wide->d_count, S, ng, d_wcnt, d_slots, m, s, round,
                                     job->d_rdone, job->d_rrows, job->d_rcount, job->d_rmult,
                                     job->d_rttop, st));
-        for (int c = 0; c < kTileClasses; c++) {
-            const uint32_t b = wide->class_begin[c], n = wide->class_begin[c + 1] - b;
-            if (!n) continue;
-            TimedLaunch tl(ctx, FPM_K_SKETCH, st);
-            HIP_TRY(launch_reads_maxcount(c, wide->d_seq, wide->d_tiles + b, n, wide->kp, s, round,
-                                          job->d_rdone, job->d_rrows, job->d_rcount, job->d_rmult,
-                                          job->d_rttop, st));
-            tl.done();
-        }
+        if (int rc = for_each_class(cb, [&](int c, uint32_t b, uint32_t n) -> int {
+                TimedLaunch tl(ctx, FPM_K_SKETCH, st);
+                HIP_TRY(launch_reads_maxcount(c, wide->d_seq, wide->d_tiles + b, n, wide->kp, s,
+                                              round, job->d_rdone, job->d_rrows, job->d_rcount,
+                                              job->d_rmult, job->d_rttop, st));
+                tl.done();
+                return FPM_OK;
+            }))
+            return rc;
         // the one host read of the round: which groups are final
         HIP_TRY(hipMemcpyAsync(job->h_rdone.data(), job->d_rdone, ng * sizeof(uint32_t),
                                hipMemcpyDeviceToHost, st));
@@ -1113,7 +760,7 @@ int fpm_sketch_reads_run(fpm_sketch_job *job, void *stream)
     fpm_ctx *ctx = job->ctx;
     if (int rc = set_device(ctx)) return rc;
     hipStream_t st = pick_stream(ctx, stream);
-    const uint64_t s = job->kp.s, ng = job->n_groups;
+    const uint64_t s = job->kp.s, ng = job->plan.n_groups;
     job->reads_rounds = 0;
     if (!ng) return FPM_OK;
     if (!job->d_rrows) {
@@ -1157,7 +804,7 @@ int fpm_sketch_reads_run(fpm_sketch_job *job, void *stream)
             if (int rc = reads_round(job, job, round, st)) return rc;
         } else {
             StageRecords R;
-            R.n_groups = job->n_groups;
+            R.n_groups = job->plan.n_groups;
             R.pos = job->recs.pos;
             R.len = job->recs.len;
             R.group = job->recs.group;
@@ -1191,7 +838,7 @@ int fpm_sketch_reads_fetch(fpm_sketch_job *job, uint64_t *out_hashes, uint32_t *
     if (job->reads_rounds < 0) return fail(FPM_EINVAL, "reads_fetch before reads_run");
     fpm_ctx *ctx = job->ctx;
     if (int rc = set_device(ctx)) return rc;
-    const size_t s = job->kp.s, ng = job->n_groups;
+    const size_t s = job->kp.s, ng = job->plan.n_groups;
     if (!ng) return FPM_OK;
     HIP_TRY(hipDeviceSynchronize());
     std::vector<uint32_t> cnt(ng);
@@ -1222,7 +869,7 @@ int fpm_sketch_job_reads_rounds(fpm_sketch_job *job, int32_t *n_rounds, uint32_t
     if (!job || !n_rounds) return fail(FPM_EINVAL, "null argument");
     *n_rounds = job->reads_rounds;
     if (group_round && job->reads_rounds >= 0)
-        for (uint32_t g = 0; g < job->n_groups; g++) group_round[g] = job->h_rdone[g];
+        for (uint32_t g = 0; g < job->plan.n_groups; g++) group_round[g] = job->h_rdone[g];
     return FPM_OK;
 }
 

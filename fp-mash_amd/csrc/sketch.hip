@@ -379,7 +379,7 @@ __device__ __forceinline__ uint32_t tile_hash(const TileDesc &td, const SketchKP
 // and no shared area sent 2.7 % of C5's tiles to the redo pass.)
 constexpr int kSurv = 2;
 constexpr int kSurvShared = 512;
-static_assert(kBlock * kSurv + kSurvShared == (int)kThrTileKeys, "fpm_sketch_api.cpp sizes thr4 by it");
+static_assert(kBlock * kSurv + kSurvShared == (int)kThrTileKeys, "sketch_plan.cpp sizes thr4 by it");
 // One tile: the body of sketch_tiles_kernel (one workgroup per tile) and of
 // sketch_redo_kernel (the tiles a THR pass listed, taken in turn by a fixed grid).
 template <int P, int K, bool THR>
@@ -1414,7 +1414,7 @@ __global__ __launch_bounds__(kMBlock) void merge_lds_kernel(const MergeDesc *__r
 // memory instead (same results; the host's size estimate only steers speed).
 constexpr int kSBlock = 256, kSWaves = kSBlock / 64;
 constexpr uint32_t kSCap = 2048;
-uint32_t merge_small_cap() { return kSCap; }
+static_assert(kSCap == kMergeSmallCap, "sketch_plan.cpp routes merge rounds by it");
 
 __device__ __forceinline__ uint32_t block_exscan_s(uint32_t v, uint32_t *tmp, uint32_t *total)
 {
@@ -1518,7 +1518,7 @@ __global__ __launch_bounds__(kSBlock) void merge_small_kernel(const MergeDesc *_
 constexpr int kSelThreads = 1024;
 constexpr uint32_t kSelCap = 15360;                      // keys staged in LDS (120 KiB)
 constexpr int kSelPer = (kSelCap + kSelThreads - 1) / kSelThreads;   // 15 per thread
-uint32_t group_select_cap() { return kSelCap; }
+static_assert(kSelCap == kGroupSelectCap, "sketch_plan.cpp decides on selections by it");
 
 __device__ __forceinline__ uint32_t bits_of(uint64_t x) { return x ? 64 - __clzll(x) : 0; }
 

@@ -8,8 +8,9 @@ Every sketch is compared with oracle.sketch_batch, bit-exact on hashes and multi
 (reads mode: with tests/reads_model.py).  The tests that stand on a route assert it through
 SketchJob.plan() (fpm_sketch_job_plan) and the run's hooks, so a moved threshold fails here
 instead of moving the coverage.  The inputs come from plain builder functions; the unmarked
-tests at the end check the builders' own promises on the CPU (a restatement of the host's
-tile cut, sample rule and merge rounds; the oracle's hashes), without a device.
+tests at the end check the builders' own promises on the CPU (a restatement of the planner's
+tile cut, sample rule and merge rounds, csrc/sketch_plan.cpp, which tests/test_sketchplan_host.py
+compares with the planner itself; the oracle's hashes), without a device.
 """
 import functools
 import itertools
@@ -24,13 +25,13 @@ gpu = pytest.mark.gpu
 
 CAPS = (256, 512, 1024, 2048, 4096, 8192)      # k-mer starts per tile class (kTileCap)
 PACK, CHUNK = 2048, 4096                        # kPackKmers, kChunkKmers
-SMALL_CAP = 2048                                # merge_small_cap()
-SEL_CAP = 15360                                 # group_select_cap()
+SMALL_CAP = 2048                                # kMergeSmallCap
+SEL_CAP = 15360                                 # kGroupSelectCap
 THR_KEYS, SURV, SURV_SHARED = 1024, 2, 512      # kThrTileKeys = 256 * kSurv + kSurvShared
 INVALID = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
-# ---- the host's staging rules, restated (fpm_sketch_api.cpp: stage_core) -----------------------
+# ---- the host's staging rules, restated (csrc/sketch_plan.cpp: plan_sketch) --------------------
 
 def tile_class(starts):
     return next(c for c, cap in enumerate(CAPS) if starts <= cap)
