@@ -466,7 +466,7 @@ hipError_t launch_tax_clade(const TaxTree &t, const uint32_t *d_tax_hashes,
                             const uint32_t *d_tax_count, uint32_t *d_clade_hashes,
                             uint32_t *d_clade_count, hipStream_t st);
 
-// kfinger (kfinger.hip): CFL k-fingers of sequence records, one lane per line.  A workgroup
+// kfinger (kfinger.hip): CFL / ICFL / CFL_ICFL k-fingers of sequence records, one lane per line.  A workgroup
 // takes one descriptor: kind 0, the window starts [start, start + count) of record rec (its
 // length >= the window); kind 1, the records rec .. rec + count - 1, each shorter than the window
 // (one line each) and together at most kKfStage bytes.  count <= kKfRun; the descriptor's lines
@@ -479,13 +479,38 @@ struct KfDesc {
     uint64_t line_base;
     uint32_t rec, start, count, kind;
 };
+// The factorization of a window (FPM_KF_* of fpmash.h): Duval's Lyndon factors; the inverse
+// Lyndon factors (ICFL); or the Lyndon factors with every one longer than `threshold` (1 ..
+// kKfMaxWindow) replaced by its own inverse Lyndon factors (CFL_ICFL).  ICFL keeps, per lane,
+// one entry and one bit per window position: in LDS, u8 entries, for windows up to kKfLdsWindow
+// (kf_lds_work_bytes per workgroup, 54 KB at the bound; 29 KB at w = 100), and beyond it in
+// `work`, u16 entries, work_groups regions of kf_wide_work_bytes(w), one per workgroup of a
+// grid that is no larger (the caller sizes it: kf_wide_groups).  A kind or threshold outside
+// these, or a wide window without `work`, is hipErrorInvalidValue from every launch below.
+constexpr uint32_t kKfCfl = 0, kKfIcfl = 1, kKfCflIcfl = 2;
+constexpr uint32_t kKfLdsWindow = 192;    // entries < 256 fit u8 and the workgroup's LDS 64 KB
+struct KfFact {
+    uint32_t kind = kKfCfl, threshold = 0;
+    void *work = nullptr;
+    uint32_t work_groups = 0;
+};
+constexpr uint32_t kf_lds_work_bytes(uint32_t w) { return kKfRun * ((w + 31) / 32 * 4 + w); }
+constexpr size_t kf_wide_work_bytes(uint32_t w)
+{
+    return (size_t)kKfRun * ((w + 31) / 32 * 4 + (size_t)w * 2);
+}
+// workgroups of a wide-window grid: two per compute unit, no more than there are descriptors
+constexpr uint32_t kf_wide_groups(uint32_t n_desc, uint32_t n_cu)
+{
+    return n_desc < 2 * n_cu ? n_desc : 2 * n_cu;
+}
 // pass one: per line its hash (u32, or u64 with use64), factor count and the text bytes after
 // its ID; *d_val_total (zeroed by the caller) += the factors of all lines
 hipError_t launch_kf_hash(const uint8_t *d_seq, const uint64_t *d_rec_pos,
                           const uint32_t *d_rec_len, const KfDesc *d_descs, uint32_t n_desc,
                           uint32_t w, uint32_t seed, uint32_t use64, void *d_hash,
                           uint32_t *d_n_vals, uint32_t *d_body, unsigned long long *d_val_total,
-                          hipStream_t st);
+                          const KfFact &f, hipStream_t st);
 // size[line] = body[line] + id_len[its record]; *d_text_total (zeroed by the caller) += the sum
 hipError_t launch_kf_text_size(const KfDesc *d_descs, uint32_t n_desc, const uint32_t *d_body,
                                const uint32_t *d_id_len, uint32_t *d_size,
@@ -494,12 +519,13 @@ hipError_t launch_kf_text_size(const KfDesc *d_descs, uint32_t n_desc, const uin
 // lengths as u16, or the text lines (record r's ID: d_ids[d_id_off[r] .. + d_id_len[r]))
 hipError_t launch_kf_values(const uint8_t *d_seq, const uint64_t *d_rec_pos,
                             const uint32_t *d_rec_len, const KfDesc *d_descs, uint32_t n_desc,
-                            uint32_t w, const uint32_t *d_off, uint16_t *d_vals, hipStream_t st);
+                            uint32_t w, const uint32_t *d_off, uint16_t *d_vals, const KfFact &f,
+                            hipStream_t st);
 hipError_t launch_kf_text(const uint8_t *d_seq, const uint64_t *d_rec_pos,
                           const uint32_t *d_rec_len, const KfDesc *d_descs, uint32_t n_desc,
                           uint32_t w, const uint32_t *d_off, const uint8_t *d_ids,
                           const uint64_t *d_id_off, const uint32_t *d_id_len, uint8_t *d_out,
-                          hipStream_t st);
+                          const KfFact &f, hipStream_t st);
 
 // The transposed grid of a rectangular compare (fpm_refset_dist_mirror_dev): cell (r, q) at
 // r * n_qry + q holds the pair "query r of the ref set against ref q of the query set".  For

@@ -1,6 +1,6 @@
-// fpm_kfinger_api.cpp — the k-finger part of the C ABI declared in include/fpmash.h: CFL
-// k-fingers of sequence records (kfinger.hip), their line hashes, and the lines as u16 values
-// or as text.
+// fpm_kfinger_api.cpp — the k-finger part of the C ABI declared in include/fpmash.h: CFL,
+// ICFL or CFL_ICFL k-fingers of sequence records (kfinger.hip), their line hashes, and the
+// lines as u16 values or as text.
 #include "fpm_internal.hpp"
 
 #include <memory>
@@ -11,6 +11,8 @@ struct fpm_kfinger {
     uint64_t n_in = 0;                       // input records (taken or not)
     uint64_t n_lines = 0;
     bool ran = false;
+    KfFact fact;                             // CFL unless fpm_kfinger_set_factorization said else;
+                                             // its work: the wide windows' ICFL memory (pooled)
     hipStream_t stream = nullptr;            // the last run's
     std::vector<uint64_t> rec_first_line;    // n_in + 1
     std::vector<uint32_t> src;               // input record of each kept record
@@ -121,6 +123,22 @@ int plan(fpm_kfinger *j, const std::vector<uint64_t> &pos, const std::vector<uin
 
 bool window_ok(uint32_t w) { return w >= 1 && w <= kKfMaxWindow; }
 
+// ICFL's working memory for windows past kKfLdsWindow: one region per workgroup of a grid of
+// two workgroups per compute unit, whatever the job's line count
+int wide_work(fpm_kfinger *j)
+{
+    if (j->fact.kind == kKfCfl || j->window <= kKfLdsWindow || j->fact.work || !j->n_desc)
+        return FPM_OK;
+    int n_cu = 0;
+    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, j->ctx->device));
+    const uint32_t groups = kf_wide_groups(j->n_desc, (uint32_t)std::max(n_cu, 1));
+    uint8_t *work = nullptr;
+    HIP_TRY(j->mem.get_pooled(&work, groups * kf_wide_work_bytes(j->window)));
+    j->fact.work = work;
+    j->fact.work_groups = groups;
+    return FPM_OK;
+}
+
 // the exclusive scan of d_size into d_off (both per line), on the job's stream
 int scan_sizes(fpm_kfinger *j, hipStream_t st)
 {
@@ -182,18 +200,35 @@ int fpm_kfinger_stage_seq(fpm_ctx *ctx, fpm_seqtext *seq, const uint8_t *take, u
     return FPM_OK;
 }
 
+int fpm_kfinger_set_factorization(fpm_kfinger *j, uint32_t kind, uint32_t threshold)
+{
+    static_assert(FPM_KF_CFL == kKfCfl && FPM_KF_ICFL == kKfIcfl && FPM_KF_CFL_ICFL == kKfCflIcfl,
+                  "fpmash.h states the factorization kinds");
+    if (!j) return fail(FPM_EINVAL, "kfinger_set_factorization: null job");
+    if (j->ran) return fail(FPM_EINVAL, "kfinger_set_factorization: the job has run");
+    if (kind != FPM_KF_CFL && kind != FPM_KF_ICFL && kind != FPM_KF_CFL_ICFL)
+        return fail(FPM_EINVAL, "kfinger_set_factorization: unknown kind");
+    if (kind == FPM_KF_CFL_ICFL && !window_ok(threshold))
+        return fail(FPM_EINVAL, "kfinger_set_factorization: threshold out of range");
+    j->fact.kind = kind;
+    j->fact.threshold = kind == FPM_KF_CFL_ICFL ? threshold : 0;
+    return FPM_OK;
+}
+
 int fpm_kfinger_run(fpm_kfinger *j, uint32_t seed, uint32_t use64, void *stream)
 {
     if (!j) return fail(FPM_EINVAL, "kfinger_run: null job");
     fpm_ctx *ctx = j->ctx;
     if (int rc = set_device(ctx)) return rc;
+    if (int rc = wide_work(j)) return rc;
     hipStream_t st = pick_stream(ctx, stream);
     j->stream = st;
     j->use64 = use64 ? 1 : 0;
     HIP_TRY(hipMemsetAsync(j->d_totals, 0, 16, st));
     TimedLaunch tl(ctx, FPM_K_KFINGER, st);
     HIP_TRY(launch_kf_hash(j->d_seq, j->d_rec_pos, j->d_rec_len, j->d_desc, j->n_desc, j->window,
-                           seed, j->use64, j->d_hash, j->d_n_vals, j->d_body, j->d_totals, st));
+                           seed, j->use64, j->d_hash, j->d_n_vals, j->d_body, j->d_totals, j->fact,
+                           st));
     tl.done();
     j->ran = true;
     return FPM_OK;
@@ -258,7 +293,7 @@ int fpm_kfinger_values(fpm_kfinger *j, uint64_t *val_off, uint16_t *vals, uint64
         j->d_size = keep;
         if (rc) return rc;
         HIP_TRY(launch_kf_values(j->d_seq, j->d_rec_pos, j->d_rec_len, j->d_desc, j->n_desc,
-                                 j->window, j->d_off, d_vals, st));
+                                 j->window, j->d_off, d_vals, j->fact, st));
         tl.done();
     }
     HIP_TRY(hipStreamSynchronize(st));
@@ -333,7 +368,7 @@ int fpm_kfinger_text(fpm_kfinger *j, const char *ids, const uint64_t *id_off, ch
     TimedLaunch tl(ctx, FPM_K_KFINGER_OUT, st);
     if (int rc = scan_sizes(j, st)) return rc;
     HIP_TRY(launch_kf_text(j->d_seq, j->d_rec_pos, j->d_rec_len, j->d_desc, j->n_desc, j->window,
-                           j->d_off, j->d_ids, j->d_id_off, j->d_id_len, d_out, st));
+                           j->d_off, j->d_ids, j->d_id_off, j->d_id_len, d_out, j->fact, st));
     tl.done();
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(d2h_staged(ctx, out, d_out, tot));

@@ -12,8 +12,21 @@
 // the line's text takes after its ID.  Pass two (kf_emit_kernel), after an exclusive scan of the
 // per-line sizes, runs Duval again and writes the u16 lengths or the text line at the line's
 // offset.  Nothing is stored per factor between the passes.
+//
+// ICFL and CFL_ICFL-T (lyn2vec `--type_factorization ICFL` / `CFL_ICFL-T`; factorizations.py:
+// 143-169 ICFL_recursive, 172-189 find_pre, 212-232 find_bre, 235-248 border, 265-301 CFL_icfl)
+// run in the same two passes through the same emit callbacks.  The inverse Lyndon factorization
+// is not streaming: each lane keeps, per window position, one entry (the border array of the
+// step under way; behind it the `last` of every finished step, at the step's start) and one bit
+// (where a step's piece ends; the right-to-left merge clears the bits of glued pieces, and what
+// is left are the factor boundaries, read left to right).  Windows up to kKfLdsWindow keep that
+// in LDS, u8 entries, lane-interleaved; wider ones in a device buffer of u16 entries, one region
+// per resident workgroup, which then walks the descriptors in a grid-stride loop.
 #include "fpm_device.hpp"
 #include "fpm_kernels.hpp"
+
+#include <algorithm>
+#include <type_traits>
 
 namespace fpm {
 
@@ -52,6 +65,148 @@ __device__ __forceinline__ void kf_duval(const uint8_t *s, uint32_t n, Emit emit
 __device__ __forceinline__ uint32_t kf_digits(uint32_t v)   // v <= kKfMaxWindow < 10000
 {
     return 1 + (v >= 10) + (v >= 100) + (v >= 1000);
+}
+
+// where a lane's ICFL working memory is: entry e and bit word i of lane t lie kKfRun entries
+// apart, at a[e * kKfRun] and bits[i * kKfRun] (both pointers already at the lane)
+template <typename E>
+struct KfWork {
+    E *a;
+    uint32_t *bits;
+    __device__ __forceinline__ uint32_t get(uint32_t e) const { return a[(size_t)e * kKfRun]; }
+    __device__ __forceinline__ void set(uint32_t e, uint32_t v) const
+    {
+        a[(size_t)e * kKfRun] = (E)v;
+    }
+    __device__ __forceinline__ uint32_t &word(uint32_t i) const
+    {
+        return bits[(size_t)i * kKfRun];
+    }
+};
+
+// The inverse Lyndon factorization of s[0 .. n) (ICFL_recursive, factorizations.py:143-169, as a
+// loop), bytes compared unsigned, the end of the word known from n; emit(len) per factor, left
+// to right.  wk: n entries (values < n) and (n + 31) / 32 bit words.
+// Forward: from step start st, scan while the bytes descend (find_pre); where the scan stops at
+// j before the end, build the border array of s[st .. st + j) at entries st .. st + j - 1,
+// walk its chain from the longest border down to 0 and keep as `last` the shortest border whose
+// next byte is below s[st + j], the longest border when none is (find_bre); the step's piece
+// is s[st .. st + j - last).  Every
+// step takes at least one byte, so the entries of finished steps (one each, at the step's
+// start) lie below st, and st + j < n.
+// Backward: the piece of a step starts a new factor when the factor behind it is longer than
+// the step's `last`, else it is glued onto that factor.
+template <typename E, typename Emit>
+__device__ __forceinline__ void kf_icfl(const uint8_t *s, uint32_t n, const KfWork<E> &wk,
+                                        Emit emit)
+{
+    if (!n) return;
+    const uint32_t nw = (n + 31) / 32;
+    for (uint32_t i = 0; i < nw; i++) wk.word(i) = 0;
+    uint32_t st = 0;
+    for (;;) {
+        const uint8_t *w = s + st;
+        const uint32_t m = n - st;
+        uint32_t i = 0, j = 1;
+        while (j < m) {
+            const uint8_t a = w[i], b = w[j];
+            if (b > a) break;
+            i = b < a ? 0 : i + 1;
+            j++;
+        }
+        if (j >= m) break;                       // the rest is the last factor
+        wk.set(st, 0);
+        uint32_t k = 0;
+        for (uint32_t e = 1; e < j; e++) {
+            const uint8_t c = w[e];
+            while (k > 0 && w[k] != c) k = wk.get(st + k - 1);
+            if (w[k] == c) k++;
+            wk.set(st + e, k);
+        }
+        uint32_t b = wk.get(st + j - 1), last = b;
+        const uint8_t c = w[j];
+        for (;;) {
+            if (w[b] < c) last = b;
+            if (!b) break;
+            b = wk.get(st + b - 1);
+        }
+        wk.set(st, last);
+        st += j - last;                          // 1 <= j - last, st < n
+        wk.word(st >> 5) |= 1u << (st & 31);
+    }
+    uint32_t cur = n - st, hi = st;
+    while (hi) {
+        // the start of the step whose piece ends at hi: the highest bit below hi, or 0
+        const uint32_t q = hi - 1;
+        uint32_t wd = q >> 5;
+        uint32_t v = wk.word(wd) & (0xFFFFFFFFu >> (31 - (q & 31)));
+        while (!v && wd) v = wk.word(--wd);
+        const uint32_t lo = v ? wd * 32 + 31 - (uint32_t)__clz((int)v) : 0;
+        if (cur > wk.get(lo)) {
+            cur = hi - lo;
+        } else {
+            cur += hi - lo;
+            wk.word(hi >> 5) &= ~(1u << (hi & 31));
+        }
+        hi = lo;
+    }
+    uint32_t prev = 0;
+    for (uint32_t wd = 0; wd < nw; wd++) {
+        uint32_t v = wk.word(wd);
+        while (v) {
+            const uint32_t p = wd * 32 + (uint32_t)__ffs((int)v) - 1;
+            v &= v - 1;
+            emit(p - prev);
+            prev = p;
+        }
+    }
+    emit(n - prev);
+}
+
+// how a kernel instance factorizes: Duval alone (the instances CFL has always had), or ICFL /
+// CFL_ICFL with the working memory in LDS, or in the device buffer
+enum : int { kKfModeCfl = 0, kKfModeLds = 1, kKfModeWide = 2 };
+
+template <int MODE>
+using KfWorkOf = KfWork<typename std::conditional<MODE == kKfModeWide, uint16_t, uint8_t>::type>;
+
+// the lane's working memory.  LDS (dynamic, kf_lds_work_bytes(w)): the bit words of all lanes,
+// then the u8 entries.  Wide: the same with u16 entries, in region `group` of `work`.
+template <int MODE>
+__device__ __forceinline__ KfWorkOf<MODE> kf_work(uint32_t w, uint8_t *work, uint32_t group)
+{
+    KfWorkOf<MODE> wk{nullptr, nullptr};
+    const uint32_t nw = (w + 31) / 32;
+    if constexpr (MODE == kKfModeLds) {
+        extern __shared__ uint32_t s_work[];
+        wk.bits = s_work + threadIdx.x;
+        wk.a = reinterpret_cast<uint8_t *>(s_work + (size_t)nw * kKfRun) + threadIdx.x;
+    } else if constexpr (MODE == kKfModeWide) {
+        uint8_t *base = work + (size_t)group * kf_wide_work_bytes(w);
+        wk.bits = reinterpret_cast<uint32_t *>(base) + threadIdx.x;
+        wk.a = reinterpret_cast<uint16_t *>(base + (size_t)nw * kKfRun * 4) + threadIdx.x;
+    }
+    return wk;
+}
+
+// the factor lengths of s[0 .. n): thr 0, ICFL; else CFL_ICFL-thr, a Lyndon factor longer than
+// thr replaced by its own ICFL factors (CFL_icfl, factorizations.py:265-301)
+template <int MODE, typename Emit>
+__device__ __forceinline__ void kf_factorize(const uint8_t *s, uint32_t n, uint32_t thr,
+                                             const KfWorkOf<MODE> &wk, Emit emit)
+{
+    if constexpr (MODE == kKfModeCfl) {
+        kf_duval(s, n, emit);
+    } else if (!thr) {
+        kf_icfl(s, n, wk, emit);
+    } else {
+        uint32_t at = 0;
+        kf_duval(s, n, [&](uint32_t len) {
+            if (len <= thr) emit(len);
+            else kf_icfl(s + at, len, wk, emit);
+            at += len;
+        });
+    }
 }
 
 // Stage the descriptor's bytes in s_seq.  On return the lane's window is s_seq[base .. base + n)
@@ -120,16 +275,14 @@ __device__ __forceinline__ unsigned long long kf_block_sum(unsigned long long v,
 
 // Pass one.  hash: u32 or u64 per line; n_vals: factors per line; body: the text bytes of the
 // line after its ID (" <len>" per factor and the '\n'); *val_total += the factors of all lines.
-__global__ __launch_bounds__(kKfRun) void kf_hash_kernel(
+template <int MODE>
+__device__ __forceinline__ void kf_hash_desc(
     const uint8_t *__restrict__ seq, const uint64_t *__restrict__ rec_pos,
-    const uint32_t *__restrict__ rec_len, const KfDesc *__restrict__ descs, uint32_t w,
-    uint32_t seed, uint32_t use64, void *__restrict__ hash, uint32_t *__restrict__ n_vals,
-    uint32_t *__restrict__ body, unsigned long long *__restrict__ val_total)
+    const uint32_t *__restrict__ rec_len, const KfDesc &d, uint32_t w, uint32_t seed,
+    uint32_t use64, void *__restrict__ hash, uint32_t *__restrict__ n_vals,
+    uint32_t *__restrict__ body, unsigned long long *__restrict__ val_total, uint32_t thr,
+    const KfWorkOf<MODE> &wk, uint8_t *s_seq, uint32_t *s_off, unsigned long long *s_red)
 {
-    __shared__ uint8_t s_seq[kKfLds];
-    __shared__ uint32_t s_off[kKfRun];
-    __shared__ unsigned long long s_red[kKfRun / 64];
-    const KfDesc d = descs[blockIdx.x];
     uint32_t base, n, rec;
     const bool active = kf_stage(seq, rec_pos, rec_len, d, w, s_seq, s_off, base, n, rec);
     uint32_t cnt = 0;
@@ -138,7 +291,7 @@ __global__ __launch_bounds__(kKfRun) void kf_hash_kernel(
         uint64_t h1 = seed, h2 = seed, pend = 0;
         // Murmur over the lengths as little-endian u64 (hash.cpp:45-73): a 16-byte block per two
         // values, an odd last value as the 8-byte tail, 8 * count folded in at the end
-        kf_duval(s_seq + base, n, [&](uint32_t len) {
+        kf_factorize<MODE>(s_seq + base, n, thr, wk, [&](uint32_t len) {
             bytes += 1 + kf_digits(len);
             if (cnt & 1) mur_block(h1, h2, pend, len);
             else pend = len;
@@ -159,6 +312,32 @@ __global__ __launch_bounds__(kKfRun) void kf_hash_kernel(
     }
     const unsigned long long t = kf_block_sum(cnt, s_red);
     if (threadIdx.x == 0 && t) atomicAdd(val_total, t);
+}
+
+// One descriptor per workgroup; kKfModeWide: workgroup g owns region g of `work` and takes the
+// descriptors g, g + gridDim.x, ...
+template <int MODE>
+__global__ __launch_bounds__(kKfRun) void kf_hash_kernel(
+    const uint8_t *__restrict__ seq, const uint64_t *__restrict__ rec_pos,
+    const uint32_t *__restrict__ rec_len, const KfDesc *__restrict__ descs, uint32_t n_desc,
+    uint32_t w, uint32_t seed, uint32_t use64, void *__restrict__ hash,
+    uint32_t *__restrict__ n_vals, uint32_t *__restrict__ body,
+    unsigned long long *__restrict__ val_total, uint32_t thr, uint8_t *__restrict__ work)
+{
+    __shared__ uint8_t s_seq[kKfLds];
+    __shared__ uint32_t s_off[kKfRun];
+    __shared__ unsigned long long s_red[kKfRun / 64];
+    const KfWorkOf<MODE> wk = kf_work<MODE>(w, work, blockIdx.x);
+    if constexpr (MODE == kKfModeWide) {
+        // (kf_block_sum's barrier stands between one descriptor's reads of the stage and the
+        // next one's writes)
+        for (uint32_t b = blockIdx.x; b < n_desc; b += gridDim.x)
+            kf_hash_desc<MODE>(seq, rec_pos, rec_len, descs[b], w, seed, use64, hash, n_vals, body,
+                               val_total, thr, wk, s_seq, s_off, s_red);
+    } else {
+        kf_hash_desc<MODE>(seq, rec_pos, rec_len, descs[blockIdx.x], w, seed, use64, hash, n_vals,
+                           body, val_total, thr, wk, s_seq, s_off, s_red);
+    }
 }
 
 // size[line] = the line's text bytes: its record's ID (id_len, per record) + body[line];
@@ -183,17 +362,15 @@ __global__ __launch_bounds__(kKfRun) void kf_text_size_kernel(
 
 // Pass two.  TEXT: the line "<id> <len> <len> ...\n" at out + off[line], the ID copied from
 // ids[id_off[rec] .. + id_len[rec]); else the lengths as u16 at vals + off[line].
-template <bool TEXT>
-__global__ __launch_bounds__(kKfRun) void kf_emit_kernel(
+template <bool TEXT, int MODE>
+__device__ __forceinline__ void kf_emit_desc(
     const uint8_t *__restrict__ seq, const uint64_t *__restrict__ rec_pos,
-    const uint32_t *__restrict__ rec_len, const KfDesc *__restrict__ descs, uint32_t w,
+    const uint32_t *__restrict__ rec_len, const KfDesc &d, uint32_t w,
     const uint32_t *__restrict__ off, const uint8_t *__restrict__ ids,
     const uint64_t *__restrict__ id_off, const uint32_t *__restrict__ id_len,
-    uint8_t *__restrict__ out, uint16_t *__restrict__ vals)
+    uint8_t *__restrict__ out, uint16_t *__restrict__ vals, uint32_t thr,
+    const KfWorkOf<MODE> &wk, uint8_t *s_seq, uint32_t *s_off)
 {
-    __shared__ uint8_t s_seq[kKfLds];
-    __shared__ uint32_t s_off[kKfRun];
-    const KfDesc d = descs[blockIdx.x];
     uint32_t base, n, rec;
     if (!kf_stage(seq, rec_pos, rec_len, d, w, s_seq, s_off, base, n, rec)) return;
     const uint64_t line = d.line_base + threadIdx.x;
@@ -203,7 +380,7 @@ __global__ __launch_bounds__(kKfRun) void kf_emit_kernel(
         const uint32_t il = id_len[rec];
         for (uint32_t t = 0; t < il; t++) o[t] = id[t];
         o += il;
-        kf_duval(s_seq + base, n, [&](uint32_t len) {
+        kf_factorize<MODE>(s_seq + base, n, thr, wk, [&](uint32_t len) {
             const uint32_t nd = kf_digits(len);
             *o = ' ';
             uint32_t v = len;
@@ -216,20 +393,83 @@ __global__ __launch_bounds__(kKfRun) void kf_emit_kernel(
         *o = '\n';
     } else {
         uint16_t *o = vals + off[line];
-        kf_duval(s_seq + base, n, [&](uint32_t len) { *o++ = (uint16_t)len; });
+        kf_factorize<MODE>(s_seq + base, n, thr, wk, [&](uint32_t len) { *o++ = (uint16_t)len; });
     }
 }
+
+template <bool TEXT, int MODE>
+__global__ __launch_bounds__(kKfRun) void kf_emit_kernel(
+    const uint8_t *__restrict__ seq, const uint64_t *__restrict__ rec_pos,
+    const uint32_t *__restrict__ rec_len, const KfDesc *__restrict__ descs, uint32_t n_desc,
+    uint32_t w, const uint32_t *__restrict__ off, const uint8_t *__restrict__ ids,
+    const uint64_t *__restrict__ id_off, const uint32_t *__restrict__ id_len,
+    uint8_t *__restrict__ out, uint16_t *__restrict__ vals, uint32_t thr,
+    uint8_t *__restrict__ work)
+{
+    __shared__ uint8_t s_seq[kKfLds];
+    __shared__ uint32_t s_off[kKfRun];
+    const KfWorkOf<MODE> wk = kf_work<MODE>(w, work, blockIdx.x);
+    if constexpr (MODE == kKfModeWide) {
+        for (uint32_t b = blockIdx.x; b < n_desc; b += gridDim.x) {
+            kf_emit_desc<TEXT, MODE>(seq, rec_pos, rec_len, descs[b], w, off, ids, id_off, id_len,
+                                     out, vals, thr, wk, s_seq, s_off);
+            __syncthreads();   // every lane is done with the stage before the next one fills it
+        }
+    } else {
+        kf_emit_desc<TEXT, MODE>(seq, rec_pos, rec_len, descs[blockIdx.x], w, off, ids, id_off,
+                                 id_len, out, vals, thr, wk, s_seq, s_off);
+    }
+}
+
+namespace {
+
+// What a launch with factorization f over window w takes: the instance, its grid, its dynamic
+// LDS and the threshold the kernel sees (0: ICFL).  false: f is not a factorization, or a wide
+// window has descriptors and no working memory (a job without lines needs none and launches
+// nothing).
+struct KfShape {
+    int mode = kKfModeCfl;
+    uint32_t grid = 0, lds = 0, thr = 0;
+};
+
+bool kf_shape(const KfFact &f, uint32_t w, uint32_t n_desc, KfShape &sh)
+{
+    sh.grid = n_desc;
+    if (f.kind == kKfCfl) return true;
+    if (f.kind == kKfCflIcfl) {
+        if (f.threshold < 1 || f.threshold > kKfMaxWindow) return false;
+        sh.thr = f.threshold;
+    } else if (f.kind != kKfIcfl) {
+        return false;
+    }
+    if (w <= kKfLdsWindow) {
+        sh.mode = kKfModeLds;
+        sh.lds = kf_lds_work_bytes(w);
+        return true;
+    }
+    if (n_desc && (!f.work || !f.work_groups)) return false;
+    sh.mode = kKfModeWide;
+    sh.grid = std::min(n_desc, f.work_groups);
+    return true;
+}
+
+}  // namespace
 
 hipError_t launch_kf_hash(const uint8_t *d_seq, const uint64_t *d_rec_pos,
                           const uint32_t *d_rec_len, const KfDesc *d_descs, uint32_t n_desc,
                           uint32_t w, uint32_t seed, uint32_t use64, void *d_hash,
                           uint32_t *d_n_vals, uint32_t *d_body, unsigned long long *d_val_total,
-                          hipStream_t st)
+                          const KfFact &f, hipStream_t st)
 {
-    if (w < 1 || w > kKfMaxWindow) return hipErrorInvalidValue;
+    KfShape sh;
+    if (w < 1 || w > kKfMaxWindow || !kf_shape(f, w, n_desc, sh)) return hipErrorInvalidValue;
     if (!n_desc) return hipSuccess;
-    hipLaunchKernelGGL(kf_hash_kernel, dim3(n_desc), dim3(kKfRun), 0, st, d_seq, d_rec_pos,
-                       d_rec_len, d_descs, w, seed, use64, d_hash, d_n_vals, d_body, d_val_total);
+    auto kernel = sh.mode == kKfModeCfl   ? kf_hash_kernel<kKfModeCfl>
+                  : sh.mode == kKfModeLds ? kf_hash_kernel<kKfModeLds>
+                                          : kf_hash_kernel<kKfModeWide>;
+    hipLaunchKernelGGL(kernel, dim3(sh.grid), dim3(kKfRun), sh.lds, st, d_seq, d_rec_pos, d_rec_len,
+                       d_descs, n_desc, w, seed, use64, d_hash, d_n_vals, d_body, d_val_total,
+                       sh.thr, (uint8_t *)f.work);
     return hipGetLastError();
 }
 
@@ -243,31 +483,47 @@ hipError_t launch_kf_text_size(const KfDesc *d_descs, uint32_t n_desc, const uin
     return hipGetLastError();
 }
 
+namespace {
+
+// pass two of either form: the instance the factorization and the window call for
+template <bool TEXT>
+hipError_t kf_launch_emit(const uint8_t *d_seq, const uint64_t *d_rec_pos,
+                          const uint32_t *d_rec_len, const KfDesc *d_descs, uint32_t n_desc,
+                          uint32_t w, const uint32_t *d_off, const uint8_t *d_ids,
+                          const uint64_t *d_id_off, const uint32_t *d_id_len, uint8_t *d_out,
+                          uint16_t *d_vals, const KfFact &f, hipStream_t st)
+{
+    KfShape sh;
+    if (w < 1 || w > kKfMaxWindow || !kf_shape(f, w, n_desc, sh)) return hipErrorInvalidValue;
+    if (!n_desc) return hipSuccess;
+    auto kernel = sh.mode == kKfModeCfl   ? kf_emit_kernel<TEXT, kKfModeCfl>
+                  : sh.mode == kKfModeLds ? kf_emit_kernel<TEXT, kKfModeLds>
+                                          : kf_emit_kernel<TEXT, kKfModeWide>;
+    hipLaunchKernelGGL(kernel, dim3(sh.grid), dim3(kKfRun), sh.lds, st, d_seq, d_rec_pos, d_rec_len,
+                       d_descs, n_desc, w, d_off, d_ids, d_id_off, d_id_len, d_out, d_vals, sh.thr,
+                       (uint8_t *)f.work);
+    return hipGetLastError();
+}
+
+}  // namespace
+
 hipError_t launch_kf_values(const uint8_t *d_seq, const uint64_t *d_rec_pos,
                             const uint32_t *d_rec_len, const KfDesc *d_descs, uint32_t n_desc,
-                            uint32_t w, const uint32_t *d_off, uint16_t *d_vals, hipStream_t st)
+                            uint32_t w, const uint32_t *d_off, uint16_t *d_vals, const KfFact &f,
+                            hipStream_t st)
 {
-    if (w < 1 || w > kKfMaxWindow) return hipErrorInvalidValue;
-    if (!n_desc) return hipSuccess;
-    hipLaunchKernelGGL(kf_emit_kernel<false>, dim3(n_desc), dim3(kKfRun), 0, st, d_seq, d_rec_pos,
-                       d_rec_len, d_descs, w, d_off, (const uint8_t *)nullptr,
-                       (const uint64_t *)nullptr, (const uint32_t *)nullptr, (uint8_t *)nullptr,
-                       d_vals);
-    return hipGetLastError();
+    return kf_launch_emit<false>(d_seq, d_rec_pos, d_rec_len, d_descs, n_desc, w, d_off, nullptr,
+                                 nullptr, nullptr, nullptr, d_vals, f, st);
 }
 
 hipError_t launch_kf_text(const uint8_t *d_seq, const uint64_t *d_rec_pos,
                           const uint32_t *d_rec_len, const KfDesc *d_descs, uint32_t n_desc,
                           uint32_t w, const uint32_t *d_off, const uint8_t *d_ids,
                           const uint64_t *d_id_off, const uint32_t *d_id_len, uint8_t *d_out,
-                          hipStream_t st)
+                          const KfFact &f, hipStream_t st)
 {
-    if (w < 1 || w > kKfMaxWindow) return hipErrorInvalidValue;
-    if (!n_desc) return hipSuccess;
-    hipLaunchKernelGGL(kf_emit_kernel<true>, dim3(n_desc), dim3(kKfRun), 0, st, d_seq, d_rec_pos,
-                       d_rec_len, d_descs, w, d_off, d_ids, d_id_off, d_id_len, d_out,
-                       (uint16_t *)nullptr);
-    return hipGetLastError();
+    return kf_launch_emit<true>(d_seq, d_rec_pos, d_rec_len, d_descs, n_desc, w, d_off, d_ids,
+                                d_id_off, d_id_len, d_out, nullptr, f, st);
 }
 
 }  // namespace fpm

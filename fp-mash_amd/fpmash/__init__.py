@@ -4,6 +4,7 @@ A ctypes mirror of the reference's engine calls for this path:
   Sketch sketching (addMinHashes/MinHashHeap, Sketch.cpp:664-735, 1490-1517) -> Context.sketch
   -fp line hashing (getHashFingerPrint, hash.cpp:45-73)                    -> Context.fp_hash_lines
   lyn2vec CFL k-fingers (fingerprint_utils.py:95-110, 443-476) + their hashes -> Context.kfinger
+    (factorization="ICFL" / "CFL_ICFL-<T>": factorizations.py:143-248, 265-301)
   compare/compareSketches/pValue (CommandDistance.cpp:335-450)             -> Context.dist
   contain/containSketches (CommandContain.cpp:314-412)                     -> Context.contain
   screen: hashSequence, sums, -w, pValueWithin (CommandScreen.cpp:133-406) -> Context.screen
@@ -140,6 +141,7 @@ SYMBOLS = [
                                     C.POINTER(vp), u64p]),
     ("fpm_kfinger_stage_seq", C.c_int, [vp, vp, u8p, C.c_uint32, C.c_uint64, C.POINTER(vp),
                                         u64p]),
+    ("fpm_kfinger_set_factorization", C.c_int, [vp, C.c_uint32, C.c_uint32]),
     ("fpm_kfinger_run", C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
     ("fpm_kfinger_fetch", C.c_int, [vp, u64p, vp, u32p]),
     ("fpm_kfinger_device_output", C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), u64p, u32p]),
@@ -367,6 +369,29 @@ def kfinger_limits():
     w, r = C.c_uint32(), C.c_uint32()
     lib().fpm_kfinger_limits(C.byref(w), C.byref(r))
     return w.value, r.value
+
+
+KF_CFL, KF_ICFL, KF_CFL_ICFL = 0, 1, 2   # FPM_KF_*
+
+
+def parse_factorization(name: str, max_threshold=None):
+    """("CFL" | "ICFL" | "CFL_ICFL", T) of lyn2vec's --type_factorization spelling
+    (lyn2vec.py:47-59): CFL, ICFL or CFL_ICFL-<T> with T >= 1 in plain decimal digits (and at
+    most max_threshold, when given); ValueError for anything else."""
+    if name in ("CFL", "ICFL"):
+        return name, 0
+    head, sep, t = name.partition("-")
+    if head == "CFL_ICFL" and sep and t.isascii() and t.isdigit() and len(t) <= 9 and int(t) >= 1:
+        if max_threshold is None or int(t) <= max_threshold:
+            return head, int(t)
+    raise ValueError(f"unknown factorization {name!r}: CFL, ICFL or CFL_ICFL-<T>")
+
+
+def kfinger_factorization(name):
+    """(FPM_KF_* kind, threshold) of lyn2vec's spelling "CFL", "ICFL" or "CFL_ICFL-<T>"
+    (lyn2vec.py:47-59), T from 1 to the widest window; ValueError for anything else."""
+    kind, thr = parse_factorization(name, kfinger_limits()[0])
+    return {"CFL": KF_CFL, "ICFL": KF_ICFL, "CFL_ICFL": KF_CFL_ICFL}[kind], thr
 
 
 def kfinger_id(header: bytes) -> bytes:
@@ -1372,10 +1397,14 @@ class Context:
 
     # --- k-fingers from sequence ----------------------------------------------------
     @staticmethod
-    def _kfinger_out(job, n, n_rec, seed, use64, ids, values, text):
-        """run + fetch (+ the pass-two outputs) of a staged k-finger job; frees it"""
+    def _kfinger_out(job, n, n_rec, seed, use64, ids, values, text, fact=(KF_CFL, 0)):
+        """run + fetch (+ the pass-two outputs) of a staged k-finger job under the factorization
+        fact = (FPM_KF_* kind, threshold); frees it"""
         L = lib()
         try:
+            kind, thr = fact
+            if kind != KF_CFL:
+                _check(L.fpm_kfinger_set_factorization(job, kind, thr))
             _check(L.fpm_kfinger_run(job, seed, int(use64), None))
             first = np.zeros(n_rec + 1, np.uint64)
             h = np.zeros(max(n, 1), np.uint64 if use64 else np.uint32)
@@ -1405,25 +1434,28 @@ class Context:
             L.fpm_kfinger_free(job)
 
     def kfinger(self, seqs, window=100, seed=42, use64=False, max_lines=None, ids=None,
-                values=False, text=False):
-        """CFL k-fingers of the records `seqs` (lyn2vec --type basic --type_factorization CFL,
-        fingerprint_utils.py:95-110, 443-476) and their line hashes (hash.cpp:45-73), on the
-        device.  -> n_lines, rec_first_line (len(seqs) + 1), hash and n_vals per line; with
+                values=False, text=False, factorization="CFL"):
+        """k-fingers of the records `seqs` (lyn2vec --type basic --type_factorization CFL,
+        fingerprint_utils.py:95-110, 443-476; factorization "ICFL" or "CFL_ICFL-<T>" for lyn2vec's
+        factorizations of those names, fpm_kfinger_set_factorization) and their line hashes
+        (hash.cpp:45-73), on the device.  -> n_lines, rec_first_line (len(seqs) + 1), hash and n_vals per line; with
         values the factor lengths (vals u16, line l's at val_off[l] .. val_off[l + 1]); with
         text the lines' text, ids[r] being record r's full ID bytes (lyn2vec's "<id>_0").
         max_lines: only the first so many lines exist (None: all)."""
+        fact = kfinger_factorization(factorization)      # (refused before anything is staged)
         data, off = pack_records([bytes(s) for s in seqs])
         job, n = vp(), C.c_uint64()
         cap = 0xFFFFFFFFFFFFFFFF if max_lines is None else int(max_lines)
         _check(lib().fpm_kfinger_stage(self.h, data, _p(off, u64p), len(seqs), window, cap,
                                        C.byref(job), C.byref(n)))
-        return self._kfinger_out(job, n.value, len(seqs), seed, use64, ids, values, text)
+        return self._kfinger_out(job, n.value, len(seqs), seed, use64, ids, values, text, fact)
 
     def kfinger_fasta(self, files, take=None, window=100, seed=42, use64=False, max_lines=None,
-                      ids=None, values=False, text=False):
+                      ids=None, values=False, text=False, factorization="CFL"):
         """kfinger over the records of FASTA / FASTQ file images parsed on the device
         (fpm_seq_parse + fpm_kfinger_stage_seq); take[r] false leaves record r out.  ids None:
         each record's ID by kfinger_id of its header line.  Also returns the parse's records."""
+        fact = kfinger_factorization(factorization)
         seq_job, recs, quality = self.seq_parse(files)
         try:
             if quality:
@@ -1446,7 +1478,7 @@ class Context:
                                                C.byref(job), C.byref(n)))
         finally:
             lib().fpm_seq_free(seq_job)
-        res = self._kfinger_out(job, n.value, n_rec, seed, use64, ids, values, text)
+        res = self._kfinger_out(job, n.value, n_rec, seed, use64, ids, values, text, fact)
         res["records"] = recs
         return res
 

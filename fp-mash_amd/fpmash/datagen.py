@@ -79,7 +79,98 @@ def duval_cfl_lengths(word: bytes):
     return out
 
 
-def cfl_lines(seq: bytes, gid: str, window=100):
+def icfl_lengths(word: bytes, stats=None):
+    """Inverse Lyndon factor lengths of `word`: the iterative form of lyn2vec's ICFL_recursive
+    (factorizations.py:143-169 with find_pre :172-189, find_bre :212-232, border :235-248).
+    The end of the word is known out of band, so a 0x24 byte is a byte like any other.
+
+    Forward, from s = 0: scan word[s:] while it descends; where it stops at j before the end,
+    the step's `last` is the shortest border b of word[s:s+j] (0 included) whose next byte is
+    below word[s+j], or the longest border when none is; s advances by j - last.  The rest is the
+    last factor.  Then right to left: a step's piece starts a new factor when the factor after it
+    is longer than the step's `last`, and is glued onto that factor otherwise.
+
+    stats, a dict, accumulates over calls: "steps", "merges" (pieces glued), "chain" (the longest
+    border chain walked, in links) and "last" (the largest `last`)."""
+    n = len(word)
+    steps = []          # (start, last)
+    s = 0
+    chain_max = 0
+    while True:
+        w = word[s:]
+        m = n - s
+        i, j = 0, 1
+        while j < m and w[j] <= w[i]:
+            i = 0 if w[j] < w[i] else i + 1
+            j += 1
+        if j >= m:
+            break
+        f = [0] * j
+        k = 0
+        for e in range(1, j):
+            while k > 0 and w[k] != w[e]:
+                k = f[k - 1]
+            if w[k] == w[e]:
+                k += 1
+            f[e] = k
+        b = last = f[j - 1]
+        links = 1
+        while True:
+            if w[b] < w[j]:
+                last = b
+            if b == 0:
+                break
+            b = f[b - 1]
+            links += 1
+        chain_max = max(chain_max, links)
+        steps.append((s, last))
+        s += j - last
+    out = [n - s] if n else []
+    end = s
+    merges = 0
+    for start, last in reversed(steps):
+        if out[0] > last:
+            out.insert(0, end - start)
+        else:
+            out[0] += end - start
+            merges += 1
+        end = start
+    if stats is not None:
+        stats["steps"] = stats.get("steps", 0) + len(steps)
+        stats["merges"] = stats.get("merges", 0) + merges
+        stats["chain"] = max(stats.get("chain", 0), chain_max)
+        stats["last"] = max([stats.get("last", 0)] + [l for _, l in steps])
+    return out
+
+
+def cfl_icfl_lengths(word: bytes, T: int, stats=None):
+    """lyn2vec's CFL_icfl (factorizations.py:265-301) without its << >> markers
+    (fingerprint_utils.py:443-476 drops them): a Lyndon factor of at most T bytes is kept, a
+    longer one gives way to its own inverse Lyndon factors."""
+    out = []
+    k = 0
+    for ln in duval_cfl_lengths(word):
+        if ln <= T:
+            out.append(ln)
+        else:
+            out.extend(icfl_lengths(word[k:k + ln], stats))
+        k += ln
+    return out
+
+
+def factor_lengths(word: bytes, factorization="CFL", stats=None):
+    """the factor lengths of `word` under "CFL", "ICFL" or "CFL_ICFL-<T>" (the binding's
+    parse_factorization reads the name)"""
+    from . import parse_factorization
+    kind, T = parse_factorization(factorization)
+    if kind == "CFL":
+        return duval_cfl_lengths(word)
+    if kind == "ICFL":
+        return icfl_lengths(word, stats)
+    return cfl_icfl_lengths(word, T, stats)
+
+
+def cfl_lines(seq: bytes, gid: str, window=100, factorization="CFL"):
     """k-finger lines of one sequence (fingerprint_utils.py:95-110, 443-476)."""
     s = seq.upper()
     lines = []
@@ -89,15 +180,16 @@ def cfl_lines(seq: bytes, gid: str, window=100):
         ss = s + s[:window]
         shifts = [ss[i:i + window] for i in range(len(s))]
     for w in shifts:
-        lines.append(f"{gid}_0 " + " ".join(str(x) for x in duval_cfl_lengths(w)) + "\n")
+        lines.append(f"{gid}_0 " + " ".join(str(x) for x in factor_lengths(w, factorization)) + "\n")
     return lines
 
 
-def cfl_text(seqs, ids, window=100):
-    return "".join(l for s, i in zip(seqs, ids) for l in cfl_lines(s, "G00000" + i, window)).encode()
+def cfl_text(seqs, ids, window=100, factorization="CFL"):
+    return "".join(l for s, i in zip(seqs, ids)
+                   for l in cfl_lines(s, "G00000" + i, window, factorization)).encode()
 
 
-def cfl_text_fast(seqs, ids, window=100, threads=None):
+def cfl_text_fast(seqs, ids, window=100, threads=None, factorization="CFL"):
     """cfl_text through the C++ generator (bin/cflgen, same bytes): C3-scale inputs
     (5,000 x 2 kb -> 10 M lines) in seconds instead of minutes."""
     import os
@@ -105,4 +197,10 @@ def cfl_text_fast(seqs, ids, window=100, threads=None):
     exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bin", "cflgen")
     inp = b"".join(i.encode() + b"\t" + s + b"\n" for s, i in zip(seqs, ids))
     args = [exe, str(window)] + ([str(threads)] if threads else [])
+    if factorization != "CFL":
+        from . import parse_factorization
+        parse_factorization(factorization)
+        # cflgen takes the name third, so the thread count is always given: the CPUs at hand,
+        # 16 at the most
+        args = [exe, str(window), str(threads or min(os.cpu_count() or 1, 16)), factorization]
     return subprocess.run(args, input=inp, stdout=subprocess.PIPE, check=True).stdout

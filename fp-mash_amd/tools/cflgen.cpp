@@ -1,10 +1,13 @@
-// cflgen — synthetic CFL k-finger text at C3 scale (5,000 x 2 kb -> 10 M lines).
+// cflgen — synthetic CFL / ICFL / CFL_ICFL k-finger text at C3 scale (5,000 x
+// 2 kb -> 10 M lines).  cflgen <window> <threads> [CFL|ICFL|CFL_ICFL-<T>], CFL when not given.
 //
 // Same output as fpmash.datagen.cfl_text (lyn2vec `--type basic --type_factorization CFL`,
 // fingerprint_utils.py:95-110, 443-476; Duval, factorizations.py:102-126), which is pinned
 // byte for byte against the fork's DNA1-CFL.txt; the Python version takes ~47 ms per 2 kb
 // sequence, this one a few hundred microseconds.  Test tooling only (tests/test_cli.py checks
-// it against datagen); not part of libfpmash.
+// it against datagen); not part of libfpmash.  ICFL and CFL_ICFL-T restate
+// fpmash.datagen.icfl_lengths / cfl_icfl_lengths (lyn2vec's ICFL_recursive and CFL_icfl,
+// factorizations.py:143-248, 265-301, as loops; the end of the word out of band).
 //
 // stdin: one record per line, "<id>\t<sequence>".  stdout: for every record and every cyclic
 // window start (one window of the whole sequence when it is shorter than the window):
@@ -18,9 +21,58 @@
 #include <thread>
 #include <vector>
 
+// 0: CFL; -1: ICFL; T >= 1: CFL_ICFL-T
+static int g_fact = 0;
+
+static void put(int len, std::string &out) {
+    char num[16];
+    int m = snprintf(num, sizeof num, " %d", len);
+    out.append(num, m);
+}
+
+// the inverse Lyndon factor lengths of w[0 .. n) (datagen.icfl_lengths)
+static void icfl(const char *word, int n, std::string &out) {
+    const unsigned char *w0 = (const unsigned char *)word;
+    std::vector<int> start, last, f;
+    int s = 0;
+    for (;;) {
+        const unsigned char *w = w0 + s;
+        const int m = n - s;
+        int i = 0, j = 1;
+        while (j < m && w[j] <= w[i]) {
+            i = w[j] < w[i] ? 0 : i + 1;
+            ++j;
+        }
+        if (j >= m) break;
+        f.assign(j, 0);
+        for (int e = 1, k = 0; e < j; ++e) {
+            while (k > 0 && w[k] != w[e]) k = f[k - 1];
+            if (w[k] == w[e]) ++k;
+            f[e] = k;
+        }
+        int b = f[j - 1], l = b;
+        for (;;) {
+            if (w[b] < w[j]) l = b;
+            if (!b) break;
+            b = f[b - 1];
+        }
+        start.push_back(s);
+        last.push_back(l);
+        s += j - l;
+    }
+    // right to left: the factor lengths, last factor first
+    std::vector<int> len{n - s};
+    int end = s;
+    for (size_t k = start.size(); k-- > 0;) {
+        if (len.back() > last[k]) len.push_back(end - start[k]);
+        else len.back() += end - start[k];
+        end = start[k];
+    }
+    for (size_t k = len.size(); k-- > 0;) put(len[k], out);
+}
+
 static void duval(const char *w, int n, std::string &out) {
     int k = 0;
-    char num[16];
     while (k < n) {
         int i = k, j = k + 1;
         while (j < n && (unsigned char)w[i] <= (unsigned char)w[j]) {
@@ -29,10 +81,18 @@ static void duval(const char *w, int n, std::string &out) {
         }
         while (k <= i) {
             int len = j - i;
-            int m = snprintf(num, sizeof num, " %d", len);
-            out.append(num, m);
+            if (g_fact > 0 && len > g_fact) icfl(w + k, len, out);
+            else put(len, out);
             k += len;
         }
+    }
+}
+
+static void factorize(const char *w, int n, std::string &out) {
+    if (g_fact < 0) {
+        if (n) icfl(w, n, out);
+    } else {
+        duval(w, n, out);
     }
 }
 
@@ -41,14 +101,14 @@ static void record(const std::string &id, std::string seq, int window, std::stri
     const std::string head = "G00000" + id + "_0";
     if ((int)seq.size() < window) {
         out += head;
-        duval(seq.data(), (int)seq.size(), out);
+        factorize(seq.data(), (int)seq.size(), out);
         out += '\n';
         return;
     }
     std::string ss = seq + seq.substr(0, window);
     for (size_t i = 0; i < seq.size(); ++i) {
         out += head;
-        duval(ss.data() + i, window, out);
+        factorize(ss.data() + i, window, out);
         out += '\n';
     }
 }
@@ -56,6 +116,17 @@ static void record(const std::string &id, std::string seq, int window, std::stri
 int main(int argc, char **argv) {
     int window = argc > 1 ? atoi(argv[1]) : 100;
     int threads = argc > 2 ? atoi(argv[2]) : (int)std::max(1u, std::thread::hardware_concurrency());
+    if (argc > 3) {
+        const std::string f = argv[3];
+        const std::string t = f.rfind("CFL_ICFL-", 0) == 0 ? f.substr(9) : "";
+        if (f == "ICFL") g_fact = -1;
+        else if (!t.empty() && t.size() <= 9 && t.find_first_not_of("0123456789") == std::string::npos &&
+                 atoi(t.c_str()) >= 1) g_fact = atoi(t.c_str());
+        else if (f != "CFL") {
+            fprintf(stderr, "cflgen: unknown factorization %s\n", f.c_str());
+            return 1;
+        }
+    }
     std::ios::sync_with_stdio(false);
     std::vector<std::string> ids, seqs;
     std::string line;

@@ -402,6 +402,16 @@ void fpm_fp_text_limits(uint32_t *text_chunk, uint32_t *span_bytes, uint32_t *he
  * as fpm_sketch_stage_seq does (stage once per parse).
  * window outside 1 .. the limit of fpm_kfinger_limits, or a record of 2^32 bytes or more, is
  * FPM_EINVAL.
+ * fpm_kfinger_set_factorization (lyn2vec --type_factorization ICFL / CFL_ICFL-T: ICFL_recursive
+ * with find_pre, find_bre and border, factorizations.py:143-248, and CFL_icfl, :265-301, with the
+ * << >> markers dropped as fingerprint_utils.py:443-476 drops them), between stage and run: what
+ * a line's lengths are.  FPM_KF_CFL, the Lyndon factors, is what a job that never calls it
+ * makes; FPM_KF_ICFL, the inverse Lyndon factors of the window; FPM_KF_CFL_ICFL, the Lyndon
+ * factors with every one longer than `threshold` replaced by its own inverse Lyndon factors
+ * (threshold 1 .. the widest window; ignored for the other kinds).  The end of the window is
+ * known out of band: a 0x24 byte is a byte like any other, where lyn2vec's in-band '$' is not.
+ * Another kind, a threshold out of range, or a call after fpm_kfinger_run is FPM_EINVAL and
+ * leaves the job as it was.
  * fpm_kfinger_run (factorizations.py:102-126 + hash.cpp:45-73): pass one on `stream` (NULL: the
  * context's): per line the hash of its 8 x count little-endian bytes (u32, or u64 with use64:
  * what fpm_fp_hash_lines gives for the same values) and its value count.
@@ -423,6 +433,10 @@ int fpm_kfinger_stage(fpm_ctx *ctx, const char *seq, const uint64_t *rec_off, ui
                       uint32_t window, uint64_t max_lines, fpm_kfinger **job, uint64_t *n_lines);
 int fpm_kfinger_stage_seq(fpm_ctx *ctx, fpm_seqtext *seq, const uint8_t *take, uint32_t window,
                           uint64_t max_lines, fpm_kfinger **job, uint64_t *n_lines);
+#define FPM_KF_CFL 0
+#define FPM_KF_ICFL 1
+#define FPM_KF_CFL_ICFL 2
+int fpm_kfinger_set_factorization(fpm_kfinger *job, uint32_t kind, uint32_t threshold);
 int fpm_kfinger_run(fpm_kfinger *job, uint32_t seed, uint32_t use64, void *stream);
 int fpm_kfinger_fetch(fpm_kfinger *job, uint64_t *rec_first_line, void *hash, uint32_t *n_vals);
 int fpm_kfinger_device_output(fpm_kfinger *job, void **d_hash, uint32_t **d_n_vals,

@@ -1,0 +1,190 @@
+"""CPU tests of the ICFL and CFL_ICFL-T restatements (fpmash.datagen.icfl_lengths /
+cfl_icfl_lengths, bin/cflgen's third argument) against lyn2vec's own results in tests/golden/,
+and of the inputs tests/test_gpu_kfinger_fact.py runs: each constructed one sits on the edge it
+is named for, by the counters the restatement returns."""
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, ROOT
+import kfinger_fact_model as F
+import kfinger_model as M
+import seqio
+import fpmash
+from fpmash import datagen
+
+FPMASH = os.path.join(ROOT, "fp-mash_amd", "bin", "fpmash")
+
+
+def dna1(n=3):
+    recs = seqio.read_records(os.path.join(GOLDEN, "DNA1.fasta"))[:n]
+    return [s for _, _, s in recs], [M.line_id(h + b" " + c) for h, c, _ in recs]
+
+
+def test_restatements_equal_lyn2vec_on_the_golden_words():
+    g = json.loads(F.golden("icfl_words.json"))
+    assert g["thresholds"] == [1, 3, 10, 20, 30] and len(g["rows"]) == 2000
+    kinds = set()
+    for word, icfl, *by_t in g["rows"]:
+        w = word.encode("latin-1")
+        assert b"$" not in w and 1 <= len(w) <= 64
+        assert datagen.icfl_lengths(w) == [int(x) for x in icfl.split()], word
+        for T, want in zip(g["thresholds"], by_t):
+            assert datagen.cfl_icfl_lengths(w, T) == [int(x) for x in want.split()], (word, T)
+        st = {}
+        datagen.icfl_lengths(w, st)
+        kinds |= {k for k in ("steps", "merges", "last") if st[k]}
+        if st["chain"] >= 10:
+            kinds.add("chain")
+    # the words reach every branch of the restatement
+    assert kinds == {"steps", "merges", "last", "chain"}
+
+
+@pytest.mark.parametrize("fact, name", [("ICFL", "DNA1-ICFL.txt"),
+                                        ("CFL_ICFL-10", "DNA1-CFL_ICFL-10.txt")])
+def test_cfl_lines_reproduce_the_golden_texts(fact, name):
+    seqs, ids = dna1()
+    text = "".join(l for s, i in zip(seqs, ids)
+                   for l in datagen.cfl_lines(s, i[:-2].decode(), 100, factorization=fact))
+    assert text.encode() == F.golden(name)
+    # the model's two sources of lines, on the same input
+    assert F.Model(seqs, ids, 100, fact, fast=True).text == F.golden(name)
+    assert F.Model(seqs, ids, 100, fact, fast=False).text == F.golden(name)
+
+
+def test_default_factorization_is_cfl():
+    seq = F.rand(1, 150)
+    assert datagen.cfl_lines(seq, "g", 100) == datagen.cfl_lines(seq, "g", 100, factorization="CFL")
+    assert datagen.cfl_text([seq], ["x"]) == datagen.cfl_text([seq], ["x"], factorization="CFL")
+    assert datagen.cfl_text_fast([seq], ["x"]) == datagen.cfl_text([seq], ["x"])
+    for fact in F.FACTS:
+        assert datagen.cfl_text_fast([seq], ["x"], 17, factorization=fact) == \
+            datagen.cfl_text([seq], ["x"], 17, factorization=fact)
+
+
+@pytest.mark.parametrize("name", ["", "cfl", "ICFL-10", "CFL_ICFL", "CFL_ICFL-", "CFL_ICFL-0",
+                                  "CFL_ICFL--1", "CFL_ICFL-1x", "CFL_ICFL-+3", "CFL_ICFL- 3", "FOO"])
+def test_unknown_factorizations(name):
+    with pytest.raises(ValueError):
+        fpmash.parse_factorization(name)
+    p = subprocess.run([M.CFLGEN, "100", "1", name], input=b"a\tACGT\n", capture_output=True)
+    assert p.returncode == 1 and p.stdout == b""
+
+
+def test_cflgen_two_arguments_unchanged():
+    seq = F.rand(2, 230)
+    two = subprocess.run([M.CFLGEN, "100", "2"], input=b"x\t" + seq + b"\n",
+                         stdout=subprocess.PIPE, check=True).stdout
+    three = subprocess.run([M.CFLGEN, "100", "2", "CFL"], input=b"x\t" + seq + b"\n",
+                           stdout=subprocess.PIPE, check=True).stdout
+    assert two == three == datagen.cfl_text([seq], ["x"])
+
+
+@pytest.mark.parametrize("w", [1, 2, 3, 17, 100, 256, 4096])
+def test_cflgen_equals_the_restatement(w):
+    """random records around the window, ACGT and a two-letter alphabet (more merges), and the
+    constructed inputs; at w = 4096 records just under the window, one line each, the Python
+    side taking tens of milliseconds a line there"""
+    if w < 4096:
+        seqs = [F.rand(w + i, n, a) for i, (n, a) in enumerate(
+            [(1, b"AC"), (w + 1, b"AC"), (w + 40, b"ACGT"), (max(w - 1, 1), b"ACGTacgtN"),
+             (w + 7, b"AC")])] + F.EXTREMES
+    else:
+        seqs = [F.rand(1, w - 1, b"AC"), F.rand(2, w - 1), F.rand(3, w - 97, b"ACGTacgtN"),
+                (b"TTG" * 1400)[:w - 2] + b"Z", (b"CAACACC" * 600)[:w - 1]]
+    ids = F.default_ids(len(seqs))
+    for fact in F.FACTS:
+        fast = F.Model(seqs, ids, w, fact, fast=True)
+        slow = F.Model(seqs, ids, w, fact, fast=False)
+        assert fast.text == slow.text, fact
+
+
+def test_constructed_inputs_sit_on_their_edges():
+    W = F.W
+    c = F.counters([F.ASCENDING], W)
+    assert len(set(F.ASCENDING.upper())) == W and c["steps"] == W - 1
+    assert datagen.icfl_lengths(F.ASCENDING) == [1] * W
+    assert datagen.icfl_lengths(F.DESCENDING) == [W]
+    assert datagen.icfl_lengths(b"A" * W) == [W]
+    for s in F.MERGING:
+        assert F.counters([s], W)["lines_merging"] >= 1, s
+    assert datagen.icfl_lengths(b"CAACACC") == [5, 2]
+    for s in (F.PERIODIC, F.PERIODIC4):
+        c = F.counters([s], W)
+        assert c["last"] > 0 and c["chain"] >= 10, (s, c)
+    for T in (1, 10, 20, 30):
+        s = F.threshold_seq(T)
+        assert len(s) < W
+        assert datagen.duval_cfl_lengths(s) == [T + 1, T]
+        assert datagen.cfl_icfl_lengths(s, T) == [1, T, T]          # T + 1 split, T kept
+        assert datagen.cfl_icfl_lengths(s, T + 1) == [T + 1, T]
+    # a whole window that is one Lyndon word, one byte over the largest threshold below it
+    assert datagen.cfl_icfl_lengths(b"A" + b"T" * (W - 1), W - 1) == [1, W - 1]
+    assert datagen.cfl_icfl_lengths(b"A" + b"T" * (W - 1), W) == [W]
+    # both factor-count parities, and lines of 1, 2 and 3 values
+    counts = {len(datagen.icfl_lengths(w)) for s in F.EXTREMES for w in F.windows(s, W)}
+    assert {1, 2, 3} <= counts and {c & 1 for c in counts} == {0, 1}
+    # 0x24 is a byte like any other: out of band, the word keeps its four bytes
+    assert datagen.icfl_lengths(b"GA$T") == [3, 1]
+    assert sum(datagen.icfl_lengths(b"$" * 5 + b"A$%$")) == 9
+
+
+@pytest.mark.parametrize("w", [17, 100, 192, 193, 255, 256])
+def test_random_parity_inputs_merge(w):
+    """A window of fewer than 4 bytes has no step with last > 0 (the shortest is BABB) and one
+    of fewer than 7 no merge, so w = 1, 2, 3 are left out; from 17 on every parity set has
+    both, by the model's own count."""
+    import fpmash
+    _, R = fpmash.kfinger_limits()
+    c = F.counters(F.window_seqs(w, R), w)
+    assert c["lines_merging"] >= 1 and c["lines_last"] >= 1, c
+
+
+def test_other_parity_inputs_merge():
+    """the same condition for every other set the GPU parity tests run: the byte-rule set, the
+    max_lines set, the short-record sets, the records of the device-parsed image, and the
+    widest window, there over every 25th line (some 500 windows of 4,096 bytes; about one in 50 merges)"""
+    KMAX, R = fpmash.kfinger_limits()
+    many, mixed = F.short_record_sets()
+    recs, take = F.stage_seq_records(R)
+    sets = {"byte rules": (F.byte_rule_seqs(), 100, 1), "max_lines": (F.max_lines_seqs(R), 100, 1),
+            "many short": (many, 100, 1), "mixed short": (mixed, 100, 1),
+            "stage_seq": ([s for (_, s), t in zip(recs, take) if t], 100, 1),
+            "widest": (F.wide_seqs(KMAX, R), KMAX, 25)}
+    for name, (seqs, w, every) in sets.items():
+        c = F.counters(seqs, w, every=every)
+        assert c["lines_merging"] >= 1 and c["lines_last"] >= 1, (name, c)
+
+
+def one_error(p):
+    assert p.returncode == 1 and p.stdout == b""
+    err = p.stderr.decode().strip().split("\n")
+    assert len(err) == 1 and err[0].startswith("ERROR:"), p.stderr
+
+
+@pytest.mark.parametrize("sketch", [False, True])
+def test_cli_refuses_unknown_factorizations_before_device_work(tmp_path, sketch):
+    import fpmash
+    max_window, _ = fpmash.kfinger_limits()
+    (tmp_path / "in.fa").write_bytes(b">a b\nACGT\n")
+    extra = ["-S"] if sketch else []
+    for f in ("FOO", "CFL_ICFL-0", "CFL_ICFL-", "cfl", "ICFL-3", "CFL_ICFL-x", "CFL_ICFL--2",
+              "CFL_ICFL-%d" % (max_window + 1)):
+        one_error(subprocess.run([FPMASH, "kfinger"] + extra + ["-F", f, "-o", "out", "in.fa"],
+                                 cwd=tmp_path, capture_output=True))
+    assert sorted(os.listdir(tmp_path)) == ["in.fa"]
+
+
+def test_binding_names():
+    import fpmash
+    max_window, _ = fpmash.kfinger_limits()
+    assert fpmash.kfinger_factorization("CFL") == (fpmash.KF_CFL, 0)
+    assert fpmash.kfinger_factorization("ICFL") == (fpmash.KF_ICFL, 0)
+    assert fpmash.kfinger_factorization("CFL_ICFL-10") == (fpmash.KF_CFL_ICFL, 10)
+    assert fpmash.kfinger_factorization("CFL_ICFL-%d" % max_window) == (fpmash.KF_CFL_ICFL, max_window)
+    for bad in ("CFL_ICFL-%d" % (max_window + 1), "CFL_ICFL-0", "icfl"):
+        with pytest.raises(ValueError):
+            fpmash.kfinger_factorization(bad)
