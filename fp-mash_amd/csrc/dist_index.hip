@@ -614,7 +614,7 @@ __global__ __launch_bounds__(kBucketThreads) void idx_bucket_kernel(
 }
 
 // ---- exclusive scan of u32 counts (n <= 2^31), three launches ----
-constexpr int kScanBlock = 1024;   // elements per block (256 threads x 4)
+// (kScanBlock elements per block: 256 threads x 4; fpm_kernels.hpp)
 
 __global__ __launch_bounds__(256) void scan_local_kernel(const uint32_t *__restrict__ in,
                                                         uint32_t *__restrict__ out, uint64_t n,
@@ -1252,7 +1252,6 @@ hipError_t launch_publish(const unsigned long long *d_src, uint32_t n, unsigned 
 
 // scan_sums + scan_add in one launch for up to kScanFoldBlocks blocks: each block sums the
 // block totals before it itself (<= 4096 reads spread over its 256 threads)
-constexpr uint32_t kScanFoldBlocks = 4096;
 __global__ __launch_bounds__(256) void scan_add_fold_kernel(uint32_t *__restrict__ out, uint64_t n,
                                                            const uint32_t *__restrict__ sums,
                                                            uint32_t nb, uint32_t *__restrict__ out2,
@@ -1283,7 +1282,7 @@ uint64_t scan_scratch_words(uint64_t n) { return (n + kScanBlock - 1) / kScanBlo
 hipError_t launch_exscan(const uint32_t *in, uint32_t *out, uint32_t *out2, uint64_t n,
                          uint32_t *scratch, uint32_t *total, hipStream_t st)
 {
-    if (!n) return hipSuccess;
+    if (!n) return total ? hipMemsetAsync(total, 0, 4, st) : hipSuccess;   // the empty sum
     uint32_t nb = (uint32_t)((n + kScanBlock - 1) / kScanBlock);
     hipLaunchKernelGGL(scan_local_kernel, dim3(nb), dim3(256), 0, st, in, out, n, scratch);
     if (nb <= kScanFoldBlocks) {

@@ -568,4 +568,26 @@ int fpm_ctx_kernel_time(fpm_ctx *ctx, int kernel, double *total_ms, uint64_t *la
     return FPM_OK;
 }
 
+void fpm_scan_limits(uint32_t *block, uint32_t *fold_blocks)
+{
+    if (block) *block = kScanBlock;
+    if (fold_blocks) *fold_blocks = kScanFoldBlocks;
+}
+
+int fpm_exscan_dev(fpm_ctx *ctx, const uint32_t *d_in, uint64_t n, uint32_t *d_out,
+                   uint32_t *d_out2, uint32_t *d_total)
+{
+    if (!ctx || (n && (!d_in || !d_out))) return fail(FPM_EINVAL, "fpm_exscan_dev: null argument");
+    if (n > (1ull << 31)) return fail(FPM_EINVAL, "fpm_exscan_dev: more than 2^31 elements");
+    if (int rc = set_device(ctx)) return rc;
+    DevBufs mem(ctx);
+    uint32_t *scan_s = nullptr;
+    HIP_TRY(mem.get_pooled(&scan_s, scan_scratch_words(n ? n : 1) * 4));
+    const hipError_t launched = launch_exscan(d_in, d_out, d_out2, n, scan_s, d_total, ctx->stream);
+    const hipError_t synced = hipStreamSynchronize(ctx->stream);   // the scratch goes back to the
+    HIP_TRY(launched);                                             // pool on return
+    HIP_TRY(synced);
+    return FPM_OK;
+}
+
 }  // extern "C"

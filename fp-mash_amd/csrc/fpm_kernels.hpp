@@ -216,6 +216,12 @@ hipError_t launch_idx_build(const void *d_ref, const uint32_t *d_ref_len, uint64
 // One-pass build (g.cap != 0): part_fill holds 2^kIdxL1 u32 (cleared by the build), *overflow
 // (inside zero[]) is set when a partition exceeded cap: the index is then unusable and the
 // caller rebuilds with g.cap = 0
+
+// launch_exscan's shapes: blocks of kScanBlock elements; up to kScanFoldBlocks of them the block
+// totals are folded inside the add kernel (two launches), past that a single workgroup scans
+// them between the two (three launches)
+constexpr int kScanBlock = 1024;            // elements per block (256 threads x 4)
+constexpr uint32_t kScanFoldBlocks = 4096;
 uint64_t scan_scratch_words(uint64_t n);
 // copy n (<= kPubWords - 1) u64 counters into host-mapped memory, then write `seq` into its
 // last word (system-scope fence between): the host spins on that word

@@ -381,6 +381,13 @@ void fpm_kfinger_free(fpm_kfinger *j)
     delete j;
 }
 
+int fpm_kfinger_wide_groups(fpm_kfinger *j, uint32_t *groups)
+{
+    if (!j || !groups) return fail(FPM_EINVAL, "kfinger_wide_groups: null argument");
+    *groups = j->ran ? j->fact.work_groups : 0;
+    return FPM_OK;
+}
+
 void fpm_kfinger_limits(uint32_t *max_window, uint32_t *run_length)
 {
     if (max_window) *max_window = kKfMaxWindow;

@@ -11,6 +11,7 @@ struct fpm_screen {
     uint32_t n_db = 0, s = 0, hash_bytes = 8;
     uint64_t stride = 0;
     uint32_t E = 0, max_len = 0;          // cells of the database, its longest row
+    uint32_t sbits = 0;                   // the build's sort bucket bits (0: no cell)
     std::vector<uint32_t> h_len;
     ScreenTable tab;                      // U, dir, count (owned)
     uint32_t *d_len = nullptr, *d_slot = nullptr, *d_ustart = nullptr, *d_post = nullptr;
@@ -92,6 +93,7 @@ int screen_build(fpm_ctx *ctx, const void *d_db, const uint32_t *d_db_len, uint6
             // ~2 cells per sort bucket
             uint32_t sbits = 1;
             while (sbits < 22 && (2ull << sbits) < E) sbits++;
+            sc->sbits = sbits;
             const uint64_t nb = 1ull << sbits;
             DevBufs sort_tmp;   // the sort's own scratch: freed at the end of this block
             unsigned long long *km;
@@ -431,6 +433,17 @@ int fpm_ctx_last_screen_kernel(fpm_ctx *ctx, int *kernel)
 {
     if (!ctx || !kernel) return fail(FPM_EINVAL, "null argument");
     *kernel = ctx->last_screen_kernel;
+    return FPM_OK;
+}
+
+int fpm_screen_table_info(fpm_screen *sc, uint64_t *cells, uint64_t *n_distinct, uint32_t *sbits,
+                          uint32_t *dbits)
+{
+    if (!sc) return fail(FPM_EINVAL, "fpm_screen_table_info: null argument");
+    if (cells) *cells = sc->E;
+    if (n_distinct) *n_distinct = sc->tab.n;
+    if (sbits) *sbits = sc->sbits;
+    if (dbits) *dbits = sc->tab.dbits;
     return FPM_OK;
 }
 

@@ -99,6 +99,8 @@ SYMBOLS = [
     ("fpm_ctx_set_timing", C.c_int, [vp, C.c_int]),
     ("fpm_ctx_reset_timing", C.c_int, [vp]),
     ("fpm_ctx_kernel_time", C.c_int, [vp, C.c_int, f64p, u64p]),
+    ("fpm_scan_limits", None, [u32p, u32p]),
+    ("fpm_exscan_dev", C.c_int, [vp, vp, C.c_uint64, vp, vp, vp]),
     ("fpm_ctx_set_dist_mode", C.c_int, [vp, C.c_int]),
     ("fpm_ctx_last_dist_stats", C.c_int, [vp, C.POINTER(C.c_int), u64p, u64p]),
     ("fpm_ctx_last_dist_kernel", C.c_int, [vp, C.POINTER(C.c_int)]),
@@ -149,6 +151,7 @@ SYMBOLS = [
     ("fpm_kfinger_text", C.c_int, [vp, C.c_char_p, u64p, vp, C.c_uint64, u64p]),
     ("fpm_kfinger_free", None, [vp]),
     ("fpm_kfinger_limits", None, [u32p, u32p]),
+    ("fpm_kfinger_wide_groups", C.c_int, [vp, u32p]),
     ("fpm_compare_grid", C.c_int, [vp, vp, u32p, C.c_uint64, C.c_uint32, vp, u32p, C.c_uint64,
                                    C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p]),
     ("fpm_compare_grid_dev", C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64,
@@ -194,6 +197,7 @@ SYMBOLS = [
     ("fpm_screen_pvalues", C.c_int, [vp, u32p, C.c_double, f64p]),
     ("fpm_ctx_last_screen_kernel", C.c_int, [vp, C.POINTER(C.c_int)]),
     ("fpm_screen_lds_cap", C.c_int, [vp, u32p]),
+    ("fpm_screen_table_info", C.c_int, [vp, u64p, u64p, u32p, u32p]),
     ("fpm_screen_tax", C.c_int, [vp, u32p, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p, u32p,
                                  u32p, u64p]),
     ("fpm_ctx_last_tax_kernel", C.c_int, [vp, C.POINTER(C.c_int)]),
@@ -369,6 +373,14 @@ def kfinger_limits():
     w, r = C.c_uint32(), C.c_uint32()
     lib().fpm_kfinger_limits(C.byref(w), C.byref(r))
     return w.value, r.value
+
+
+def scan_limits():
+    """(elements per scan block, the most blocks the two-launch form of the u32 exclusive scan
+    takes: past their product it runs three launches) (fpm_scan_limits; a test hook)."""
+    b, f = C.c_uint32(), C.c_uint32()
+    lib().fpm_scan_limits(C.byref(b), C.byref(f))
+    return b.value, f.value
 
 
 KF_CFL, KF_ICFL, KF_CFL_ICFL = 0, 1, 2   # FPM_KF_*
@@ -795,6 +807,15 @@ class Screen:
                 "tax_count": arr[1][:n], "clade_hashes": arr[2][:n], "clade_count": arr[3][:n],
                 "total_count": int(tot[0]), "total_hashes": int(tot[1])}
 
+    def table_info(self):
+        """fpm_screen_table_info: what the build chose (a test hook) -> dict: cells, n_distinct,
+        sbits (sort bucket bits), dbits (directory bits)"""
+        e, n = C.c_uint64(), C.c_uint64()
+        sb, db = C.c_uint32(), C.c_uint32()
+        _check(lib().fpm_screen_table_info(self.h, C.byref(e), C.byref(n), C.byref(sb),
+                                           C.byref(db)))
+        return {"cells": e.value, "n_distinct": n.value, "sbits": sb.value, "dbits": db.value}
+
     def free(self):
         if self.h:
             lib().fpm_screen_free(self.h)
@@ -868,6 +889,11 @@ class Context:
         t, n = C.c_double(), C.c_uint64()
         _check(lib().fpm_ctx_kernel_time(self.h, kernel, C.byref(t), C.byref(n)))
         return t.value, n.value
+
+    def exscan_dev(self, d_in, n, d_out, d_out2=None, d_total=None):
+        """fpm_exscan_dev: the library's u32 exclusive scan over device pointers (d_out2 and
+        d_total may be None; a test hook; synchronises)"""
+        _check(lib().fpm_exscan_dev(self.h, d_in, int(n), d_out, d_out2, d_total))
 
     def merge_small_spills(self):
         """fpm_merge_small_spills: small-list merges that overflowed the LDS cap (resets)."""
@@ -1410,7 +1436,10 @@ class Context:
             h = np.zeros(max(n, 1), np.uint64 if use64 else np.uint32)
             nv = np.zeros(max(n, 1), np.uint32)
             _check(L.fpm_kfinger_fetch(job, _p(first, u64p), h.ctypes.data, _p(nv, u32p)))
-            res = {"n_lines": n, "rec_first_line": first, "hash": h[:n], "n_vals": nv[:n]}
+            groups = C.c_uint32()
+            _check(L.fpm_kfinger_wide_groups(job, C.byref(groups)))
+            res = {"n_lines": n, "rec_first_line": first, "hash": h[:n], "n_vals": nv[:n],
+                   "wide_groups": groups.value}
             if values:
                 tot = C.c_uint64()
                 _check(L.fpm_kfinger_values(job, None, None, 0, C.byref(tot)))
@@ -1441,6 +1470,7 @@ class Context:
         (hash.cpp:45-73), on the device.  -> n_lines, rec_first_line (len(seqs) + 1), hash and n_vals per line; with
         values the factor lengths (vals u16, line l's at val_off[l] .. val_off[l + 1]); with
         text the lines' text, ids[r] being record r's full ID bytes (lyn2vec's "<id>_0").
+        wide_groups: fpm_kfinger_wide_groups of the run (a test hook).
         max_lines: only the first so many lines exist (None: all)."""
         fact = kfinger_factorization(factorization)      # (refused before anything is staged)
         data, off = pack_records([bytes(s) for s in seqs])

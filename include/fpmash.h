@@ -126,6 +126,20 @@ int fpm_ctx_kernel_time(fpm_ctx *ctx, int kernel, double *total_ms, uint64_t *la
 /* merges routed to the small-list kernel whose lists overflowed its LDS cap (searched in global
  * memory instead: same results, slower) since the last call on this device; resets it */
 int fpm_merge_small_spills(fpm_ctx *ctx, uint64_t *count);
+/* The exclusive scan of u32 counts every table build, index build and text pass of the library
+ * goes through (dist_index.hip: launch_exscan), by itself, as test hooks.
+ * fpm_scan_limits (no device needed; any output may be NULL): *block the elements one workgroup
+ * scans, *fold_blocks the most blocks whose totals the add kernel folds itself (two launches);
+ * past block x fold_blocks elements one workgroup scans the block totals between the two (three
+ * launches).
+ * fpm_exscan_dev: d_out[i] = d_in[0] + ... + d_in[i - 1] (mod 2^32) for i < n, the same into
+ * d_out2 and the sum of all n into *d_total where those are not NULL; device pointers, n at most
+ * 2^31.  It takes the scan's scratch from the context's pool, launches the scan on the context's
+ * stream as the callers inside the library do, and synchronises.  Nothing past element n - 1 is
+ * written; n = 0 writes only *d_total = 0. */
+void fpm_scan_limits(uint32_t *block, uint32_t *fold_blocks);
+int fpm_exscan_dev(fpm_ctx *ctx, const uint32_t *d_in, uint64_t n, uint32_t *d_out,
+                   uint32_t *d_out2, uint32_t *d_total);
 
 /* dist strategy: FPM_DIST_AUTO picks the inverted-index path unless the shared-hash
  * events exceed pairs*S/4; DENSE walks every pair; SPARSE always uses the index.
@@ -447,6 +461,12 @@ int fpm_kfinger_text(fpm_kfinger *job, const char *ids, const uint64_t *id_off, 
                      uint64_t cap, uint64_t *n_bytes);
 void fpm_kfinger_free(fpm_kfinger *job);
 void fpm_kfinger_limits(uint32_t *max_window, uint32_t *run_length);
+/* The workgroups of the grid the job's run used for a window whose ICFL working memory lies in
+ * device memory (a test hook like fpm_sketch_job_plan, the result does not depend on it): at
+ * most two per compute unit and no more than the job has descriptors, each taking every
+ * *groups-th descriptor.  0 for CFL, for a window that keeps that memory in LDS, for a job
+ * without lines, and before fpm_kfinger_run. */
+int fpm_kfinger_wide_groups(fpm_kfinger *job, uint32_t *groups);
 
 /* ---- dist ---------------------------------------------------------------------
  * Replaces compare()/compareSketches()/pValue() (CommandDistance.cpp:335-450) over
@@ -750,6 +770,12 @@ int fpm_screen_pvalues(fpm_screen *sc, const uint32_t *shared, double kmer_space
 #define FPM_SK_ROWS_GLOBAL 2
 int fpm_ctx_last_screen_kernel(fpm_ctx *ctx, int *kernel);
 int fpm_screen_lds_cap(fpm_ctx *ctx, uint32_t *cap);
+/* What the table build chose (a test hook like fpm_ctx_last_screen_kernel; any output may be
+ * NULL): *cells the database's cells within the row lengths, *n_distinct = |U|, *sbits the bits
+ * of the counting sort's bucket index (about two cells per bucket, at most 22; 0 for a database
+ * without cells) and *dbits those of the lookup directory (2^dbits >= 2 |U|, at most 24). */
+int fpm_screen_table_info(fpm_screen *sc, uint64_t *cells, uint64_t *n_distinct, uint32_t *sbits,
+                          uint32_t *dbits);
 
 /* ---- taxscreen ----------------------------------------------------------------------
  * `mash taxscreen` after its pool pass (the same as screen's): one lowest-common-ancestor fold

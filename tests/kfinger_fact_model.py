@@ -61,14 +61,33 @@ def record_lines(seq: bytes, full_id: bytes, w: int, fact: str, fast=None):
     return [l.encode("latin-1") for l in datagen.cfl_lines(seq, gid, w, factorization=fact)]
 
 
+def batch_lines(seqs, ids, w: int, fact: str):
+    """record_lines(..., fast=True) of every record, from one run of cflgen over all of them
+    (a process per record costs more than its lines once there are a thousand records)"""
+    assert all(i.endswith(b"_0") for i in ids)
+    assert not any(b"\n" in s or b"\t" in s for s in seqs)
+    out = subprocess.run([M.CFLGEN, str(w), "4", fact], stdout=subprocess.PIPE, check=True,
+                         input=b"".join(b"\t" + bytes(s) + b"\n" for s in seqs if len(s))).stdout
+    bodies = out.split(b"\n")[:-1]
+    assert all(l.startswith(b"G00000_0") for l in bodies)
+    res, at = [], 0
+    for s, i in zip(seqs, ids):
+        n = M.n_lines(len(s), w)
+        res.append([i + l[len(b"G00000_0"):] + b"\n" for l in bodies[at:at + n]])
+        at += n
+    assert at == len(bodies)
+    return res
+
+
 class Model(M.Model):
     """kfinger_model.Model under factorization `fact`"""
 
     def __init__(self, seqs, ids, w, fact, max_lines=None, fast=None):
         self.lines = []
         self.rec_first_line = [0]
-        for s, i in zip(seqs, ids):
-            got = record_lines(bytes(s), i, w, fact, fast)
+        batch = batch_lines(seqs, ids, w, fact) if fast else None
+        for r, (s, i) in enumerate(zip(seqs, ids)):
+            got = batch[r] if batch else record_lines(bytes(s), i, w, fact, fast)
             assert len(got) == M.n_lines(len(s), w)
             self.lines += got
             if max_lines is not None:
@@ -83,6 +102,22 @@ class Model(M.Model):
         self.flat = (np.concatenate(self.vals) if self.vals
                      else np.zeros(0, np.uint64)).astype(np.uint16)
         self._hash = {}
+
+
+def cut(m, max_lines):
+    """Model(..., max_lines=max_lines) from the uncut model m of the same records: its first
+    max_lines lines"""
+    c = object.__new__(Model)
+    c.lines = m.lines[:max_lines]
+    c.rec_first_line = np.minimum(m.rec_first_line, np.uint64(max_lines))
+    c.text = b"".join(c.lines)
+    c.vals = m.vals[:max_lines]
+    c.n_vals = m.n_vals[:max_lines]
+    c.val_off = m.val_off[:len(c.lines) + 1]
+    c.flat = m.flat[:int(c.val_off[-1])]
+    c._hash = {}
+    c.hashes = lambda oracle, seed, use64: m.hashes(oracle, seed, use64)[:max_lines]
+    return c
 
 
 def windows(seq: bytes, w: int):
@@ -148,6 +183,56 @@ def stage_seq_records(R):
     """(header, sequence) records of a FASTA image and the take mask over them"""
     recs = [(b"T%d G%d rest" % (i, i), rand(30 + i, n)) for i, n in enumerate([120, 7, R + 130, 99])]
     return recs, [1, 0, 1, 1]
+
+
+def plan_descs(lens, w, R, stage, max_lines=None):
+    """the descriptors fpm_kfinger_stage makes of records of these lengths (one per workgroup
+    of a narrow window; a wide window's workgroups share them out): a record of w bytes or more
+    gives one per R window starts; records shorter than w, one line each, share one while they
+    follow each other, number at most R and fill at most `stage` bytes.  max_lines ends the job
+    inside a record or before one.  fpm_kfinger_wide_groups of a job with fewer descriptors
+    than the device takes workgroups is this number (tests/test_gpu_kfinger_scale.py)."""
+    descs = line = pack_n = pack_bytes = 0
+    cap = float("inf") if max_lines is None else max_lines
+    for n in lens:
+        if n == 0 or line >= cap:
+            continue
+        if n < w:
+            if pack_n == R or pack_bytes + n > stage:
+                pack_n = pack_bytes = 0
+            descs += pack_n == 0
+            pack_n += 1
+            pack_bytes += n
+            line += 1
+            continue
+        pack_n = pack_bytes = 0
+        lines = min(n, cap - line)
+        descs += -(-lines // R)
+        line += lines
+    return descs
+
+
+def stride_lens(n_desc, w, R):
+    """record lengths that make exactly n_desc cheap descriptors of both kinds: a record
+    shorter than the window (one line, a pack of its own between two long records) alternates
+    with one of w .. w + 7 bytes (one descriptor of that many lines), and every 50th record has
+    2 R + 5 bytes: three descriptors, the last one of five lines"""
+    assert w + 7 <= R
+    lens, descs = [], 0
+    while descs < n_desc:
+        i = len(lens)
+        if i % 2 == 0:
+            lens.append(1 + (i // 2 * 37) % (w - 1))
+        elif i % 50 == 49 and descs + 3 <= n_desc:
+            lens.append(2 * R + 5)
+        else:
+            lens.append(w + i // 2 % 8)
+        descs += -(-lens[-1] // R) if lens[-1] >= w else 1
+    return lens
+
+
+def stride_seqs(n_desc, w, R):
+    return [rand(31000 + i, n) for i, n in enumerate(stride_lens(n_desc, w, R))]
 
 
 W = 100

@@ -97,6 +97,36 @@ class Model:
         return self._hash[key]
 
 
+def window2(seq: bytes, full_id: bytes):
+    """Model([seq], [full_id], 2) of one record of two bytes or more, in closed form, for records
+    of millions of bytes: line i is the window (s[i], s[(i + 1) mod n]) upper-cased, one Lyndon
+    factor of 2 when its first byte is below its second, else two of 1.  -> dict: rising (bool
+    per line), n_vals, val_off, vals (u16) and text."""
+    s = np.frombuffer(seq, np.uint8)
+    assert len(s) >= 2
+    s = np.where((s >= 0x61) & (s <= 0x7A), s - 0x20, s).astype(np.uint8)
+    rising = s < np.roll(s, -1)
+    n_vals = np.where(rising, 1, 2).astype(np.uint32)
+    val_off = np.zeros(len(s) + 1, np.uint64)
+    val_off[1:] = np.cumsum(n_vals, dtype=np.uint64)
+    vals = np.ones(int(val_off[-1]), np.uint16)
+    vals[val_off[:-1][rising].astype(np.int64)] = 2
+    # "<id> 2\n" or "<id> 1 1\n"
+    idb = np.frombuffer(full_id, np.uint8)
+    size = len(idb) + np.where(rising, 3, 5)
+    at = np.zeros(len(s) + 1, np.int64)
+    at[1:] = np.cumsum(size)
+    text = np.full(int(at[-1]), ord(" "), np.uint8)
+    for j, c in enumerate(idb):
+        text[at[:-1] + j] = c
+    body = at[:-1] + len(idb)
+    text[body + 1] = np.where(rising, ord("2"), ord("1"))
+    text[body[~rising] + 3] = ord("1")
+    text[at[1:] - 1] = ord("\n")
+    return {"rising": rising, "n_vals": n_vals, "val_off": val_off, "vals": vals,
+            "text": text.tobytes()}
+
+
 def references(oracle, text: bytes, seed=42):
     """the References `sketch -fp` makes of the text: (name, length, u32 hashes in line order)"""
     refs, _used, _last = oracle.fp_references(text, seed=seed)

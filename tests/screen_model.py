@@ -167,6 +167,133 @@ def closed(rows, keys, k=21, winner=False, lengths=None, counts=None):
     return shared, median
 
 
+# ---- closed form over a whole matrix: no loop over cells or keys ------------------------------
+def _row_sums(C):
+    """(shared, median) per row of a matrix of gathered counters (0: not counted)"""
+    shared = (C > 0).sum(axis=1)
+    # ascending with the zeros pushed past every counter: position shared // 2 is the median
+    S = np.sort(np.where(C == 0, np.uint64(1) << np.uint64(32), C.astype(np.uint64)), axis=1)
+    S = np.concatenate([S, np.zeros((len(S), 1), np.uint64)], axis=1)      # (a row of no cell)
+    median = S[np.arange(len(S)), shared // 2]
+    return shared.astype(np.uint32), np.where(shared > 0, median, 0).astype(np.uint32)
+
+
+def closed_matrix(R, lens, keys, k=21, lengths=None):
+    """`closed` and `closed_counts` for databases of 10^7 cells: R a (rows x stride) matrix, row
+    i's hashes its first lens[i] cells.  -> dict: U, count, holders (the rows that hold each entry
+    of U), shared, median and, with lengths
+    (one per row), scores (estimate_identity of the plain shared counts), wshared and wmedian:
+    -w by screen_winner_kernel's rule, the greatest score, then the greatest length, then the
+    lowest index."""
+    R = np.asarray(R)
+    n = len(lens)
+    R = R.reshape(n, R.size // n if n else 0)
+    lens = np.asarray(lens, np.int64)
+    inside = np.arange(R.shape[1])[None, :] < lens[:, None]
+    U, inv = np.unique(R[inside].astype(np.uint64), return_inverse=True)
+    inv = inv.reshape(-1)
+    keys = np.asarray(keys, np.uint64)
+    cnt = np.zeros(len(U), np.uint32)
+    if len(U) and len(keys):
+        at = np.searchsorted(U, keys)
+        hit = at < len(U)
+        hit[hit] = U[at[hit]] == keys[hit]
+        cnt = (np.bincount(at[hit], minlength=len(U)) & 0xFFFFFFFF).astype(np.uint32)
+    C = np.zeros(R.shape, np.uint32)
+    C[inside] = cnt[inv]
+    out = {"U": U, "count": cnt, "holders": np.bincount(inv, minlength=len(U))}
+    out["shared"], out["median"] = _row_sums(C)
+    if lengths is None:
+        return out
+    score = np.array([estimate_identity(int(a), int(l), k) for a, l in zip(out["shared"], lens)])
+    length = np.asarray(lengths, np.uint64)
+    # rows in the order -w prefers them; an entry goes to the first of its holders in that order
+    by_rank = np.lexsort((np.arange(n), ~length, -score))
+    rank = np.empty(n, np.int64)
+    rank[by_rank] = np.arange(n)
+    row_of = np.broadcast_to(np.arange(n)[:, None], R.shape)[inside]
+    best = np.full(len(U), n, np.int64)
+    np.minimum.at(best, inv, rank[row_of])
+    owner = np.append(by_rank, -1)[best]                 # (every entry of U has a holder)
+    W = np.zeros(R.shape, np.uint32)
+    W[inside] = np.where(owner[inv] == row_of, cnt[inv], 0)
+    out["scores"] = score
+    out["wshared"], out["wmedian"] = _row_sums(W)
+    return out
+
+
+# ---- the inputs of tests/test_gpu_screen_scale.py ---------------------------------------------
+SCALE_SHARED = 3000          # keys a few rows share
+SCALE_SHARED_ROWS = 5        # ... at most so many rows each
+
+
+def scale_holders():
+    """an upper bound of the cells scale_db gives to shared keys: the database has at least
+    rows * width - scale_holders() distinct values"""
+    return SCALE_SHARED * SCALE_SHARED_ROWS
+
+
+def _distinct(rng, n, dtype):
+    """n distinct values in random order, away from both ends of the type's range"""
+    top = min(int(np.iinfo(dtype).max), 2 ** 63) - 256
+    v = np.zeros(0, np.uint64)
+    while len(v) < n:
+        v = np.unique(np.concatenate([v, rng.integers(256, top, size=n - len(v) + n // 64 + 64,
+                                                      dtype=np.uint64)]))
+    return rng.permutation(v)[:n].astype(dtype)
+
+
+def scale_db(seed, n, width, dtype=np.uint64, heavy=0, heavy_rows=0):
+    """n strictly ascending rows of `width` cells: values drawn without replacement over the
+    whole matrix, so distinct within every row, then SCALE_SHARED keys each put into 2 ..
+    SCALE_SHARED_ROWS rows; with heavy > 0, `heavy` further keys held by heavy_rows rows each
+    (random values like all others, not clustered).  -> (matrix, the heavy keys)"""
+    rng = np.random.default_rng(seed)
+    k_row = np.zeros(n, np.int64)
+    member = np.zeros((n, 0), bool)
+    if heavy:
+        # per heavy key the heavy_rows rows with the smallest of n random numbers
+        member = np.zeros((heavy, n), bool)
+        pick = np.argpartition(rng.random((heavy, n)), heavy_rows, axis=1)[:, :heavy_rows]
+        member[np.arange(heavy)[:, None], pick] = True
+        member = np.ascontiguousarray(member.T)
+        k_row = member.sum(axis=1)
+        assert k_row.max() < width - 8
+    n_light = int(n * width - k_row.sum())
+    vals = _distinct(rng, n_light + heavy + SCALE_SHARED, dtype)
+    light, hv, shared = np.split(vals, [n_light, n_light + heavy])
+    R = np.empty((n, width), dtype)
+    is_light = np.arange(width)[None, :] >= k_row[:, None]
+    R[is_light] = light
+    R[~is_light] = hv[np.nonzero(member)[1]]
+    for key in shared:
+        rows = rng.choice(n, size=int(rng.integers(2, SCALE_SHARED_ROWS + 1)), replace=False)
+        cols = k_row[rows] + (rng.random(len(rows)) * (width - k_row[rows])).astype(np.int64)
+        R[rows, cols] = key                      # (over a light cell, maybe an earlier shared key)
+    R.sort(axis=1)
+    assert (R[:, 1:] > R[:, :-1]).all()
+    return R, hv.astype(np.uint64)
+
+
+def scale_pool(seed, U, draws, hot=None):
+    """pool keys: `draws` draws with repeats from a tenth of U, skewed so counters run from 1 to
+    some tens, every key of `hot` a few times, and misses: below U[0], above U[-1], 0, the
+    largest u64, and neighbours of present keys"""
+    rng = np.random.default_rng(seed)
+    some = rng.choice(len(U), size=max(len(U) // 10, 1), replace=False)
+    keys = [U[some[(len(some) * rng.random(draws) ** 2).astype(np.int64)]]]
+    if hot is not None and len(hot):
+        keys.append(np.repeat(hot, rng.integers(1, 6, size=len(hot))))
+    at = rng.integers(0, len(U), size=2000)
+    miss = np.concatenate([U[at] + np.uint64(1), U[at] - np.uint64(1),
+                           np.array([0, U[0] - np.uint64(1), U[-1] + np.uint64(1), 2 ** 64 - 1],
+                                    np.uint64),
+                           rng.integers(0, 2 ** 64, size=1000, dtype=np.uint64)])
+    miss = miss[U[np.clip(np.searchsorted(U, miss), 0, len(U) - 1)] != miss]
+    keys.append(miss)
+    return rng.permutation(np.concatenate(keys).astype(np.uint64)), miss
+
+
 # ---- output (CommandScreen.cpp:215-253) -------------------------------------------------------
 def lines(oracle, rows, names, comments, shared, median, setsize, k, kmer_space,
           identity_min=0.0, pvalue_max=1.0):

@@ -40,6 +40,14 @@ def test_no_device_fails_loudly():
     assert fpmash.lib().fpm_abi_version() == 1
 
 
+def test_scan_limits_need_no_device():
+    import fpmash
+    block, fold_blocks = fpmash.scan_limits()
+    assert block >= 256 and block % 256 == 0       # whole elements per thread of a 256-lane group
+    assert fold_blocks >= 1 and block * fold_blocks < 2 ** 31
+    fpmash.lib().fpm_scan_limits(None, None)       # NULL outputs are allowed
+
+
 def test_library_is_gfx950_code_object():
     import subprocess
     import fpmash

@@ -188,3 +188,46 @@ def test_binding_names():
     for bad in ("CFL_ICFL-%d" % (max_window + 1), "CFL_ICFL-0", "icfl"):
         with pytest.raises(ValueError):
             fpmash.kfinger_factorization(bad)
+
+
+# ---- the helpers of tests/test_gpu_kfinger_scale.py ------------------------------------------
+
+@pytest.mark.parametrize("fact", ["ICFL", "CFL_ICFL-30"])
+def test_batch_and_cut_models(fact):
+    """one run of cflgen over all records gives the lines of a run per record, empty and short
+    records included, and cut() is the model with max_lines"""
+    seqs = [F.rand(1, 230), b"", F.rand(2, 7), F.rand(3, 100), b"ac", F.rand(4, 150)]
+    ids = F.default_ids(len(seqs))
+    whole = F.Model(seqs, ids, 100, fact, fast=True)
+    assert whole.lines == F.Model(seqs, ids, 100, fact, fast=False).lines
+    total = len(whole.lines)
+    assert total == 230 + 1 + 100 + 1 + 150
+    for cap in (0, 1, 229, 230, 231, 300, total - 1, total, total + 9):
+        a, b = F.cut(whole, cap), F.Model(seqs, ids, 100, fact, max_lines=cap)
+        assert a.lines == b.lines and a.text == b.text
+        assert np.array_equal(a.rec_first_line, b.rec_first_line)
+        assert np.array_equal(a.n_vals, b.n_vals) and np.array_equal(a.val_off, b.val_off)
+        assert np.array_equal(a.flat, b.flat) and a.flat.dtype == b.flat.dtype
+
+
+def test_plan_descs_and_the_grid_stride_lengths():
+    kmax, R = fpmash.kfinger_limits()
+    stage, w = R + kmax - 1, 193
+    # long records: one descriptor per R starts; short ones share one while they are neighbours
+    assert F.plan_descs([w, w + 7, R, R + 1, 2 * R + 5], w, R, stage) == 1 + 1 + 1 + 2 + 3
+    assert F.plan_descs([5, 0, 6, w, 7, 8], w, R, stage) == 3
+    assert F.plan_descs([1] * (R + 1), w, R, stage) == 2                # R records fill a pack
+    assert F.plan_descs([w - 1] * (stage // (w - 1) + 1), w, R, stage) == 2   # so do `stage` bytes
+    # max_lines: inside a record, at its end, before a short one
+    assert F.plan_descs([2 * R + 5, 3], w, R, stage, max_lines=R + 1) == 2
+    assert F.plan_descs([2 * R + 5, 3], w, R, stage, max_lines=2 * R + 5) == 3
+    assert F.plan_descs([2 * R + 5, 3], w, R, stage, max_lines=2 * R + 6) == 4
+    assert F.plan_descs([2 * R + 5, 3], w, R, stage, max_lines=0) == 0
+    for n_desc in (1, 2, 60, 1061, 1062, 1063):
+        lens = F.stride_lens(n_desc, w, R)
+        assert F.plan_descs(lens, w, R, stage) == n_desc
+        if n_desc >= 60:
+            assert lens.count(2 * R + 5) >= 1
+            assert all((n < w) == (i % 2 == 0) for i, n in enumerate(lens))
+            assert {n for n in lens if w <= n < 2 * R} == set(range(w, w + 8))
+            assert min(lens) == 1 and max(n for n in lens if n < w) > w - 40

@@ -104,3 +104,19 @@ def test_cli_refusals_before_device_work(tmp_path, sketch):
     one_error(run(extra + ["-o", "out", "in.fa", "missing.fa"], cwd=tmp_path))
     one_error(run(extra + ["-o", "out", "missing.fa"], cwd=tmp_path))
     assert sorted(os.listdir(tmp_path)) == ["in.fa"]
+
+
+def test_window2_closed_form():
+    """the closed form tests/test_gpu_kfinger_scale.py checks four million lines with, against
+    the model, on a record with lower case, equal neighbours and a wrap"""
+    rng = np.random.default_rng(12)
+    seq = bytes(rng.choice(list(b"ACGTacgt"), 300).astype(np.uint8))
+    for s in (seq, b"AC", b"CA", b"AA", b"aC" + seq + b"T"):
+        m = M.Model([s], [b"g_0"], 2)
+        c = M.window2(s, b"g_0")
+        assert len(m.lines) == len(s) == len(c["rising"])
+        assert c["text"] == m.text
+        assert np.array_equal(c["n_vals"], m.n_vals) and np.array_equal(c["val_off"], m.val_off)
+        assert np.array_equal(c["vals"], m.flat) and c["vals"].dtype == m.flat.dtype
+        assert [v.tolist() for v in m.vals] == [[2] if r else [1, 1] for r in c["rising"]]
+    assert M.window2(b"AC", b"x")["text"] == b"x 2\nx 1 1\n"

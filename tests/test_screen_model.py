@@ -16,11 +16,33 @@ def rand_db(rng, n, size, universe):
             for _ in range(n)]
 
 
+def as_matrix(rows, pad, dtype=np.uint64):
+    """the rows in a matrix `pad` cells wider than the longest, the cells past each length
+    holding the type's largest value (which a row may hold too)"""
+    R = np.full((len(rows), max([len(r) for r in rows] + [0]) + pad), np.iinfo(dtype).max, dtype)
+    for i, r in enumerate(rows):
+        R[i, :len(r)] = r
+    return R, np.array([len(r) for r in rows], np.uint32)
+
+
 def same(rows, keys, **kw):
     a = M.literal(rows, keys, **kw)
     b = M.closed(rows, keys, **{k: v for k, v in kw.items() if k != "visit"})
     assert list(a[0]) == list(b[0])
     assert list(a[1]) == list(b[1])
+    # the whole-matrix form (tests/test_gpu_screen_scale.py's reference) against the two
+    if "visit" not in kw:
+        U, cnt = M.closed_counts(rows, keys)
+        for pad in (0, 3):
+            R, lens = as_matrix(rows, pad)
+            m = M.closed_matrix(R, lens, keys, lengths=kw.get("lengths"))
+            assert np.array_equal(m["U"], U) and np.array_equal(m["count"], cnt)
+            assert m["count"].dtype == np.uint32
+            which = ("wshared", "wmedian") if kw.get("winner") else ("shared", "median")
+            assert m[which[0]].tolist() == list(a[0]) and m[which[1]].tolist() == list(a[1])
+            if kw.get("winner"):
+                plain = M.literal(rows, keys)
+                assert m["shared"].tolist() == plain[0] and m["median"].tolist() == plain[1]
     return a
 
 
@@ -97,6 +119,9 @@ def test_winner_rule_order_independent():
     assert M.closed(rows, keys, winner=True, lengths=[5, 9])[0] == [0, 3]
     assert M.literal(rows, keys, winner=True, lengths=[7, 7])[0] == [3, 0]
     assert M.closed(rows, keys, winner=True, lengths=[7, 7])[0] == [3, 0]
+    R, lens = as_matrix(rows, 1)
+    assert M.closed_matrix(R, lens, keys, lengths=[5, 9])["wshared"].tolist() == [0, 3]
+    assert M.closed_matrix(R, lens, keys, lengths=[7, 7])["wshared"].tolist() == [3, 0]
     # the full tie is the one case the visiting order decides in the reference
     assert M.literal(rows, keys, winner=True, lengths=[7, 7], visit=lambda ix: ix[::-1])[0] == [0, 3]
 
