@@ -412,7 +412,7 @@ __device__ __forceinline__ void sketch_tile(
     __shared__ uint32_t wcnt[ES * kWaves + 1];
     __shared__ uint32_t bins_own[THR ? 1 : kBins];
     uint32_t *const bins = THR ? reinterpret_cast<uint32_t *>(surv) : bins_own;
-    __shared__ uint32_t big_bucket, s_cut;
+    __shared__ uint32_t big_bucket, s_cut, s_nkept;
 
     FPM_PHASE_DECL;
     FPM_PHASE(0);
@@ -581,47 +581,46 @@ __device__ __forceinline__ void sketch_tile(
         if (b < NB) {
             const uint32_t c = bins[b];
             bins[b] = acc;
-            if (acc < p.s && acc + c >= p.s) s_cut = (uint32_t)b + 1;
+            if (acc < p.s && acc + c >= p.s) { s_cut = (uint32_t)b + 1; s_nkept = acc + c; }
             acc += c;
         }
     }
     if (bmax > kMaxBucket) big_bucket = 1;
     __syncthreads();
     const uint32_t cut = big_bucket ? (uint32_t)NB : s_cut;
-    const uint32_t nkept = cut < (uint32_t)NB ? bins[cut] : nvalid;   // before the scatter
+    // the keys below the cut (the start of bucket `cut`, from the thread that set the cut: the
+    // scatter below moves bins[] of every bucket with no barrier before it)
+    const uint32_t nkept = cut < (uint32_t)NB ? s_nkept : nvalid;
     FPM_PHASE(4);
-    uint32_t lo_b = 0, hi_b = cut, nv = nkept;
+    // scatter every key to its bucket: afterwards bins[b] = end of bucket b, start =
+    // bins[b - 1], the buckets below the cut fill keys[0, nkept) and the others
+    // keys[nkept, nvalid).  The keys live in LDS alone from here on (kr[] is dead: the rank
+    // below reads them back by position, so the registers go to its rounds instead).
+#pragma unroll
+    for (int e = 0; e < ES; e++)
+        if (vbits >> e & 1) keys[atomicAdd(&bins[(uint32_t)(kr[e] >> bshift)], 1u)] = kr[e];
+    __syncthreads();
+    uint32_t lo_p = 0, hi_p = nkept, hi_b = cut, nv = nkept;
     for (int pass = 0; pass < 2; pass++) {
-        // an opaque copy of the shift per pass: otherwise the compiler hoists every key's
-        // bucket addresses (2 x E VGPRs) out of this loop and spills (72-VGPR budget at P = 2048)
-        uint32_t bsh = bshift;
-        asm volatile("" : "+v"(bsh));
-        // scatter the keys of buckets [lo_b, hi_b): afterwards bins[b] = end of bucket b,
-        // start = bins[b - 1]; each key keeps its slot for the in-bucket rank below
-        uint32_t act = 0;
-#pragma unroll
-        for (int e = 0; e < ES; e++) {
-            const uint32_t bk = (uint32_t)(kr[e] >> bsh);
-            act |= ((vbits >> e & 1) && bk >= lo_b && bk < hi_b) ? (1u << e) : 0u;
-        }
-        uint32_t slot[ES];
-#pragma unroll
-        for (int e = 0; e < ES; e++)
-            if (act >> e & 1) {
-                slot[e] = atomicAdd(&bins[(uint32_t)(kr[e] >> bsh)], 1u);
-                keys[slot[e]] = kr[e];
-            }
-        __syncthreads();
         FPM_PHASE(5);
         if (!big_bucket) {
-            // in-bucket rank of every key (ties by slot): the bucket's ~2 keys are read with
-            // independent LDS loads, then every key is written to its sorted position (an
-            // insertion sort per bucket was a chain of dependent LDS round trips: 26 % of the
-            // tile's time, tools/micro/sketch_phases.hip)
+            // in-bucket rank of the keys at positions [lo_p, hi_p) (ties by position): only the
+            // keys below the cut in the first pass, so a tile that keeps s of its ~2 s keys
+            // runs half the rounds of one that ranks every register slot (a key's slot is
+            // random with respect to its bucket: masking slots saves nothing per wave).  The
+            // bucket's ~2 keys are read with independent LDS loads, then every key is written
+            // to its sorted position (an insertion sort per bucket was a chain of dependent
+            // LDS round trips: 26 % of the tile's time, tools/micro/sketch_phases.hip)
+            const uint32_t span = (uint32_t)__builtin_amdgcn_readfirstlane((int)(hi_p - lo_p));
+            uint64_t x[ES];
+            uint32_t dst[ES];
 #pragma unroll
-            for (int e = 0; e < ES; e++)
-                if (act >> e & 1) {
-                    const uint32_t b = (uint32_t)(kr[e] >> bsh);
+            for (int i = 0; i < ES; i++) {
+                if ((uint32_t)i * kBlock >= span) break;               // block-uniform
+                const uint32_t j = lo_p + (uint32_t)i * kBlock + (uint32_t)tid;
+                if (j < hi_p) {
+                    x[i] = keys[j];
+                    const uint32_t b = (uint32_t)(x[i] >> bshift);
                     const uint32_t s0 = b ? bins[b - 1] : 0u, s1 = bins[b];
                     const uint32_t mb = s1 - s0;
                     uint32_t r = 0;
@@ -631,18 +630,21 @@ __device__ __forceinline__ void sketch_tile(
                     for (uint32_t u = 0; u < 8; u++) {
                         const uint32_t t = s0 + u;
                         const uint64_t y = keys[t < (uint32_t)PS ? t : (uint32_t)PS - 1];
-                        r += (u < mb) & ((y < kr[e]) | ((y == kr[e]) & (t < slot[e])));
+                        r += (u < mb) & ((y < x[i]) | ((y == x[i]) & (t < j)));
                     }
                     for (uint32_t t = s0 + 8; t < s1; t++) {
                         const uint64_t y = keys[t];
-                        r += (y < kr[e]) | ((y == kr[e]) & (t < slot[e]));
+                        r += (y < x[i]) | ((y == x[i]) & (t < j));
                     }
-                    slot[e] = s0 + r;
+                    dst[i] = s0 + r;
                 }
+            }
             __syncthreads();
 #pragma unroll
-            for (int e = 0; e < ES; e++)
-                if (act >> e & 1) keys[slot[e]] = kr[e];
+            for (int i = 0; i < ES; i++) {
+                if ((uint32_t)i * kBlock >= span) break;
+                if (lo_p + (uint32_t)i * kBlock + (uint32_t)tid < hi_p) keys[dst[i]] = x[i];
+            }
             __syncthreads();
         } else {
             for (int i = tid; i < PS; i += kBlock)
@@ -663,7 +665,8 @@ __device__ __forceinline__ void sketch_tile(
             if (tid == 0) out_count[td.out_row] = total < p.s ? total : p.s;
             break;
         }
-        lo_b = hi_b;
+        lo_p = nkept;
+        hi_p = nvalid;
         hi_b = NB;
         nv = nvalid;
     }
