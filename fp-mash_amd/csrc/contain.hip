@@ -19,6 +19,7 @@
 // contain_rows_kernel computes that with one wave per ref row; contain_literal_kernel is the
 // walk as written, one lane per pair, for lists in any order (-fp sketches) and as the
 // cross-check of the fast kernel; rows_ascending_kernel tells the host which one applies.
+#include "fpm_device.hpp"
 #include "fpm_kernels.hpp"
 #include "../../include/fpmash.h"
 
@@ -306,94 +307,66 @@ uint32_t contain_lds_cap(uint32_t hash_bytes)
     return (lds_granted() - kLdsPad - dir_bytes(kDirBitsMax)) / hash_bytes;
 }
 
-hipError_t launch_rows_ascending(const void *d_ref, const uint32_t *d_ref_len, uint64_t ref_stride,
-                                 uint32_t n_ref, const void *d_qry, const uint32_t *d_qry_len,
-                                 uint64_t qry_stride, uint32_t n_qry, uint32_t hash_bytes,
+hipError_t launch_rows_ascending(const RowSet &R, const RowSet &Q, uint32_t hash_bytes,
                                  uint32_t *flag, hipStream_t st)
 {
-    const uint64_t rows = (uint64_t)n_ref + n_qry;
+    const uint64_t rows = (uint64_t)R.n + Q.n;
     if (!rows) return hipSuccess;
     if (rows > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    if (hash_bytes == 8)
-        hipLaunchKernelGGL(rows_ascending_kernel<uint64_t>, dim3((uint32_t)rows), dim3(kThreads), 0,
-                           st, (const uint64_t *)d_ref, d_ref_len, ref_stride, n_ref,
-                           (const uint64_t *)d_qry, d_qry_len, qry_stride, flag);
-    else if (hash_bytes == 4)
-        hipLaunchKernelGGL(rows_ascending_kernel<uint32_t>, dim3((uint32_t)rows), dim3(kThreads), 0,
-                           st, (const uint32_t *)d_ref, d_ref_len, ref_stride, n_ref,
-                           (const uint32_t *)d_qry, d_qry_len, qry_stride, flag);
-    else
-        return hipErrorInvalidValue;
-    return hipGetLastError();
+    return with_hash(hash_bytes, [&](auto h) {
+        using T = decltype(h);
+        hipLaunchKernelGGL(rows_ascending_kernel<T>, dim3((uint32_t)rows), dim3(kThreads), 0, st,
+                           (const T *)R.rows, R.len, R.stride, R.n, (const T *)Q.rows, Q.len,
+                           Q.stride, flag);
+        return hipGetLastError();
+    });
 }
 
-template <typename T>
-static hipError_t contain_rows_t(const T *d_ref, const uint32_t *d_ref_len, uint64_t ref_stride,
-                                 uint32_t n_ref, const T *d_qry, const uint32_t *d_qry_len,
-                                 uint64_t qry_stride, uint32_t n_qry, uint32_t max_qry_len,
-                                 uint32_t *d_common, uint32_t *d_steps, hipStream_t st, bool *lds)
-{
-    // the grid flattened into gridDim.x: n_qry may exceed the 65,535 of gridDim.y
-    const uint64_t blocks = (uint64_t)n_qry * ((n_ref + kBlockRefs - 1) / kBlockRefs);
-    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const bool in_lds = max_qry_len <= contain_lds_cap(sizeof(T));
-    if (lds) *lds = in_lds;
-    if (in_lds) {
-        uint32_t bbits = kDirBitsMin;
-        while (bbits < kDirBitsMax && (1u << bbits) < 2 * (uint64_t)max_qry_len) bbits++;
-        const size_t bytes = dir_bytes(bbits) +
-                             (((size_t)max_qry_len * sizeof(T) + kLdsPad + 15) & ~(size_t)15);
-        hipLaunchKernelGGL((contain_rows_kernel<T, true>), dim3((uint32_t)blocks), dim3(kThreads),
-                           bytes, st, d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len,
-                           qry_stride, n_qry, bbits, d_common, d_steps);
-    } else {
-        hipLaunchKernelGGL((contain_rows_kernel<T, false>), dim3((uint32_t)blocks), dim3(kThreads),
-                           0, st, d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len,
-                           qry_stride, n_qry, kDirBitsMin, d_common, d_steps);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_contain_rows(const void *d_ref, const uint32_t *d_ref_len, uint64_t ref_stride,
-                               uint32_t n_ref, const void *d_qry, const uint32_t *d_qry_len,
-                               uint64_t qry_stride, uint32_t n_qry, uint32_t hash_bytes,
+hipError_t launch_contain_rows(const RowSet &R, const RowSet &Q, uint32_t hash_bytes,
                                uint32_t max_qry_len, uint32_t *d_common, uint32_t *d_steps,
-                               hipStream_t st, bool *lds)
+                               bool *lds, hipStream_t st)
 {
     if (lds) *lds = false;
-    if (!n_ref || !n_qry) return hipSuccess;
-    if (hash_bytes == 8)
-        return contain_rows_t((const uint64_t *)d_ref, d_ref_len, ref_stride, n_ref,
-                              (const uint64_t *)d_qry, d_qry_len, qry_stride, n_qry, max_qry_len,
-                              d_common, d_steps, st, lds);
-    if (hash_bytes == 4)
-        return contain_rows_t((const uint32_t *)d_ref, d_ref_len, ref_stride, n_ref,
-                              (const uint32_t *)d_qry, d_qry_len, qry_stride, n_qry, max_qry_len,
-                              d_common, d_steps, st, lds);
-    return hipErrorInvalidValue;
+    if (!R.n || !Q.n) return hipSuccess;
+    // the grid flattened into gridDim.x: n_qry may exceed the 65,535 of gridDim.y
+    const uint64_t blocks = (uint64_t)Q.n * ((R.n + kBlockRefs - 1) / kBlockRefs);
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    return with_hash(hash_bytes, [&](auto h) {
+        using T = decltype(h);
+        const T *ref = (const T *)R.rows, *qry = (const T *)Q.rows;
+        const bool in_lds = max_qry_len <= contain_lds_cap(sizeof(T));
+        if (lds) *lds = in_lds;
+        if (in_lds) {
+            uint32_t bbits = kDirBitsMin;
+            while (bbits < kDirBitsMax && (1u << bbits) < 2 * (uint64_t)max_qry_len) bbits++;
+            const size_t bytes = dir_bytes(bbits) +
+                                 (((size_t)max_qry_len * sizeof(T) + kLdsPad + 15) & ~(size_t)15);
+            hipLaunchKernelGGL((contain_rows_kernel<T, true>), dim3((uint32_t)blocks),
+                               dim3(kThreads), bytes, st, ref, R.len, R.stride, R.n, qry, Q.len,
+                               Q.stride, Q.n, bbits, d_common, d_steps);
+        } else {
+            hipLaunchKernelGGL((contain_rows_kernel<T, false>), dim3((uint32_t)blocks),
+                               dim3(kThreads), 0, st, ref, R.len, R.stride, R.n, qry, Q.len,
+                               Q.stride, Q.n, kDirBitsMin, d_common, d_steps);
+        }
+        return hipGetLastError();
+    });
 }
 
-hipError_t launch_contain_literal(const void *d_ref, const uint32_t *d_ref_len,
-                                  uint64_t ref_stride, uint32_t n_ref, const void *d_qry,
-                                  const uint32_t *d_qry_len, uint64_t qry_stride, uint32_t n_qry,
-                                  uint32_t hash_bytes, uint32_t *d_common, uint32_t *d_steps,
-                                  hipStream_t st)
+hipError_t launch_contain_literal(const RowSet &R, const RowSet &Q, uint32_t hash_bytes,
+                                  uint32_t *d_common, uint32_t *d_steps, hipStream_t st)
 {
-    const uint64_t n = (uint64_t)n_ref * n_qry;
+    const uint64_t n = (uint64_t)R.n * Q.n;
     if (!n) return hipSuccess;
     const uint64_t blocks = (n + kThreads - 1) / kThreads;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    if (hash_bytes == 8)
-        hipLaunchKernelGGL(contain_literal_kernel<uint64_t>, dim3((uint32_t)blocks), dim3(kThreads),
-                           0, st, (const uint64_t *)d_ref, d_ref_len, ref_stride, n_ref,
-                           (const uint64_t *)d_qry, d_qry_len, qry_stride, n, d_common, d_steps);
-    else if (hash_bytes == 4)
-        hipLaunchKernelGGL(contain_literal_kernel<uint32_t>, dim3((uint32_t)blocks), dim3(kThreads),
-                           0, st, (const uint32_t *)d_ref, d_ref_len, ref_stride, n_ref,
-                           (const uint32_t *)d_qry, d_qry_len, qry_stride, n, d_common, d_steps);
-    else
-        return hipErrorInvalidValue;
-    return hipGetLastError();
+    return with_hash(hash_bytes, [&](auto h) {
+        using T = decltype(h);
+        hipLaunchKernelGGL(contain_literal_kernel<T>, dim3((uint32_t)blocks), dim3(kThreads), 0, st,
+                           (const T *)R.rows, R.len, R.stride, R.n, (const T *)Q.rows, Q.len,
+                           Q.stride, n, d_common, d_steps);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace fpm

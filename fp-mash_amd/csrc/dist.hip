@@ -782,61 +782,33 @@ __global__ __launch_bounds__(64 * kRankWaves) void rank_rows_kernel(
 #undef FPM_RANK_NP
 }
 
-template <typename C>
-static hipError_t merge_rows_c(const uint64_t *d_cand, const uint64_t *row_seg, uint32_t n_qry,
-                               const uint64_t *d_ref, const uint32_t *d_ref_len,
-                               uint64_t ref_stride, uint32_t n_ref, const uint64_t *d_qry,
-                               const uint32_t *d_qry_len, uint64_t qry_stride, uint32_t S,
-                               bool sym, C *d_numer, C *d_denom, uint32_t *d_cnum,
-                               uint32_t *d_cden, hipStream_t st, uint32_t q_lo,
-                               uint32_t *rank_cap, CmpRows cmp)
+hipError_t launch_merge_rows(const CandList &cl, const uint64_t *row_seg, const RowSet &R,
+                             const RowSet &Q, uint32_t S, bool sym, Counts cnt, CmpRows cmp,
+                             uint32_t *rank_cap, hipStream_t st)
 {
-    const dim3 g(xcd_grid(n_qry)), b(64 * kRankWaves);
-    const uint64_t cap = std::max(ref_stride, qry_stride);
+    if (!Q.n) return hipSuccess;
+    const dim3 g(xcd_grid(Q.n)), b(64 * kRankWaves);
+    const uint64_t cap = std::max(R.stride, Q.stride);
+    if (cap > 2048) return hipErrorInvalidValue;
     if (rank_cap) *rank_cap = cap <= 1024 ? 1024u : 2048u;
-    if (cmp.rows) {
-        // the compacted rows of one set against itself, every row's probe behind us
-        if (!cmp.len || !sym || d_ref != d_qry || ref_stride != qry_stride || q_lo != 0 ||
-            n_qry != n_ref || cap > 2048)
-            return hipErrorInvalidValue;
-        if (cap <= 1024)
-            hipLaunchKernelGGL((rank_rows_kernel<1024, C, true>), g, b, 0, st, d_cand, row_seg,
-                               n_qry, q_lo, d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len,
-                               qry_stride, S, (uint32_t)sym, d_numer, d_denom, d_cnum, d_cden, cmp);
-        else
-            hipLaunchKernelGGL((rank_rows_kernel<2048, C, true>), g, b, 0, st, d_cand, row_seg,
-                               n_qry, q_lo, d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len,
-                               qry_stride, S, (uint32_t)sym, d_numer, d_denom, d_cnum, d_cden, cmp);
-        return hipGetLastError();
-    }
-    if (cap <= 1024)
-        hipLaunchKernelGGL((rank_rows_kernel<1024, C>), g, b, 0, st, d_cand, row_seg, n_qry, q_lo,
-                           d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len, qry_stride, S,
-                           (uint32_t)sym, d_numer, d_denom, d_cnum, d_cden, cmp);
-    else if (cap <= 2048)
-        hipLaunchKernelGGL((rank_rows_kernel<2048, C>), g, b, 0, st, d_cand, row_seg, n_qry, q_lo,
-                           d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len, qry_stride, S,
-                           (uint32_t)sym, d_numer, d_denom, d_cnum, d_cden, cmp);
-    else
+    // the compacted rows of one set against itself, every row's probe behind us
+    if (cmp.rows && (!cmp.len || !sym || R.rows != Q.rows || R.stride != Q.stride || Q.n != R.n))
         return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-hipError_t launch_merge_rows(const uint64_t *d_cand, const uint64_t *row_seg, uint32_t n_qry,
-                             const uint64_t *d_ref, const uint32_t *d_ref_len, uint64_t ref_stride,
-                             uint32_t n_ref, const uint64_t *d_qry, const uint32_t *d_qry_len,
-                             uint64_t qry_stride, uint32_t S, bool sym, Counts cnt,
-                             uint32_t *d_cnum, uint32_t *d_cden, hipStream_t st, uint32_t q_lo,
-                             uint32_t *rank_cap, CmpRows cmp)
-{
-    if (!n_qry) return hipSuccess;
-    if (cnt.c16)
-        return merge_rows_c(d_cand, row_seg, n_qry, d_ref, d_ref_len, ref_stride, n_ref, d_qry,
-                            d_qry_len, qry_stride, S, sym, (uint16_t *)cnt.numer,
-                            (uint16_t *)cnt.denom, d_cnum, d_cden, st, q_lo, rank_cap, cmp);
-    return merge_rows_c(d_cand, row_seg, n_qry, d_ref, d_ref_len, ref_stride, n_ref, d_qry,
-                        d_qry_len, qry_stride, S, sym, (uint32_t *)cnt.numer,
-                        (uint32_t *)cnt.denom, d_cnum, d_cden, st, q_lo, rank_cap, cmp);
+    return with_counts(cnt, [&](auto c) {
+        using C = decltype(c);
+        const auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, g, b, 0, st, (const uint64_t *)cl.cand, row_seg, Q.n, 0u,
+                               (const uint64_t *)R.rows, R.len, R.stride, R.n,
+                               (const uint64_t *)Q.rows, Q.len, Q.stride, S, (uint32_t)sym,
+                               (C *)cnt.numer, (C *)cnt.denom, cl.cnum, cl.cden, cmp);
+            return hipGetLastError();
+        };
+        if (cmp.rows)
+            return cap <= 1024 ? launch(rank_rows_kernel<1024, C, true>)
+                               : launch(rank_rows_kernel<2048, C, true>);
+        return cap <= 1024 ? launch(rank_rows_kernel<1024, C, false>)
+                           : launch(rank_rows_kernel<2048, C, false>);
+    });
 }
 
 // ---- FP64 p-value (same algorithm as the oracle restatement)
@@ -967,8 +939,46 @@ __device__ double pvalue_dev(uint32_t x, uint64_t len_ref, uint64_t len_qry, dou
     return beta_P(r, (double)k + 1.0, (double)n - (double)k);
 }
 
-// distance (CommandDistance.cpp:404-419), p-value and the -d / -v filters, one pair per
-// thread (a candidate's p-value continued fraction stays on its own lane)
+// Distance (CommandDistance.cpp:404-419), p-value and the -d / -v pass of one pair from its
+// counts: the only copy of the reference's per-pair arithmetic.  Every finalize and list kernel
+// below calls it, so the full and the compact outputs cannot drift apart.
+__device__ __forceinline__ void cell_values(uint32_t c, uint32_t d, uint64_t len_ref,
+                                            uint64_t len_qry, uint32_t kmer_size,
+                                            double kmer_space, double max_dist, double max_pvalue,
+                                            double &dv, double &pv, bool &ok)
+{
+    if (c == d) dv = 0.0;
+    else if (c == 0) dv = 1.0;
+    else {
+        double jac = (double)c / (double)d;
+        dv = -log(2.0 * jac / (1.0 + jac)) / (double)kmer_size;
+        if (dv > 1.0) dv = 1.0;
+    }
+    ok = !(max_dist >= 0 && dv > max_dist);
+    pv = 0.0;
+    if (ok) {
+        pv = pvalue_dev(c, len_ref, len_qry, kmer_space, d);
+        ok = !(max_pvalue >= 0 && pv > max_pvalue);
+    }
+}
+
+// cell_values of cell o into the full outputs
+__device__ __forceinline__ void finalize_cell(uint64_t o, uint32_t c, uint32_t d, uint64_t len_ref,
+                                              uint64_t len_qry, uint32_t kmer_size,
+                                              double kmer_space, double max_dist,
+                                              double max_pvalue, double *dist, double *pval,
+                                              uint8_t *pass)
+{
+    double dv, pv;
+    bool ok;
+    cell_values(c, d, len_ref, len_qry, kmer_size, kmer_space, max_dist, max_pvalue, dv, pv, ok);
+    dist[o] = dv;
+    pval[o] = pv;
+    if (pass) pass[o] = ok ? 1 : 0;
+}
+
+// every cell of a computed grid, one pair per thread (a candidate's p-value continued fraction
+// stays on its own lane)
 template <typename C>
 __global__ __launch_bounds__(256) void dist_finalize_kernel(
     const C *__restrict__ numer, const C *__restrict__ denom,
@@ -979,31 +989,51 @@ __global__ __launch_bounds__(256) void dist_finalize_kernel(
 {
     const uint64_t o = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= n_pairs) return;
-    const uint32_t c = numer[o], d = denom[o];
     const uint32_t r = (uint32_t)(o % n_ref), q = (uint32_t)(o / n_ref);
-    double dv;
-    if (c == d) dv = 0.0;
-    else if (c == 0) dv = 1.0;
-    else {
-        double jac = (double)c / (double)d;
-        dv = -log(2.0 * jac / (1.0 + jac)) / (double)kmer_size;
-        if (dv > 1.0) dv = 1.0;
-    }
-    bool ok = !(max_dist >= 0 && dv > max_dist);
-    double pv = 0.0;
-    if (ok) {
-        pv = pvalue_dev(c, ref_length[r], qry_length[q], kmer_space, d);
-        ok = !(max_pvalue >= 0 && pv > max_pvalue);
-    }
-    dist[o] = dv;
-    pval[o] = pv;
-    if (pass) pass[o] = ok ? 1 : 0;
+    finalize_cell(o, numer[o], denom[o], ref_length[r], qry_length[q], kmer_size, kmer_space,
+                  max_dist, max_pvalue, dist, pval, pass);
 }
 
-// Every cell's no-shared-hash values (PairFill): a pure write stream, 25 B per cell, one
-// workgroup per 1024 cells of one query row (row = blockIdx.x / blocks-per-row, uniform).
-// VEC (n_ref % 4 == 0, so a row starts 4-cell aligned): each lane writes 4 consecutive
-// cells with 16-B stores (1 KiB per wave store; the pass bytes as one dword).
+// Every cell's no-shared-hash values (PairFill): a pure write stream, 25 B per cell.
+
+// Four consecutive cells o .. o + 3 of one query row (its list length lq, the four refs' in rl)
+// with 16-B stores (1 KiB per wave store; the pass bytes as one dword): the body of both 4-cell
+// fills.  keep1 / pkeep: a distance / a p-value of 1 passes the -d / -v filter.
+template <typename C>
+__device__ __forceinline__ void fill_cells4(uint64_t o, uint4 rl, uint32_t lq, uint32_t S,
+                                            bool keep1, bool pkeep, C *numer, C *denom,
+                                            const PairFill &fill)
+{
+    const uint32_t d[4] = {rl.x + lq, rl.y + lq, rl.z + lq, rl.w + lq};  // <= 2 stride
+    uint32_t dn[4], pa = 0;
+    double dv[4], pv[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const bool ok = d[u] == 0 || keep1;
+        dn[u] = d[u] < S ? d[u] : S;
+        dv[u] = d[u] == 0 ? 0.0 : 1.0;
+        pv[u] = ok ? 1.0 : 0.0;
+        pa |= (ok && pkeep ? 1u : 0u) << (8 * u);
+    }
+    // plain stores: non-temporal ones (nt) let the candidate compare beside run 15%
+    // faster but slowed this stream by 20% (step 1.99 -> 2.14 ms); 16-B write-through
+    // (sc1) buffer stores slowed it 1.9x (0.9 -> 1.67 ms beside the compare)
+    if (numer) {
+        store_counts4(numer + o, 0, 0, 0, 0);
+        store_counts4(denom + o, dn[0], dn[1], dn[2], dn[3]);
+    }
+    if (fill.out.dist) {     // (null: the counts only, the compact output)
+        *(double2 *)(fill.out.dist + o) = make_double2(dv[0], dv[1]);
+        *(double2 *)(fill.out.dist + o + 2) = make_double2(dv[2], dv[3]);
+        *(double2 *)(fill.out.pval + o) = make_double2(pv[0], pv[1]);
+        *(double2 *)(fill.out.pval + o + 2) = make_double2(pv[2], pv[3]);
+        if (fill.out.pass) *(uint32_t *)(fill.out.pass + o) = pa;
+    }
+}
+
+// Row-aligned: one workgroup per 1024 cells of one query row (row = blockIdx.x / blocks-per-row,
+// uniform).  VEC (n_ref % 4 == 0, so a row starts 4-cell aligned): each lane writes 4
+// consecutive cells (fill_cells4).
 constexpr uint32_t kFillCells = 1024;
 template <bool VEC, typename C>
 __global__ __launch_bounds__(256) void dist_fill_kernel(
@@ -1020,33 +1050,8 @@ __global__ __launch_bounds__(256) void dist_fill_kernel(
     if (VEC) {
         const uint32_t r = rb * kFillCells + threadIdx.x * 4;
         if (r >= n_ref) continue;
-        const uint64_t o = row + r;
-        const uint4 rl = *(const uint4 *)(ref_len + r);
-        const uint32_t d[4] = {rl.x + lq, rl.y + lq, rl.z + lq, rl.w + lq};  // <= 2 stride
-        uint32_t dn[4], pa = 0;
-        double dv[4], pv[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const bool ok = d[u] == 0 || keep1;
-            dn[u] = d[u] < S ? d[u] : S;
-            dv[u] = d[u] == 0 ? 0.0 : 1.0;
-            pv[u] = ok ? 1.0 : 0.0;
-            pa |= (ok && pkeep ? 1u : 0u) << (8 * u);
-        }
-        // plain stores: non-temporal ones (nt) let the candidate compare beside run 15%
-        // faster but slowed this stream by 20% (step 1.99 -> 2.14 ms); 16-B write-through
-        // (sc1) buffer stores slowed it 1.9x (0.9 -> 1.67 ms beside the compare)
-        if (numer) {
-            store_counts4(numer + o, 0, 0, 0, 0);
-            store_counts4(denom + o, dn[0], dn[1], dn[2], dn[3]);
-        }
-        if (fill.dist) {     // (null: the counts only, the compact output)
-            *(double2 *)(fill.dist + o) = make_double2(dv[0], dv[1]);
-            *(double2 *)(fill.dist + o + 2) = make_double2(dv[2], dv[3]);
-            *(double2 *)(fill.pval + o) = make_double2(pv[0], pv[1]);
-            *(double2 *)(fill.pval + o + 2) = make_double2(pv[2], pv[3]);
-            if (fill.pass) *(uint32_t *)(fill.pass + o) = pa;
-        }
+        fill_cells4(row + r, *(const uint4 *)(ref_len + r), lq, S, keep1, pkeep, numer, denom,
+                    fill);
         continue;
     }
 #pragma unroll
@@ -1060,10 +1065,10 @@ __global__ __launch_bounds__(256) void dist_fill_kernel(
             numer[o] = 0;
             denom[o] = (C)(d < S ? d : S);
         }
-        if (!fill.dist) continue;
-        fill.dist[o] = d == 0 ? 0.0 : 1.0;
-        fill.pval[o] = ok ? 1.0 : 0.0;
-        if (fill.pass) fill.pass[o] = ok && pkeep ? 1 : 0;
+        if (!fill.out.dist) continue;
+        fill.out.dist[o] = d == 0 ? 0.0 : 1.0;
+        fill.out.pval[o] = ok ? 1.0 : 0.0;
+        if (fill.out.pass) fill.out.pass[o] = ok && pkeep ? 1 : 0;
     }
     }
 }
@@ -1092,38 +1097,15 @@ __global__ __launch_bounds__(256) void dist_fill_flat_kernel(
     int64_t rr = (int64_t)(o - (uint64_t)q * n_ref);
     if (rr < 0) { q--; rr += n_ref; }
     else if (rr >= (int64_t)n_ref) { q++; rr -= n_ref; }
-    const uint32_t r = (uint32_t)rr;
     const uint32_t lq = qry_len[q];
-    const uint4 rl = *(const uint4 *)(ref_len + r);
-    const uint32_t d[4] = {rl.x + lq, rl.y + lq, rl.z + lq, rl.w + lq};  // <= 2 stride
-    uint32_t dn[4], pa = 0;
-    double dv[4], pv[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-        const bool ok = d[u] == 0 || keep1;
-        dn[u] = d[u] < S ? d[u] : S;
-        dv[u] = d[u] == 0 ? 0.0 : 1.0;
-        pv[u] = ok ? 1.0 : 0.0;
-        pa |= (ok && pkeep ? 1u : 0u) << (8 * u);
-    }
-    if (numer) {
-        store_counts4(numer + o, 0, 0, 0, 0);
-        store_counts4(denom + o, dn[0], dn[1], dn[2], dn[3]);
-    }
-    if (fill.dist) {         // (null: the counts only, the compact output)
-        *(double2 *)(fill.dist + o) = make_double2(dv[0], dv[1]);
-        *(double2 *)(fill.dist + o + 2) = make_double2(dv[2], dv[3]);
-        *(double2 *)(fill.pval + o) = make_double2(pv[0], pv[1]);
-        *(double2 *)(fill.pval + o + 2) = make_double2(pv[2], pv[3]);
-        if (fill.pass) *(uint32_t *)(fill.pass + o) = pa;
-    }
+    fill_cells4(o, *(const uint4 *)(ref_len + (uint32_t)rr), lq, S, keep1, pkeep, numer, denom,
+                fill);
 }
 
-hipError_t launch_dist_fill(const uint32_t *d_ref_len, uint32_t n_ref, const uint32_t *d_qry_len,
-                            uint32_t n_qry, uint32_t S, Counts cnt, const PairFill &fill,
-                            hipStream_t st, bool flat)
+hipError_t launch_dist_fill(const RowSet &R, const RowSet &Q, uint32_t S, Counts cnt,
+                            const PairFill &fill, bool flat, hipStream_t st)
 {
-    void *d_numer = cnt.numer, *d_denom = cnt.denom;
+    const uint32_t n_ref = R.n, n_qry = Q.n;
     if (!n_ref || !n_qry) return hipSuccess;
     const uint32_t nrb = (n_ref + kFillCells - 1) / kFillCells;
     const uint64_t blocks = (uint64_t)nrb * n_qry;
@@ -1131,38 +1113,32 @@ hipError_t launch_dist_fill(const uint32_t *d_ref_len, uint32_t n_ref, const uin
     // 16-B stores need 16-B aligned rows of every output (the pass row as 4-B aligned)
     const auto al = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
     // (null outputs are aligned)
-    const bool vec = n_ref % 4 == 0 && al(d_ref_len, 16) && al(d_numer, 16) &&
-                     al(d_denom, 16) && al(fill.dist, 16) && al(fill.pval, 16) &&
-                     al(fill.pass, 4);
-    // the full grid: short workgroups hand their slots back to the candidate compare running
-    // beside (a capped grid-stride fill of 256-4096 workgroups held them and measured slower)
-    const uint32_t grid = (uint32_t)blocks;
+    const bool vec = n_ref % 4 == 0 && al(R.len, 16) && al(cnt.numer, 16) &&
+                     al(cnt.denom, 16) && al(fill.out.dist, 16) && al(fill.out.pval, 16) &&
+                     al(fill.out.pass, 4);
     const uint64_t cells = (uint64_t)n_ref * n_qry;
-    if (flat && vec && cells < (1ULL << 50)) {
-        const uint64_t fb = (cells / 4 + 255) / 256;
-        if (fb >= (1ULL << 31)) return hipErrorInvalidValue;
-        const double inv_n = 1.0 / (double)n_ref;
-#define FPM_FLAT(C_)                                                                               \
-    hipLaunchKernelGGL((dist_fill_flat_kernel<C_>), dim3((uint32_t)fb), dim3(256), 0, st,          \
-                       d_ref_len, n_ref, d_qry_len, cells, inv_n, S, (C_ *)d_numer, (C_ *)d_denom, \
-                       fill)
-        if (cnt.c16) FPM_FLAT(uint16_t);
-        else FPM_FLAT(uint32_t);
-#undef FPM_FLAT
+    const uint64_t fb = (cells / 4 + 255) / 256;
+    const bool flat_fill = flat && vec && cells < (1ULL << 50);
+    if (flat_fill && fb >= (1ULL << 31)) return hipErrorInvalidValue;
+    return with_counts(cnt, [&](auto c) {
+        using C = decltype(c);
+        C *numer = (C *)cnt.numer, *denom = (C *)cnt.denom;
+        // the full grid: short workgroups hand their slots back to the candidate compare running
+        // beside (a capped grid-stride fill of 256-4096 workgroups held them and measured slower)
+        const auto rows = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(256), 0, st, R.len, n_ref,
+                               Q.len, nrb, (uint32_t)blocks, S, numer, denom, fill);
+        };
+        if (flat_fill)
+            hipLaunchKernelGGL((dist_fill_flat_kernel<C>), dim3((uint32_t)fb), dim3(256), 0, st,
+                               R.len, n_ref, Q.len, cells, 1.0 / (double)n_ref, S, numer, denom,
+                               fill);
+        else if (vec)
+            rows(dist_fill_kernel<true, C>);
+        else
+            rows(dist_fill_kernel<false, C>);
         return hipGetLastError();
-    }
-#define FPM_FILL(V, C)                                                                         \
-    hipLaunchKernelGGL((dist_fill_kernel<V, C>), dim3(grid), dim3(256), 0, st, d_ref_len, n_ref, \
-                       d_qry_len, nrb, (uint32_t)blocks, S, (C *)d_numer, (C *)d_denom, fill)
-    if (cnt.c16) {
-        if (vec) FPM_FILL(true, uint16_t);
-        else FPM_FILL(false, uint16_t);
-    } else {
-        if (vec) FPM_FILL(true, uint32_t);
-        else FPM_FILL(false, uint32_t);
-    }
-#undef FPM_FILL
-    return hipGetLastError();
+    });
 }
 
 // A compact grid's counts before its sketches exist (fpm_dist_list_prefill): numer 0 and
@@ -1231,46 +1207,19 @@ __global__ __launch_bounds__(256) void dist_counts_fixup_kernel(
     }
 }
 
-hipError_t launch_dist_counts_fixup(const uint32_t *d_ref_len, uint32_t n_ref,
-                                    const uint32_t *d_qry_len, uint32_t n_qry, uint32_t S,
-                                    uint16_t *denom, hipStream_t st)
+hipError_t launch_dist_counts_fixup(const RowSet &R, const RowSet &Q, uint32_t S, uint16_t *denom,
+                                    hipStream_t st)
 {
-    if (!n_ref || !n_qry) return hipSuccess;
-    hipLaunchKernelGGL(dist_counts_fixup_kernel, dim3((n_qry + 63) / 64), dim3(256), 0, st,
-                       d_ref_len, n_ref, d_qry_len, n_qry, S, denom);
+    if (!R.n || !Q.n) return hipSuccess;
+    hipLaunchKernelGGL(dist_counts_fixup_kernel, dim3((Q.n + 63) / 64), dim3(256), 0, st, R.len,
+                       R.n, Q.len, Q.n, S, denom);
     return hipGetLastError();
 }
 
-// The same per-pair arithmetic as dist_finalize_kernel, for the candidate cells of the
-// sparse path only (the probe wrote every other cell's final values).  Grid-stride over the
-// device-side candidate count; with `sym` each candidate (q, r) (one of the pair's two cells,
-// probe_rows_kernel) also finalizes its mirror (r, q), whose numer / denom the rank kernel
-// wrote.
-__device__ __forceinline__ void finalize_cell(uint64_t o, uint32_t c, uint32_t d, uint64_t len_ref,
-                                              uint64_t len_qry, uint32_t kmer_size,
-                                              double kmer_space, double max_dist,
-                                              double max_pvalue, double *dist, double *pval,
-                                              uint8_t *pass)
-{
-    double dv;
-    if (c == d) dv = 0.0;
-    else if (c == 0) dv = 1.0;
-    else {
-        double jac = (double)c / (double)d;
-        dv = -log(2.0 * jac / (1.0 + jac)) / (double)kmer_size;
-        if (dv > 1.0) dv = 1.0;
-    }
-    bool ok = !(max_dist >= 0 && dv > max_dist);
-    double pv = 0.0;
-    if (ok) {
-        pv = pvalue_dev(c, len_ref, len_qry, kmer_space, d);
-        ok = !(max_pvalue >= 0 && pv > max_pvalue);
-    }
-    dist[o] = dv;
-    pval[o] = pv;
-    if (pass) pass[o] = ok ? 1 : 0;
-}
-
+// The candidate cells of the sparse path only (the probe wrote every other cell's final values).
+// Grid-stride over the device-side candidate count; with `sym` each candidate (q, r) (one of the
+// pair's two cells, probe_rows_kernel) also finalizes its mirror (r, q), whose numer / denom the
+// rank kernel wrote.
 template <typename C>
 __global__ __launch_bounds__(256) void dist_cand_finalize_kernel(
     const uint64_t *__restrict__ cand, const unsigned long long *__restrict__ n_cand,
@@ -1307,65 +1256,40 @@ __global__ __launch_bounds__(256) void dist_cand_finalize_kernel(
             finalize_cell(o2, nm, dn, ref_length[q], qry_length[r], kmer_size, kmer_space,
                           max_dist, max_pvalue, dist, pval, pass);
         }
-        if (mir.dist) {        // transposed grid: ref r as the query, query q as the ref
+        if (mir.out.dist) {    // transposed grid: ref r as the query, query q as the ref
             const uint64_t o2 = (uint64_t)r * mir.n_qry + q;
             ((C *)mir.cnt.numer)[o2] = (C)nm;
             ((C *)mir.cnt.denom)[o2] = (C)dn;
             finalize_cell(o2, nm, dn, qry_length[q], ref_length[r], kmer_size, kmer_space,
-                          max_dist, max_pvalue, mir.dist, mir.pval, mir.pass);
+                          max_dist, max_pvalue, mir.out.dist, mir.out.pval, mir.out.pass);
         }
     }
 }
 
-hipError_t launch_dist_cand_finalize(const uint64_t *d_cand, const unsigned long long *d_n_cand,
-                                     uint64_t cap, bool sym, const uint32_t *d_cnum,
-                                     const uint32_t *d_cden, Counts cnt,
-                                     const uint64_t *d_ref_length,
-                                     const uint64_t *d_qry_length, uint32_t n_ref,
-                                     uint32_t kmer_size, double kmer_space, double max_dist,
-                                     double max_pvalue, double *d_dist, double *d_pvalue,
-                                     uint8_t *d_pass, const MirrorOut &mir, hipStream_t st)
+hipError_t launch_dist_cand_finalize(const CandList &cl, bool sym, Counts cnt, const RowSet &R,
+                                     const RowSet &Q, const DistParams &par, const CellOut &out,
+                                     const MirrorOut &mir, hipStream_t st)
 {
-    if (!cap) return hipSuccess;
-    if (mir.dist && (!mir.cnt.numer || !mir.cnt.denom || mir.cnt.c16 != cnt.c16 || !d_cnum))
+    if (!cl.cap) return hipSuccess;
+    if (mir.out.dist && (!mir.cnt.numer || !mir.cnt.denom || mir.cnt.c16 != cnt.c16 || !cl.cnum))
         return hipErrorInvalidValue;
-    const uint64_t blocks = std::min<uint64_t>((cap + 255) / 256, 4096);
-#define FPM_CFIN(C)                                                                          \
-    hipLaunchKernelGGL(dist_cand_finalize_kernel<C>, dim3((uint32_t)blocks), dim3(256), 0, st,  \
-                       d_cand, d_n_cand, (uint32_t)sym, d_cnum, d_cden, (C *)cnt.numer,        \
-                       (C *)cnt.denom, d_ref_length, d_qry_length, n_ref, kmer_size,           \
-                       kmer_space, max_dist, max_pvalue, d_dist, d_pvalue, d_pass, mir)
-    if (cnt.c16) FPM_CFIN(uint16_t);
-    else FPM_CFIN(uint32_t);
-#undef FPM_CFIN
-    return hipGetLastError();
+    const uint64_t blocks = std::min<uint64_t>((cl.cap + 255) / 256, 4096);
+    return with_counts(cnt, [&](auto c) {
+        using C = decltype(c);
+        hipLaunchKernelGGL(dist_cand_finalize_kernel<C>, dim3((uint32_t)blocks), dim3(256), 0, st,
+                           (const uint64_t *)cl.cand, (const unsigned long long *)cl.n,
+                           (uint32_t)sym, (const uint32_t *)cl.cnum, (const uint32_t *)cl.cden,
+                           (C *)cnt.numer, (C *)cnt.denom, R.length, Q.length, R.n, par.kmer_size,
+                           par.kmer_space, par.max_dist, par.max_pvalue, out.dist, out.pval,
+                           out.pass, mir);
+        return hipGetLastError();
+    });
 }
 
 // ---- Compact output: dense numer / denom cells plus a list of the
 // cells that share hashes (numer > 0) with their distance / p-value / pass.  Every other cell
 // has closed-form values (CommandDistance.cpp:404-419, 433-450 at common = 0), so nothing is
 // written for it beyond its counts.
-
-// distance, p-value and -d / -v pass of one cell (finalize_cell's arithmetic, by value)
-__device__ __forceinline__ void cell_values(uint32_t c, uint32_t d, uint64_t len_ref,
-                                            uint64_t len_qry, uint32_t kmer_size,
-                                            double kmer_space, double max_dist, double max_pvalue,
-                                            double &dv, double &pv, bool &ok)
-{
-    if (c == d) dv = 0.0;
-    else if (c == 0) dv = 1.0;
-    else {
-        double jac = (double)c / (double)d;
-        dv = -log(2.0 * jac / (1.0 + jac)) / (double)kmer_size;
-        if (dv > 1.0) dv = 1.0;
-    }
-    ok = !(max_dist >= 0 && dv > max_dist);
-    pv = 0.0;
-    if (ok) {
-        pv = pvalue_dev(c, len_ref, len_qry, kmer_space, d);
-        ok = !(max_pvalue >= 0 && pv > max_pvalue);
-    }
-}
 
 // Distance and p-value of n independent cells from their counts and genome lengths (the
 // optional batch call of SURVEY §8(b): the values the compact output leaves out, for the cells
@@ -1390,22 +1314,18 @@ __global__ __launch_bounds__(256) void pvalue_batch_kernel(const C *__restrict__
     if (pvalue) pvalue[i] = pv;
 }
 
-hipError_t launch_pvalue_batch(const void *numer, const void *denom, uint32_t count_bytes,
-                               const uint64_t *len_ref, const uint64_t *len_qry, uint64_t n,
-                               uint32_t kmer_size, double kmer_space, double *dist,
-                               double *pvalue, hipStream_t st)
+hipError_t launch_pvalue_batch(Counts cnt, const uint64_t *len_ref, const uint64_t *len_qry,
+                               uint64_t n, const DistParams &par, double *dist, double *pvalue,
+                               hipStream_t st)
 {
     if (!n) return hipSuccess;
-    const dim3 g((uint32_t)((n + 255) / 256));
-    if (count_bytes == 2)
-        hipLaunchKernelGGL(pvalue_batch_kernel<uint16_t>, g, dim3(256), 0, st,
-                           (const uint16_t *)numer, (const uint16_t *)denom, len_ref, len_qry, n,
-                           kmer_size, kmer_space, dist, pvalue);
-    else
-        hipLaunchKernelGGL(pvalue_batch_kernel<uint32_t>, g, dim3(256), 0, st,
-                           (const uint32_t *)numer, (const uint32_t *)denom, len_ref, len_qry, n,
-                           kmer_size, kmer_space, dist, pvalue);
-    return hipGetLastError();
+    return with_counts(cnt, [&](auto c) {
+        using C = decltype(c);
+        hipLaunchKernelGGL(pvalue_batch_kernel<C>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0,
+                           st, (const C *)cnt.numer, (const C *)cnt.denom, len_ref, len_qry, n,
+                           par.kmer_size, par.kmer_space, dist, pvalue);
+        return hipGetLastError();
+    });
 }
 
 // Block-wide slot reservation: thread t needs k_t entries; returns its first slot.  One
@@ -1548,45 +1468,39 @@ __global__ __launch_bounds__(kListThreads) void dist_grid_list_kernel(
     }
 }
 
-hipError_t launch_dist_cand_list(const uint64_t *d_cand, const unsigned long long *d_n_cand,
-                                 uint64_t cap, bool sym, const uint32_t *d_cnum,
-                                 const uint32_t *d_cden, Counts cnt, const uint64_t *d_ref_length,
-                                 const uint64_t *d_qry_length, uint32_t n_ref, uint32_t kmer_size,
-                                 double kmer_space, double max_dist, double max_pvalue,
-                                 const CellList &list, Counts mcnt, uint32_t m_nqry,
-                                 const CellList &mlist, hipStream_t st)
+hipError_t launch_dist_cand_list(const CandList &cl, bool sym, Counts cnt, const RowSet &R,
+                                 const RowSet &Q, const DistParams &par, const CellList &list,
+                                 Counts mcnt, const CellList &mlist, hipStream_t st)
 {
-    if (!cap) return hipSuccess;
-    if (mcnt.numer && (!mcnt.denom || mcnt.c16 != cnt.c16 || !d_cnum || !mlist.count))
+    if (!cl.cap) return hipSuccess;
+    if (mcnt.numer && (!mcnt.denom || mcnt.c16 != cnt.c16 || !cl.cnum || !mlist.count))
         return hipErrorInvalidValue;
-    const uint64_t blocks = std::min<uint64_t>((cap + kListThreads - 1) / kListThreads, 4096);
-#define FPM_CLIST(C)                                                                          \
-    hipLaunchKernelGGL(dist_cand_list_kernel<C>, dim3((uint32_t)blocks), dim3(kListThreads), 0, st, \
-                       d_cand, d_n_cand, (uint32_t)sym, d_cnum, d_cden, (C *)cnt.numer,        \
-                       (C *)cnt.denom, d_ref_length, d_qry_length, n_ref, kmer_size,           \
-                       kmer_space, max_dist, max_pvalue, list, mcnt, m_nqry, mlist)
-    if (cnt.c16) FPM_CLIST(uint16_t);
-    else FPM_CLIST(uint32_t);
-#undef FPM_CLIST
-    return hipGetLastError();
+    const uint64_t blocks = std::min<uint64_t>((cl.cap + kListThreads - 1) / kListThreads, 4096);
+    return with_counts(cnt, [&](auto c) {
+        using C = decltype(c);
+        hipLaunchKernelGGL(dist_cand_list_kernel<C>, dim3((uint32_t)blocks), dim3(kListThreads), 0,
+                           st, (const uint64_t *)cl.cand, (const unsigned long long *)cl.n,
+                           (uint32_t)sym, (const uint32_t *)cl.cnum, (const uint32_t *)cl.cden,
+                           (C *)cnt.numer, (C *)cnt.denom, R.length, Q.length, R.n, par.kmer_size,
+                           par.kmer_space, par.max_dist, par.max_pvalue, list, mcnt, Q.n, mlist);
+        return hipGetLastError();
+    });
 }
 
-hipError_t launch_dist_grid_list(Counts cnt, uint32_t n_ref, uint32_t n_qry,
-                                 const uint64_t *d_ref_length, const uint64_t *d_qry_length,
-                                 uint32_t kmer_size, double kmer_space, double max_dist,
-                                 double max_pvalue, const CellList &list, hipStream_t st)
+hipError_t launch_dist_grid_list(Counts cnt, const RowSet &R, const RowSet &Q,
+                                 const DistParams &par, const CellList &list, hipStream_t st)
 {
-    const uint64_t n = (uint64_t)n_ref * n_qry;
+    const uint64_t n = (uint64_t)R.n * Q.n;
     if (!n) return hipSuccess;
     const uint64_t blocks = std::min<uint64_t>((n / 4 + kListThreads - 1) / kListThreads + 1, 1u << 16);
-#define FPM_GLIST(C)                                                                          \
-    hipLaunchKernelGGL(dist_grid_list_kernel<C>, dim3((uint32_t)blocks), dim3(kListThreads), 0, st, \
-                       (const C *)cnt.numer, (const C *)cnt.denom, n_ref, n, d_ref_length,     \
-                       d_qry_length, kmer_size, kmer_space, max_dist, max_pvalue, list)
-    if (cnt.c16) FPM_GLIST(uint16_t);
-    else FPM_GLIST(uint32_t);
-#undef FPM_GLIST
-    return hipGetLastError();
+    return with_counts(cnt, [&](auto c) {
+        using C = decltype(c);
+        hipLaunchKernelGGL(dist_grid_list_kernel<C>, dim3((uint32_t)blocks), dim3(kListThreads), 0,
+                           st, (const C *)cnt.numer, (const C *)cnt.denom, R.n, n, R.length,
+                           Q.length, par.kmer_size, par.kmer_space, par.max_dist, par.max_pvalue,
+                           list);
+        return hipGetLastError();
+    });
 }
 
 // triangle -fp's compareFingerprints (CommandTriangle.cpp:255-302): positional compare of
@@ -1619,93 +1533,61 @@ __global__ __launch_bounds__(256) void positional_grid_kernel(
     pass[o] = (dv <= max_dist && pv <= max_pvalue) ? 1 : 0;
 }
 
-hipError_t launch_positional_grid(const void *d_ref, const uint32_t *d_ref_len,
-                                  uint64_t ref_stride, uint32_t n_ref, const void *d_qry,
-                                  const uint32_t *d_qry_len, uint64_t qry_stride, uint32_t n_qry,
-                                  uint32_t hash_bytes, double max_dist, double max_pvalue,
-                                  uint32_t *d_numer, uint32_t *d_denom, double *d_dist,
-                                  double *d_pvalue, uint8_t *d_pass, hipStream_t st)
+hipError_t launch_positional_grid(const RowSet &R, const RowSet &Q, uint32_t hash_bytes,
+                                  double max_dist, double max_pvalue, uint32_t *d_numer,
+                                  uint32_t *d_denom, const CellOut &out, hipStream_t st)
 {
-    if (!n_ref || !n_qry) return hipSuccess;
-    const dim3 g((n_ref + 255) / 256, n_qry);
-    if (n_qry > 65535) return hipErrorInvalidValue;
-    if (hash_bytes == 8)
-        hipLaunchKernelGGL(positional_grid_kernel<uint64_t>, g, dim3(256), 0, st,
-                           (const uint64_t *)d_ref, d_ref_len, ref_stride, n_ref,
-                           (const uint64_t *)d_qry, d_qry_len, qry_stride, n_qry, max_dist,
-                           max_pvalue, d_numer, d_denom, d_dist, d_pvalue, d_pass);
-    else
-        hipLaunchKernelGGL(positional_grid_kernel<uint32_t>, g, dim3(256), 0, st,
-                           (const uint32_t *)d_ref, d_ref_len, ref_stride, n_ref,
-                           (const uint32_t *)d_qry, d_qry_len, qry_stride, n_qry, max_dist,
-                           max_pvalue, d_numer, d_denom, d_dist, d_pvalue, d_pass);
-    return hipGetLastError();
+    if (!R.n || !Q.n) return hipSuccess;
+    if (Q.n > 65535) return hipErrorInvalidValue;
+    return with_hash(hash_bytes, [&](auto h) {
+        using H = decltype(h);
+        hipLaunchKernelGGL(positional_grid_kernel<H>, dim3((R.n + 255) / 256, Q.n), dim3(256), 0,
+                           st, (const H *)R.rows, R.len, R.stride, R.n, (const H *)Q.rows, Q.len,
+                           Q.stride, Q.n, max_dist, max_pvalue, d_numer, d_denom, out.dist,
+                           out.pval, out.pass);
+        return hipGetLastError();
+    });
 }
 
-template <typename C>
-static hipError_t compare_grid_c(const void *d_ref, const uint32_t *d_ref_len, uint64_t ref_stride,
-                                 uint32_t n_ref, const void *d_qry, const uint32_t *d_qry_len,
-                                 uint64_t qry_stride, uint32_t n_qry, uint32_t hash_bytes,
-                                 uint32_t sketch_size, C *d_numer, C *d_denom, hipStream_t st,
-                                 bool *took_lds)
+template <typename H, typename C>
+static hipError_t compare_grid_t(const RowSet &R, const RowSet &Q, uint32_t sketch_size, Counts cnt,
+                                 bool *took_lds, hipStream_t st)
 {
-    if (took_lds) *took_lds = false;
-    if (n_ref == 0 || n_qry == 0) return hipSuccess;
-    dim3 grid((n_ref + kTile - 1) / kTile, (n_qry + kTile - 1) / kTile);
+    const H *ref = (const H *)R.rows, *qry = (const H *)Q.rows;
+    C *numer = (C *)cnt.numer, *denom = (C *)cnt.denom;
+    dim3 grid((R.n + kTile - 1) / kTile, (Q.n + kTile - 1) / kTile);
     // LDS-staged walk when the tile's 32 lists of W = min(S, stride) entries fit
-    {
-        constexpr size_t kMaxLds = 156 * 1024;
-        const uint64_t W = std::min<uint64_t>({(uint64_t)sketch_size, std::max(ref_stride, qry_stride)});
-        constexpr int kBlk = kWalkBlk;
-        const size_t lds = (size_t)2 * kTile * ((W + kBlk + 3) & ~3ull) * hash_bytes;
-        if (W > 0 && lds <= kMaxLds && (hash_bytes == 4 || hash_bytes == 8)) {
-            const void *fn = hash_bytes == 8 ? (const void *)compare_grid_lds_kernel<uint64_t, kBlk, C>
-                                             : (const void *)compare_grid_lds_kernel<uint32_t, kBlk, C>;
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds) ==
-                hipSuccess) {
-                if (took_lds) *took_lds = true;
-                if (hash_bytes == 8)
-                    hipLaunchKernelGGL((compare_grid_lds_kernel<uint64_t, kBlk, C>), grid, dim3(256), lds, st,
-                                       (const uint64_t *)d_ref, d_ref_len, ref_stride, n_ref,
-                                       (const uint64_t *)d_qry, d_qry_len, qry_stride, n_qry,
-                                       sketch_size, (uint32_t)W, d_numer, d_denom);
-                else
-                    hipLaunchKernelGGL((compare_grid_lds_kernel<uint32_t, kBlk, C>), grid, dim3(256), lds, st,
-                                       (const uint32_t *)d_ref, d_ref_len, ref_stride, n_ref,
-                                       (const uint32_t *)d_qry, d_qry_len, qry_stride, n_qry,
-                                       sketch_size, (uint32_t)W, d_numer, d_denom);
-                return hipGetLastError();
-            }
-            (void)hipGetLastError();
+    constexpr size_t kMaxLds = 156 * 1024;
+    constexpr int kBlk = kWalkBlk;
+    const uint64_t W = std::min<uint64_t>(sketch_size, std::max(R.stride, Q.stride));
+    const size_t lds = (size_t)2 * kTile * ((W + kBlk + 3) & ~3ull) * sizeof(H);
+    if (W > 0 && lds <= kMaxLds) {
+        if (hipFuncSetAttribute((const void *)compare_grid_lds_kernel<H, kBlk, C>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds) ==
+            hipSuccess) {
+            if (took_lds) *took_lds = true;
+            hipLaunchKernelGGL((compare_grid_lds_kernel<H, kBlk, C>), grid, dim3(256), lds, st, ref,
+                               R.len, R.stride, R.n, qry, Q.len, Q.stride, Q.n, sketch_size,
+                               (uint32_t)W, numer, denom);
+            return hipGetLastError();
         }
+        (void)hipGetLastError();
     }
-    if (hash_bytes == 8)
-        hipLaunchKernelGGL((compare_grid_kernel<uint64_t, C>), grid, dim3(256), 0, st,
-                           (const uint64_t *)d_ref, d_ref_len, ref_stride, n_ref,
-                           (const uint64_t *)d_qry, d_qry_len, qry_stride, n_qry, sketch_size,
-                           d_numer, d_denom);
-    else if (hash_bytes == 4)
-        hipLaunchKernelGGL((compare_grid_kernel<uint32_t, C>), grid, dim3(256), 0, st,
-                           (const uint32_t *)d_ref, d_ref_len, ref_stride, n_ref,
-                           (const uint32_t *)d_qry, d_qry_len, qry_stride, n_qry, sketch_size,
-                           d_numer, d_denom);
-    else
-        return hipErrorInvalidValue;
+    hipLaunchKernelGGL((compare_grid_kernel<H, C>), grid, dim3(256), 0, st, ref, R.len, R.stride,
+                       R.n, qry, Q.len, Q.stride, Q.n, sketch_size, numer, denom);
     return hipGetLastError();
 }
 
-hipError_t launch_compare_grid(const void *d_ref, const uint32_t *d_ref_len, uint64_t ref_stride,
-                               uint32_t n_ref, const void *d_qry, const uint32_t *d_qry_len,
-                               uint64_t qry_stride, uint32_t n_qry, uint32_t hash_bytes,
-                               uint32_t sketch_size, Counts cnt, hipStream_t st, bool *lds)
+hipError_t launch_compare_grid(const RowSet &R, const RowSet &Q, uint32_t hash_bytes,
+                               uint32_t sketch_size, Counts cnt, bool *lds, hipStream_t st)
 {
-    if (cnt.c16)
-        return compare_grid_c(d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len, qry_stride,
-                              n_qry, hash_bytes, sketch_size, (uint16_t *)cnt.numer,
-                              (uint16_t *)cnt.denom, st, lds);
-    return compare_grid_c(d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len, qry_stride, n_qry,
-                          hash_bytes, sketch_size, (uint32_t *)cnt.numer, (uint32_t *)cnt.denom,
-                          st, lds);
+    if (lds) *lds = false;
+    if (R.n == 0 || Q.n == 0) return hipSuccess;
+    return with_hash(hash_bytes, [&](auto h) {
+        return with_counts(cnt, [&](auto c) {
+            return compare_grid_t<decltype(h), decltype(c)>(R, Q, sketch_size, cnt, lds, st);
+        });
+    });
 }
 
 // ---- Dense walk of u32 lists on 16-bit rank images (the -fp shape: C3).
@@ -2056,16 +1938,14 @@ void compare_grid_img_scratch(uint32_t n_qry, uint32_t sketch_size, uint64_t ref
     *bimg_bytes = (uint64_t)n_qry * Wimg * 2 + 64;
 }
 
-template <typename C>
-static hipError_t compare_grid_img_c(const uint32_t *ref, const uint32_t *ref_len,
-                                     uint64_t ref_stride, uint32_t n_ref, const uint32_t *qry,
-                                     const uint32_t *qry_len, uint64_t qry_stride, uint32_t n_qry,
-                                     uint32_t S, void *ublk_p, void *bimg_p, C *numer, C *denom,
-                                     hipStream_t st)
+hipError_t launch_compare_grid_img(const RowSet &R, const RowSet &Q, uint32_t S, void *ublk_p,
+                                   void *bimg_p, Counts cnt, hipStream_t st)
 {
+    if (R.n == 0 || Q.n == 0) return hipSuccess;
     constexpr int kBlk = kImgBlk3;
-    const uint32_t W = (uint32_t)std::min<uint64_t>(S, std::max(ref_stride, qry_stride));
-    const uint32_t nqb = (n_qry + kImgTile - 1) / kImgTile, nrb = (n_ref + kImgTile - 1) / kImgTile;
+    const uint32_t *ref = (const uint32_t *)R.rows, *qry = (const uint32_t *)Q.rows;
+    const uint32_t W = (uint32_t)std::min<uint64_t>(S, std::max(R.stride, Q.stride));
+    const uint32_t nqb = (Q.n + kImgTile - 1) / kImgTile, nrb = (R.n + kImgTile - 1) / kImgTile;
     const uint32_t Wimg = (W + 7) & ~7u, Wp = img_row_u16(W, kBlk);
     uint32_t *ublk = (uint32_t *)ublk_p, *usize = ublk + (size_t)nqb * kImgBlk;
     uint16_t *bimg = (uint16_t *)bimg_p;
@@ -2074,97 +1954,59 @@ static hipError_t compare_grid_img_c(const uint32_t *ref, const uint32_t *ref_le
     if (hipError_t e = hipFuncSetAttribute((const void *)qblock_union_kernel,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_u))
         return e;
-    const void *fn = (const void *)compare_grid_img_kernel<kBlk, C>;
-    if (hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t))
-        return e;
-    hipLaunchKernelGGL(qblock_union_kernel, dim3(nqb), dim3(1024), lds_u, st, qry, qry_len,
-                       qry_stride, n_qry, W, Wimg, ublk, usize, bimg);
     // a 1-D grid: kXcds x (the XCD's own ref blocks x query blocks + its share of the leftover
     // tiles) (the kernel's tile map)
     const uint32_t per = nrb / kXcds, rem = nrb - per * kXcds;
     const uint32_t grid = kXcds * (per * nqb + (rem * nqb + kXcds - 1) / kXcds);
-    hipLaunchKernelGGL((compare_grid_img_kernel<kBlk, C>), dim3(grid, 1), dim3(1024),
-                       lds_t, st, ref, ref_len, ref_stride, n_ref, qry_len, n_qry,
-                       (const uint32_t *)ublk, (const uint32_t *)usize, (const uint16_t *)bimg,
-                       Wimg, S, W, nrb, numer, denom);
-    return hipGetLastError();
+    return with_counts(cnt, [&](auto c) {
+        using C = decltype(c);
+        if (hipError_t e = hipFuncSetAttribute((const void *)compare_grid_img_kernel<kBlk, C>,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)lds_t))
+            return e;
+        hipLaunchKernelGGL(qblock_union_kernel, dim3(nqb), dim3(1024), lds_u, st, qry, Q.len,
+                           Q.stride, Q.n, W, Wimg, ublk, usize, bimg);
+        hipLaunchKernelGGL((compare_grid_img_kernel<kBlk, C>), dim3(grid, 1), dim3(1024), lds_t, st,
+                           ref, R.len, R.stride, R.n, Q.len, Q.n, (const uint32_t *)ublk,
+                           (const uint32_t *)usize, (const uint16_t *)bimg, Wimg, S, W, nrb,
+                           (C *)cnt.numer, (C *)cnt.denom);
+        return hipGetLastError();
+    });
 }
 
-hipError_t launch_compare_grid_img(const void *d_ref, const uint32_t *d_ref_len,
-                                   uint64_t ref_stride, uint32_t n_ref, const void *d_qry,
-                                   const uint32_t *d_qry_len, uint64_t qry_stride, uint32_t n_qry,
-                                   uint32_t sketch_size, void *ublk, void *bimg, Counts cnt,
-                                   hipStream_t st)
-{
-    if (n_ref == 0 || n_qry == 0) return hipSuccess;
-    if (cnt.c16)
-        return compare_grid_img_c((const uint32_t *)d_ref, d_ref_len, ref_stride, n_ref,
-                                  (const uint32_t *)d_qry, d_qry_len, qry_stride, n_qry,
-                                  sketch_size, ublk, bimg, (uint16_t *)cnt.numer,
-                                  (uint16_t *)cnt.denom, st);
-    return compare_grid_img_c((const uint32_t *)d_ref, d_ref_len, ref_stride, n_ref,
-                              (const uint32_t *)d_qry, d_qry_len, qry_stride, n_qry, sketch_size,
-                              ublk, bimg, (uint32_t *)cnt.numer, (uint32_t *)cnt.denom, st);
-}
-
-template <typename C>
-static hipError_t walk_candidates_c(const uint64_t *d_cand, const unsigned long long *d_n_cand,
-                                    uint64_t cap, const void *d_ref, const uint32_t *d_ref_len,
-                                    uint64_t ref_stride, uint32_t n_ref, const void *d_qry,
-                                    const uint32_t *d_qry_len, uint64_t qry_stride,
-                                    uint32_t hash_bytes, uint32_t S, RecRows rr, RecRows rq,
-                                    C *d_numer, C *d_denom, hipStream_t st)
-{
-    dim3 grid((uint32_t)((cap + 255) / 256));
-    if (hash_bytes == 8)
-        hipLaunchKernelGGL((walk_cand_kernel<uint64_t, C>), grid, dim3(256), 0, st, d_cand, d_n_cand,
-                           (const uint64_t *)d_ref, d_ref_len, ref_stride, n_ref,
-                           (const uint64_t *)d_qry, d_qry_len, qry_stride, S, rr, rq, d_numer,
-                           d_denom);
-    else
-        hipLaunchKernelGGL((walk_cand_kernel<uint32_t, C>), grid, dim3(256), 0, st, d_cand, d_n_cand,
-                           (const uint32_t *)d_ref, d_ref_len, ref_stride, n_ref,
-                           (const uint32_t *)d_qry, d_qry_len, qry_stride, S, rr, rq, d_numer,
-                           d_denom);
-    return hipGetLastError();
-}
-
-hipError_t launch_walk_candidates(const uint64_t *d_cand, const unsigned long long *d_n_cand,
-                                  uint64_t cap, const void *d_ref, const uint32_t *d_ref_len,
-                                  uint64_t ref_stride, uint32_t n_ref, const void *d_qry,
-                                  const uint32_t *d_qry_len, uint64_t qry_stride,
+hipError_t launch_walk_candidates(const CandList &cl, const RowSet &R, const RowSet &Q,
                                   uint32_t hash_bytes, uint32_t S, Counts cnt, RecRows rec_ref,
                                   RecRows rec_qry, hipStream_t st)
 {
-    if (!cap) return hipSuccess;
+    if (!cl.cap) return hipSuccess;
     if (!rec_ref.val || !rec_qry.val) rec_ref = rec_qry = RecRows{};   // both sides or neither
-    if (cnt.c16)
-        return walk_candidates_c(d_cand, d_n_cand, cap, d_ref, d_ref_len, ref_stride, n_ref, d_qry,
-                                 d_qry_len, qry_stride, hash_bytes, S, rec_ref, rec_qry,
-                                 (uint16_t *)cnt.numer, (uint16_t *)cnt.denom, st);
-    return walk_candidates_c(d_cand, d_n_cand, cap, d_ref, d_ref_len, ref_stride, n_ref, d_qry,
-                             d_qry_len, qry_stride, hash_bytes, S, rec_ref, rec_qry,
-                             (uint32_t *)cnt.numer, (uint32_t *)cnt.denom, st);
+    const dim3 grid((uint32_t)((cl.cap + 255) / 256));
+    return with_hash(hash_bytes, [&](auto h) {
+        return with_counts(cnt, [&](auto c) {
+            using H = decltype(h);
+            using C = decltype(c);
+            hipLaunchKernelGGL((walk_cand_kernel<H, C>), grid, dim3(256), 0, st,
+                               (const uint64_t *)cl.cand, (const unsigned long long *)cl.n,
+                               (const H *)R.rows, R.len, R.stride, R.n, (const H *)Q.rows, Q.len,
+                               Q.stride, S, rec_ref, rec_qry, (C *)cnt.numer, (C *)cnt.denom);
+            return hipGetLastError();
+        });
+    });
 }
 
-hipError_t launch_dist_finalize(Counts cnt, const uint64_t *d_ref_length, const uint64_t *d_qry_length,
-                                uint32_t n_ref, uint32_t n_qry, uint32_t kmer_size,
-                                double kmer_space, double max_dist, double max_pvalue,
-                                double *d_dist, double *d_pvalue, uint8_t *d_pass,
-                                hipStream_t st)
+hipError_t launch_dist_finalize(Counts cnt, const RowSet &R, const RowSet &Q, const DistParams &par,
+                                const CellOut &out, hipStream_t st)
 {
-    uint64_t n = (uint64_t)n_ref * n_qry;
+    const uint64_t n = (uint64_t)R.n * Q.n;
     if (n == 0) return hipSuccess;
-    const uint64_t blocks = (n + 255) / 256;
-#define FPM_DFIN(C)                                                                          \
-    hipLaunchKernelGGL(dist_finalize_kernel<C>, dim3((uint32_t)blocks), dim3(256), 0, st,       \
-                       (const C *)cnt.numer, (const C *)cnt.denom, d_ref_length, d_qry_length, \
-                       n_ref, n, kmer_size, kmer_space, max_dist, max_pvalue, d_dist, d_pvalue, \
-                       d_pass)
-    if (cnt.c16) FPM_DFIN(uint16_t);
-    else FPM_DFIN(uint32_t);
-#undef FPM_DFIN
-    return hipGetLastError();
+    return with_counts(cnt, [&](auto c) {
+        using C = decltype(c);
+        hipLaunchKernelGGL(dist_finalize_kernel<C>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0,
+                           st, (const C *)cnt.numer, (const C *)cnt.denom, R.length, Q.length, R.n,
+                           n, par.kmer_size, par.kmer_space, par.max_dist, par.max_pvalue,
+                           out.dist, out.pval, out.pass);
+        return hipGetLastError();
+    });
 }
 
 // screen's pValueWithin (CommandScreen.cpp:386-406) for n references, r = setSize / kmerSpace

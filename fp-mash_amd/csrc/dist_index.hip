@@ -1200,22 +1200,18 @@ __global__ __launch_bounds__(64 * kRecWaves) void record_rows_kernel(
     if (lane == 0) out_len[row] = cnt;
 }
 
-hipError_t launch_record_rows(const void *in, const uint32_t *in_len, uint64_t in_stride,
-                              uint32_t n, uint32_t hash_bytes, uint32_t S, void *out,
+hipError_t launch_record_rows(const RowSet &in, uint32_t hash_bytes, uint32_t S, void *out,
                               uint32_t *pos_out, uint32_t *out_len, uint64_t out_stride,
-                              hipStream_t st, uint32_t *unsorted)
+                              uint32_t *unsorted, hipStream_t st)
 {
-    if (!n) return hipSuccess;
-    const dim3 g((n + kRecWaves - 1) / kRecWaves), b(64 * kRecWaves);
-    if (hash_bytes == 8)
-        hipLaunchKernelGGL(record_rows_kernel<uint64_t>, g, b, 0, st, (const uint64_t *)in, in_len,
-                           in_stride, n, S, (uint64_t *)out, pos_out, out_len, out_stride,
-                           unsorted);
-    else
-        hipLaunchKernelGGL(record_rows_kernel<uint32_t>, g, b, 0, st, (const uint32_t *)in, in_len,
-                           in_stride, n, S, (uint32_t *)out, pos_out, out_len, out_stride,
-                           unsorted);
-    return hipGetLastError();
+    if (!in.n) return hipSuccess;
+    const dim3 g((in.n + kRecWaves - 1) / kRecWaves), b(64 * kRecWaves);
+    return with_hash(hash_bytes, [&](auto h) {
+        using H = decltype(h);
+        hipLaunchKernelGGL(record_rows_kernel<H>, g, b, 0, st, (const H *)in.rows, in.len,
+                           in.stride, in.n, S, (H *)out, pos_out, out_len, out_stride, unsorted);
+        return hipGetLastError();
+    });
 }
 
 __global__ __launch_bounds__(kPubWords) void publish_kernel(const unsigned long long *__restrict__ src,
@@ -1316,25 +1312,24 @@ uint64_t idx_tent_words(const IdxGeom &g, uint64_t E)
     return g.cap ? (uint64_t)kParts * g.cap : E;
 }
 
-hipError_t launch_idx_build(const void *d_ref, const uint32_t *d_ref_len, uint64_t stride,
-                            uint32_t n_ref, uint32_t hash_bytes, IdxGeom g, uint32_t *tile_hist,
-                            uint32_t *tile_off, uint32_t *scan_s, uint64_t *tent,
-                            uint32_t *dir, uint32_t *entries, uint32_t *unsorted,
-                            unsigned long long *self_events, unsigned long long *zero,
-                            uint32_t nzero, unsigned long long *acc, uint32_t *part_fill,
-                            uint32_t *overflow, hipStream_t st, unsigned long long *zero_x,
-                            unsigned long long *n_entries)
+hipError_t launch_idx_build(const IdxBuild &a, hipStream_t st)
 {
+    const IdxGeom &g = a.g;
+    const void *d_ref = a.rows.rows;
+    const uint32_t *d_ref_len = a.rows.len;
+    const uint64_t stride = a.rows.stride;
+    const uint32_t n_ref = a.rows.n, hash_bytes = a.hash_bytes;
+    if (hash_bytes != 4 && hash_bytes != 8) return hipErrorInvalidValue;
     if (g.vcut && !g.cut) return hipErrorInvalidValue;
     const uint32_t ntiles = g.ntiles;
     const uint64_t magic = stride > 1 ? ~0ULL / stride + 1 : 0;   // row_of's multiplier
     const uint32_t kg = std::max<uint32_t>(1, std::min<uint32_t>(
         (n_ref + kKmaxThreads * kKmaxU - 1) / (kKmaxThreads * kKmaxU), 64));
-    const bool one_pass = g.cap != 0 && part_fill && overflow;
+    const bool one_pass = g.cap != 0 && a.part_fill && a.overflow;
     hipLaunchKernelGGL(idx_kmax_kernel, dim3(kg), dim3(kKmaxThreads), 0, st, d_ref, d_ref_len,
-                       stride, n_ref, hash_bytes, (unsigned long long *)g.kmax, zero, nzero, acc,
-                       one_pass ? part_fill : nullptr, one_pass ? kParts : 0u, zero_x,
-                       g.vcut ? g.cut : 0u, n_entries);
+                       stride, n_ref, hash_bytes, (unsigned long long *)g.kmax, a.zero, a.nzero,
+                       a.acc, one_pass ? a.part_fill : nullptr, one_pass ? kParts : 0u, a.zero_x,
+                       g.vcut ? g.cut : 0u, a.n_entries);
     // level 2: the sub-bucket range split over 2^lsplit workgroups until its counters fit
     // 32 KB and a range's mean entries 24k (C4, E = 5e7: 2 per partition).  The LDS copy: 16k
     // entries (80 KB with the counters, two workgroups per CU) when the ranges' mean fits 12k
@@ -1359,100 +1354,96 @@ hipError_t launch_idx_build(const void *d_ref, const uint32_t *d_ref_len, uint64
             return e;
         hipLaunchKernelGGL(idx_part_scatter1_kernel, dim3(ntiles), dim3(kIdxThreads),
                            (size_t)g.tile * 8, st, d_ref, d_ref_len, (uint32_t)stride, magic,
-                           n_ref, hash_bytes, g, part_fill, tent, unsorted, overflow);
+                           n_ref, hash_bytes, g, a.part_fill, a.tent, a.unsorted, a.overflow);
         hipLaunchKernelGGL(idx_bucket_kernel, bgrid, dim3(kBucketThreads),
-                           (size_t)(cnt_bytes0 + (uint64_t)lds_cap * 4), st, (const uint64_t *)tent,
-                           ntiles, (const uint32_t *)nullptr, g, lds_cap, dir, entries, self_events,
-                           (const uint32_t *)part_fill, lsplit, n_entries);
+                           (size_t)(cnt_bytes0 + (uint64_t)lds_cap * 4), st,
+                           (const uint64_t *)a.tent, ntiles, (const uint32_t *)nullptr, g, lds_cap,
+                           a.dir, a.entries, a.self_events, (const uint32_t *)a.part_fill, lsplit,
+                           a.n_entries);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(idx_part_hist_kernel, dim3(ntiles), dim3(kIdxThreads), 0, st, d_ref,
-                       d_ref_len, (uint32_t)stride, magic, n_ref, hash_bytes, ntiles, tile_hist,
-                       unsorted, g);
+                       d_ref_len, (uint32_t)stride, magic, n_ref, hash_bytes, ntiles, a.tile_hist,
+                       a.unsorted, g);
     const uint64_t nh = (uint64_t)kParts * ntiles;
-    if (hipError_t e = launch_exscan(tile_hist, tile_off, nullptr, nh, scan_s, tile_off + nh, st))
+    if (hipError_t e = launch_exscan(a.tile_hist, a.tile_off, nullptr, nh, a.scan_s,
+                                     a.tile_off + nh, st))
         return e;
     if (hipError_t e = dyn_lds_attr(0, (const void *)idx_part_scatter_kernel, kIdxTile * 8))
         return e;
     hipLaunchKernelGGL(idx_part_scatter_kernel, dim3(ntiles), dim3(kIdxThreads),
                        (size_t)g.tile * 8, st, d_ref, d_ref_len, (uint32_t)stride, magic, n_ref,
-                       hash_bytes, ntiles, (const uint32_t *)tile_hist, (const uint32_t *)tile_off,
-                       g, tent);
+                       hash_bytes, ntiles, (const uint32_t *)a.tile_hist,
+                       (const uint32_t *)a.tile_off, g, a.tent);
     // LDS copy of a partition's entries when they fit beside the counters (two workgroups per
     // CU: 80 KiB each at l2 = 12); cap 0 = every partition on the global two-pass path
     hipLaunchKernelGGL(idx_bucket_kernel, bgrid, dim3(kBucketThreads),
-                       (size_t)(cnt_bytes0 + (uint64_t)lds_cap * 4), st, (const uint64_t *)tent,
-                       ntiles, (const uint32_t *)tile_off, g, lds_cap, dir, entries, self_events,
-                       (const uint32_t *)nullptr, lsplit, n_entries);
+                       (size_t)(cnt_bytes0 + (uint64_t)lds_cap * 4), st, (const uint64_t *)a.tent,
+                       ntiles, (const uint32_t *)a.tile_off, g, lds_cap, a.dir, a.entries,
+                       a.self_events, (const uint32_t *)nullptr, lsplit, a.n_entries);
     return hipGetLastError();
 }
 
-hipError_t launch_probe_count(const void *d_qry, const uint32_t *d_qry_len, uint64_t stride,
-                              uint32_t n_qry, uint32_t hash_bytes, IdxGeom g, const uint32_t *dir,
+hipError_t launch_probe_count(const RowSet &Q, uint32_t hash_bytes, IdxGeom g, const uint32_t *dir,
                               unsigned long long *events, uint32_t *unsorted, hipStream_t st)
 {
-    uint64_t n = (uint64_t)n_qry * stride;
+    if (hash_bytes != 4 && hash_bytes != 8) return hipErrorInvalidValue;
+    const uint64_t n = (uint64_t)Q.n * Q.stride;
     const uint64_t threads = (n + kPC - 1) / kPC;
     if (n) hipLaunchKernelGGL(probe_count_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256),
-                              0, st, d_qry, d_qry_len, stride, n_qry, hash_bytes, g, dir, events,
+                              0, st, Q.rows, Q.len, Q.stride, Q.n, hash_bytes, g, dir, events,
                               unsorted);
     return hipGetLastError();
 }
 
-hipError_t launch_probe_rows(const void *d_qry, const uint32_t *d_qry_len, uint64_t stride,
-                             uint32_t n_qry, uint32_t n_ref, uint32_t hash_bytes, IdxGeom g,
-                             const uint32_t *dir, const uint32_t *entries,
-                             const uint32_t *d_ref_len, uint32_t S, bool sym, bool defaults,
-                             bool self_set, Counts cnt, uint64_t *cand,
-                             unsigned long long *n_cand, uint64_t *row_seg,
-                             const uint32_t *d_qry_it_len, uint32_t *q_unsorted,
-                             unsigned long long *events, uint64_t cap, uint32_t *cand_over,
-                             hipStream_t st, uint32_t q_lo, bool half, CmpRows cmp)
+hipError_t launch_probe_rows(const ProbeRows &a, hipStream_t st)
 {
+    const uint32_t n_qry = a.qry.n, n_ref = a.ref.n;
+    const Counts &cnt = a.cnt;
+    const CmpRows &cmp = a.cmp;
+    if (a.hash_bytes != 4 && a.hash_bytes != 8) return hipErrorInvalidValue;
     if (!n_qry || !n_ref) return hipSuccess;
     // the compacted rows are the half probe's, of u64 rows its kept bits cover, with every ref
     // of a row in one workgroup (all foreign hits of a hash seen in one place)
-    if (cmp.rows && (!half || !cmp.len || hash_bytes != 8 || stride > kCmpMaxRow ||
-                     n_ref > (1u << 19) || q_lo != 0 || n_qry != n_ref))
+    if (cmp.rows && (!a.half || !cmp.len || a.hash_bytes != 8 || a.qry.stride > kCmpMaxRow ||
+                     n_ref > (1u << 19) || a.q_lo != 0 || n_qry != n_ref))
         return hipErrorInvalidValue;
     // the half form is the symmetric probe's, over an index whose flags were cut at this S
     // (and never the skip-count path's: no record rows, no order test, no event count)
-    if (half && (!sym || !self_set || g.cut != S || d_qry_it_len || q_unsorted || events))
+    if (a.half && (!a.sym || !a.self_set || a.g.cut != a.S || a.qry_it_len || a.q_unsorted ||
+                   a.events))
         return hipErrorInvalidValue;
     const uint32_t chunk = 1u << 19;   // refs per workgroup: 64 KiB of LDS bitmap
     const uint32_t nchunks = (n_ref + chunk - 1) / chunk;
     const uint32_t cref = nchunks == 1 ? n_ref : chunk;
     // (half: the seen and both bitmaps, up to 128 KiB, past the default dynamic-LDS limit)
-    const size_t lds = ((cref + 31) / 32) * 4 * (half ? 2 : 1);
-    if (lds > 64 * 1024) {
-        const void *fn = cmp.rows ? (cnt.c16 ? (const void *)probe_rows_kernel<uint16_t, true, true>
-                                             : (const void *)probe_rows_kernel<uint32_t, true, true>)
-                                  : (cnt.c16 ? (const void *)probe_rows_kernel<uint16_t, true>
-                                             : (const void *)probe_rows_kernel<uint32_t, true>);
-        if (hipError_t e = dyn_lds_attr((cnt.c16 ? 3 : 4) + (cmp.rows ? 2 : 0), fn, 128 * 1024))
-            return e;
-    }
+    const size_t lds = ((cref + 31) / 32) * 4 * (a.half ? 2 : 1);
     // vector default stores (4 cells): every row and chunk start 4-cell aligned, buffers
     // 16-B aligned
     const auto al = [](const void *p) { return ((uintptr_t)p & 15) == 0; };
-    const uint32_t vec_defaults = n_ref % 4 == 0 && cref % 4 == 0 && al(d_ref_len) &&
+    const uint32_t vec_defaults = n_ref % 4 == 0 && cref % 4 == 0 && al(a.ref.len) &&
                                   al(cnt.numer) && al(cnt.denom);
-#define FPM_PROBE(C, ...)                                                                       \
-    hipLaunchKernelGGL((probe_rows_kernel<C, __VA_ARGS__>), dim3(xcd_grid(n_qry), nchunks),      \
-                       dim3(256), lds,                                                           \
-                       st, d_qry, d_qry_len, stride, n_qry, q_lo, n_ref, hash_bytes, g, dir,     \
-                       entries, cref,                                                            \
-                       d_ref_len, S, (uint32_t)sym, (uint32_t)defaults, vec_defaults,           \
-                       (uint32_t)self_set, (C *)cnt.numer, (C *)cnt.denom, cand, n_cand, row_seg, \
-                       d_qry_it_len, q_unsorted, events, cap, cand_over, cmp)
-    if (cmp.rows && cnt.c16) FPM_PROBE(uint16_t, true, true);
-    else if (cmp.rows) FPM_PROBE(uint32_t, true, true);
-    else if (cnt.c16 && half) FPM_PROBE(uint16_t, true);
-    else if (cnt.c16) FPM_PROBE(uint16_t, false);
-    else if (half) FPM_PROBE(uint32_t, true);
-    else FPM_PROBE(uint32_t, false);
-#undef FPM_PROBE
-    return hipGetLastError();
+    return with_counts(cnt, [&](auto c) {
+        using C = decltype(c);
+        const auto launch = [&](auto kernel, int lds_slot) {
+            if (lds > 64 * 1024)
+                if (hipError_t e = dyn_lds_attr(lds_slot + (cnt.c16 ? 0 : 1), (const void *)kernel,
+                                                128 * 1024))
+                    return e;
+            hipLaunchKernelGGL(kernel, dim3(xcd_grid(n_qry), nchunks), dim3(256), lds, st,
+                               a.qry.rows, a.qry.len, a.qry.stride, n_qry, a.q_lo, n_ref,
+                               a.hash_bytes, a.g, a.dir, a.entries, cref, a.ref.len, a.S,
+                               (uint32_t)a.sym, (uint32_t)a.defaults, vec_defaults,
+                               (uint32_t)a.self_set, (C *)cnt.numer, (C *)cnt.denom, a.out.cand,
+                               a.out.n, a.row_seg, a.qry_it_len, a.q_unsorted, a.events, a.out.cap,
+                               a.cand_over, cmp);
+            return hipGetLastError();
+        };
+        // (dyn_lds_attr slots 3 / 4: the half form by count width, 5 / 6: with compacted rows)
+        if (cmp.rows) return launch(probe_rows_kernel<C, true, true>, 5);
+        if (a.half) return launch(probe_rows_kernel<C, true, false>, 3);
+        return launch(probe_rows_kernel<C, false, false>, 3);
+    });
 }
 
 }  // namespace fpm

@@ -6,16 +6,14 @@
 
 namespace {
 
-int contain_impl(fpm_ctx *ctx, const void *d_ref, const uint32_t *d_ref_len, uint64_t ref_stride,
-                 uint32_t n_ref, const void *d_qry, const uint32_t *d_qry_len,
-                 uint64_t qry_stride, uint32_t n_qry, uint32_t hash_bytes, uint32_t *d_common,
-                 uint32_t *d_steps, void *stream)
+int contain_impl(fpm_ctx *ctx, const RowSet &R, const RowSet &Q, uint32_t hash_bytes,
+                 uint32_t *d_common, uint32_t *d_steps, void *stream)
 {
     if (int rc = set_device(ctx)) return rc;
     if (hash_bytes != 4 && hash_bytes != 8) return fail(FPM_EINVAL, "hash_bytes must be 4 or 8");
     ctx->last_contain_kernel = FPM_CK_NONE;
-    if ((uint64_t)n_ref * n_qry == 0) return FPM_OK;
-    if (!d_ref || !d_ref_len || !d_qry || !d_qry_len || !d_common || !d_steps)
+    if ((uint64_t)R.n * Q.n == 0) return FPM_OK;
+    if (!R.rows || !R.len || !Q.rows || !Q.len || !d_common || !d_steps)
         return fail(FPM_EINVAL, "fpm_contain: null buffer");
     hipStream_t st = pick_stream(ctx, stream);
     bool literal = ctx->contain_mode == FPM_CONTAIN_LITERAL;
@@ -25,8 +23,7 @@ int contain_impl(fpm_ctx *ctx, const void *d_ref, const uint32_t *d_ref_len, uin
         HIP_TRY(scratch(ctx, kSlotCounters, kCtrWords * 8, &ctr));
         uint32_t *flag = (uint32_t *)((unsigned long long *)ctr + kCtrContain);
         HIP_TRY(hipMemsetAsync(flag, 0, 8, st));
-        HIP_TRY(launch_rows_ascending(d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len,
-                                      qry_stride, n_qry, hash_bytes, flag, st));
+        HIP_TRY(launch_rows_ascending(R, Q, hash_bytes, flag, st));
         uint32_t host[2] = {0, 0};
         HIP_TRY(hipMemcpyAsync(host, flag, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -35,14 +32,11 @@ int contain_impl(fpm_ctx *ctx, const void *d_ref, const uint32_t *d_ref_len, uin
     }
     TimedLaunch tl(ctx, FPM_K_COMPARE, st);
     if (literal) {
-        HIP_TRY(launch_contain_literal(d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len,
-                                       qry_stride, n_qry, hash_bytes, d_common, d_steps, st));
+        HIP_TRY(launch_contain_literal(R, Q, hash_bytes, d_common, d_steps, st));
         ctx->last_contain_kernel = FPM_CK_LITERAL;
     } else {
         bool lds = false;
-        HIP_TRY(launch_contain_rows(d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len,
-                                    qry_stride, n_qry, hash_bytes, max_qry_len, d_common, d_steps,
-                                    st, &lds));
+        HIP_TRY(launch_contain_rows(R, Q, hash_bytes, max_qry_len, d_common, d_steps, &lds, st));
         ctx->last_contain_kernel = lds ? FPM_CK_ROWS_LDS : FPM_CK_ROWS_GLOBAL;
     }
     tl.done();
@@ -58,8 +52,9 @@ int fpm_contain_dev(fpm_ctx *ctx, const void *d_ref, const uint32_t *d_ref_len,
                     const uint32_t *d_qry_len, uint64_t qry_stride, uint32_t n_qry,
                     uint32_t hash_bytes, uint32_t *d_common, uint32_t *d_steps, void *stream)
 {
-    return contain_impl(ctx, d_ref, d_ref_len, ref_stride, n_ref, d_qry, d_qry_len, qry_stride,
-                        n_qry, hash_bytes, d_common, d_steps, stream);
+    return contain_impl(ctx, RowSet{d_ref, d_ref_len, nullptr, ref_stride, n_ref},
+                        RowSet{d_qry, d_qry_len, nullptr, qry_stride, n_qry}, hash_bytes, d_common,
+                        d_steps, stream);
 }
 
 int fpm_contain(fpm_ctx *ctx, const void *ref, const uint32_t *ref_len, uint64_t ref_stride,
@@ -87,8 +82,9 @@ int fpm_contain(fpm_ctx *ctx, const void *ref, const uint32_t *ref_len, uint64_t
     if (e == hipSuccess) e = mem.get(&co, np * 4);
     if (e == hipSuccess) e = mem.get(&stp, np * 4);
     if (e != hipSuccess) return fail(FPM_ENOMEM, std::string("contain staging: ") + hipGetErrorString(e));
-    if (int rc = contain_impl(ctx, r, rl, ref_stride, n_ref, same ? r : q, same ? rl : ql, qry_stride,
-                              n_qry, hash_bytes, co, stp, nullptr))
+    if (int rc = contain_impl(ctx, RowSet{r, rl, nullptr, ref_stride, n_ref},
+                              RowSet{same ? r : q, same ? rl : ql, nullptr, qry_stride, n_qry},
+                              hash_bytes, co, stp, nullptr))
         return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(copy_out(ctx, out_common, co, np * 4));

@@ -6,10 +6,28 @@
 // is integer-VALU bound, not HBM bound.
 #pragma once
 
+#include "fpm_kernels.hpp"
+
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace fpm {
+
+// Width dispatch of the launchers: f(C{}) with C the type of a grid's numer / denom cells, and
+// f(H{}) with H the type of the rows' hashes.  Any hash width but 4 and 8 is
+// hipErrorInvalidValue and launches nothing.  f returns the launch's hipError_t.
+template <typename F>
+hipError_t with_counts(const Counts &cnt, F &&f)
+{
+    return cnt.c16 ? f(uint16_t{}) : f(uint32_t{});
+}
+template <typename F>
+hipError_t with_hash(uint32_t hash_bytes, F &&f)
+{
+    if (hash_bytes == 8) return f(uint64_t{});
+    if (hash_bytes == 4) return f(uint32_t{});
+    return hipErrorInvalidValue;
+}
 
 constexpr uint64_t kC1 = 0x87c37b91114253d5ULL;
 constexpr uint64_t kC2 = 0x4cf5ad432745937fULL;

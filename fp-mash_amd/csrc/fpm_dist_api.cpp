@@ -8,28 +8,11 @@
 #include <functional>
 #include <memory>
 
-// A set of sketch rows on the device: n rows of `stride` hashes, each row's entry count and
-// (for the distances) each sequence's length.
-struct RowSet {
-    const void *rows;
-    const uint32_t *len;
-    const uint64_t *length;
-    uint64_t stride;
-    uint32_t n;
-};
-
-// what turns a pair's counts into a distance, a p-value and a pass flag
-struct DistParams {
-    uint32_t kmer_size;
-    double kmer_space, max_dist, max_pvalue;
-};
-
 // One grid's outputs: the counts, and either the full per-cell distance / p-value / pass
 // (fpm_dist_dev*) or the compact list of the cells with numer > 0 (fpm_dist_list_dev*).
 struct DistOut {
     Counts cnt;
-    double *dist = nullptr, *pval = nullptr;
-    uint8_t *pass = nullptr;
+    CellOut cell;
     CellList list{};
 };
 
@@ -123,13 +106,27 @@ static int build_index(fpm_ctx *ctx, const RowSet &R, uint32_t hash_bytes, IdxGe
         uint32_t *overflow = (uint32_t *)(ctr + kCtrOverflow);
         {
             TimedLaunch tl(ctx, FPM_K_INDEX, st);
-            HIP_TRY(launch_idx_build(R.rows, R.len, R.stride, R.n, hash_bytes, g,
-                                     (uint32_t *)tile_hist, (uint32_t *)tile_off,
-                                     (uint32_t *)scan_s, (uint64_t *)tent, dir, entries, unsorted,
-                                     self_events ? ctr : nullptr, ctr, kCtrZeroWords,
-                                     ctr + kCtrKmaxAcc, (uint32_t *)part_fill, overflow, st,
-                                     zero_x, ctr + kCtrIndexed));
-            static_assert(kCtrEntries == kCtrIndexed + 1, "launch_idx_build's n_entries[0..1]");
+            IdxBuild b;
+            b.rows = R;
+            b.hash_bytes = hash_bytes;
+            b.g = g;
+            b.tile_hist = (uint32_t *)tile_hist;
+            b.tile_off = (uint32_t *)tile_off;
+            b.scan_s = (uint32_t *)scan_s;
+            b.tent = (uint64_t *)tent;
+            b.dir = dir;
+            b.entries = entries;
+            b.unsorted = unsorted;
+            b.self_events = self_events ? ctr : nullptr;
+            b.zero = ctr;
+            b.nzero = kCtrZeroWords;
+            b.zero_x = zero_x;
+            b.acc = ctr + kCtrKmaxAcc;
+            b.part_fill = (uint32_t *)part_fill;
+            b.overflow = overflow;
+            b.n_entries = ctr + kCtrIndexed;
+            static_assert(kCtrEntries == kCtrIndexed + 1, "IdxBuild::n_entries[0..1]");
+            HIP_TRY(launch_idx_build(b, st));
             if (int rc = then()) return rc;
             tl.done();
         }
@@ -217,9 +214,9 @@ static int refset_build_index(fpm_refset *rs, hipStream_t st)
         HIP_TRY(grow_slot(rs->slot[fpm_refset::kRecPos], (size_t)R.n * rs->mr * 4, &dref_pos));
         {
             TimedLaunch tl(ctx, FPM_K_INDEX, st);
-            HIP_TRY(launch_record_rows(R.rows, R.len, R.stride, R.n, rs->hash_bytes,
-                                       rs->sketch_size, dref, (uint32_t *)dref_pos,
-                                       (uint32_t *)dref_len, rs->mr, st));
+            HIP_TRY(launch_record_rows(R, rs->hash_bytes, rs->sketch_size, dref,
+                                       (uint32_t *)dref_pos, (uint32_t *)dref_len, rs->mr, nullptr,
+                                       st));
             tl.done();
         }
         geom = make_geom(R.n, (uint64_t)R.n * rs->mr, 0);
@@ -277,6 +274,11 @@ struct SparsePlan {
     const void *p_rows = nullptr;               // the rows the probe reads
     const uint32_t *p_len = nullptr;            // and their lengths (null: the query rows' own)
     uint64_t p_stride = 0;
+    // those rows as the probe count's input
+    RowSet counted(const RowSet &Q) const
+    {
+        return RowSet{p_rows, p_len ? p_len : Q.len, nullptr, p_stride, Q.n};
+    }
     uint64_t ev = 0;
     bool all_sorted = true;
     RecRows rec_r{}, rec_q{};                   // record rows (unsorted lists) for the walk
@@ -297,6 +299,28 @@ static bool probe_half(const Compare &c, const SparsePlan &p, bool sym)
     // (sym already excludes record rows and the skip-count path: neither is a sorted set
     // against itself; the launcher refuses the half form with either)
     return sym && c.ctx->probe_half && p.geom.cut == c.S && !p.p_len && !p.skip_count;
+}
+
+// The probe's arguments that follow from the call and its plan.  The form (sym, defaults, half,
+// cmp) and the skip-count path's outputs are set by the caller.
+static ProbeRows probe_args(const Compare &c, const SparsePlan &p, const CandList &out,
+                            uint64_t *row_seg)
+{
+    ProbeRows a;
+    a.qry = RowSet{p.p_rows, c.Q.len, nullptr, p.p_stride, c.Q.n};
+    a.qry_it_len = p.p_len;
+    a.ref = c.R;
+    a.hash_bytes = c.hash_bytes;
+    a.S = c.S;
+    a.g = p.geom;
+    a.dir = p.dir;
+    a.entries = p.entries;
+    a.self_set = c.self_set;
+    a.cnt = c.cnt;
+    a.out = out;
+    a.row_seg = row_seg;
+    a.cand_over = p.cand_over();
+    return a;
 }
 
 // The transient index of one set against itself leaves out every value above V*, the largest
@@ -368,8 +392,7 @@ static int settle_prefill(Compare &c)
     if (c.prefill_done) return FPM_OK;
     c.prefill_done = true;
     HIP_TRY(hipStreamWaitEvent(c.st, c.ctx->ev_prefill, 0));
-    HIP_TRY(launch_dist_counts_fixup(c.R.len, c.R.n, c.Q.len, c.Q.n, c.S, (uint16_t *)c.cnt.denom,
-                                     c.st));
+    HIP_TRY(launch_dist_counts_fixup(c.R, c.Q, c.S, (uint16_t *)c.cnt.denom, c.st));
     return FPM_OK;
 }
 
@@ -379,12 +402,8 @@ static int launch_fill(Compare &c, bool record_in)
 {
     fpm_ctx *ctx = c.ctx;
     const DistFinal *fin = c.fin;
-    PairFill fill;
-    fill.dist = c.compact ? nullptr : fin->prim.dist;
-    fill.pval = c.compact ? nullptr : fin->prim.pval;
-    fill.pass = c.compact ? nullptr : fin->prim.pass;
-    fill.max_dist = fin->par.max_dist;
-    fill.max_pvalue = fin->par.max_pvalue;
+    // (the compact output: the counts only)
+    PairFill fill{c.compact ? CellOut{} : fin->prim.cell, fin->par.max_dist, fin->par.max_pvalue};
     HIP_TRY(ensure_aux(ctx));
     if (record_in) HIP_TRY(hipEventRecord(ctx->ev_in, c.st));
     HIP_TRY(hipStreamWaitEvent(ctx->aux, ctx->ev_in, 0));
@@ -396,16 +415,11 @@ static int launch_fill(Compare &c, bool record_in)
     // written (both grids with a transpose) times 1.6 exceed the events
     const long double cells_w = (long double)c.n_pairs * (c.want_mir ? 2 : 1);
     const bool flat = cells_w * 1.6L > (long double)ctx->last_events;
-    HIP_TRY(launch_dist_fill(c.R.len, c.R.n, c.Q.len, c.Q.n, c.S, c.fill_cnt ? c.cnt : Counts{},
-                             fill, ctx->aux, flat));
+    HIP_TRY(launch_dist_fill(c.R, c.Q, c.S, c.fill_cnt ? c.cnt : Counts{}, fill, flat, ctx->aux));
     if (c.want_mir) {
-        // the transposed grid: the ref rows as queries against the query rows
-        PairFill mf = fill;
-        mf.dist = c.compact ? nullptr : fin->mir.dist;
-        mf.pval = c.compact ? nullptr : fin->mir.pval;
-        mf.pass = c.compact ? nullptr : fin->mir.pass;
-        HIP_TRY(launch_dist_fill(c.Q.len, c.Q.n, c.R.len, c.R.n, c.S, fin->mir.cnt, mf, ctx->aux,
-                                 flat));
+        // the transposed grid: the query rows as refs, the ref rows as queries
+        fill.out = c.compact ? CellOut{} : fin->mir.cell;
+        HIP_TRY(launch_dist_fill(c.Q, c.R, c.S, fin->mir.cnt, fill, flat, ctx->aux));
     }
     tl.done();
     HIP_TRY(hipEventRecord(ctx->ev_fill, ctx->aux));
@@ -432,8 +446,8 @@ static int index_transient(Compare &c, SparsePlan &p)
     // the query side's probe count behind an index build (a set against itself needs none)
     auto count_probe = [&]() -> int {
         if (!self_set)
-            HIP_TRY(launch_probe_count(p.p_rows, p.p_len ? p.p_len : Q.len, p.p_stride, Q.n,
-                                       hash_bytes, p.geom, p.dir, events, p.unsorted(), st));
+            HIP_TRY(launch_probe_count(p.counted(Q), hash_bytes, p.geom, p.dir, events,
+                                       p.unsorted(), st));
         return FPM_OK;
     };
     // Unsorted lists (-fp): the index runs over each row's records among its first
@@ -455,11 +469,11 @@ static int index_transient(Compare &c, SparsePlan &p)
             HIP_TRY(scratch(ctx, kSlotRecQryPos, (size_t)Q.n * mq * 4, &dqry_pos));
         }
         TimedLaunch tl(ctx, FPM_K_INDEX, st);
-        HIP_TRY(launch_record_rows(R.rows, R.len, R.stride, R.n, hash_bytes, c.S, dref,
-                                   (uint32_t *)dref_pos, (uint32_t *)dref_len, mr, st, flag));
+        HIP_TRY(launch_record_rows(R, hash_bytes, c.S, dref, (uint32_t *)dref_pos,
+                                   (uint32_t *)dref_len, mr, flag, st));
         if (!self_set)
-            HIP_TRY(launch_record_rows(Q.rows, Q.len, Q.stride, Q.n, hash_bytes, c.S, dqry,
-                                       (uint32_t *)dqry_pos, (uint32_t *)dqry_len, mq, st, flag));
+            HIP_TRY(launch_record_rows(Q, hash_bytes, c.S, dqry, (uint32_t *)dqry_pos,
+                                       (uint32_t *)dqry_len, mq, flag, st));
         tl.done();
         return FPM_OK;
     };
@@ -520,11 +534,13 @@ static int index_transient(Compare &c, SparsePlan &p)
         // speculation drops them with it)
         p.spec_cmp = compact_rows(c, p.spec_half);
         TimedLaunch tl(ctx, FPM_K_PROBE, st);
-        HIP_TRY(launch_probe_rows(Q.rows, Q.len, Q.stride, Q.n, R.n, hash_bytes, p.geom, p.dir,
-                                  p.entries, R.len, c.S, self_set, pf.defaults, self_set, c.cnt,
-                                  (uint64_t *)cand, p.n_cand(), (uint64_t *)row_seg, nullptr,
-                                  nullptr, nullptr, pf.cap, p.cand_over(), st, 0, p.spec_half,
-                                  p.spec_cmp));
+        ProbeRows a = probe_args(c, p, CandList{(uint64_t *)cand, p.n_cand(), pf.cap},
+                                 (uint64_t *)row_seg);
+        a.sym = self_set;
+        a.defaults = pf.defaults;
+        a.half = p.spec_half;
+        a.cmp = p.spec_cmp;
+        HIP_TRY(launch_probe_rows(a, st));
         tl.done();
         p.spec_probe = true;
         return FPM_OK;
@@ -599,8 +615,8 @@ static int index_phase(Compare &c, SparsePlan &p)
         HIP_TRY(scratch(ctx, kSlotRecQry, (size_t)Q.n * mq * c.hash_bytes, &dqry));
         HIP_TRY(scratch(ctx, kSlotRecQryLen, (size_t)Q.n * 4, &dqry_len));
         HIP_TRY(scratch(ctx, kSlotRecQryPos, (size_t)Q.n * mq * 4, &dqry_pos));
-        HIP_TRY(launch_record_rows(Q.rows, Q.len, Q.stride, Q.n, c.hash_bytes, c.S, dqry,
-                                   (uint32_t *)dqry_pos, (uint32_t *)dqry_len, mq, st));
+        HIP_TRY(launch_record_rows(Q, c.hash_bytes, c.S, dqry, (uint32_t *)dqry_pos,
+                                   (uint32_t *)dqry_len, mq, nullptr, st));
         p.rec_r = RecRows{rs->slot[fpm_refset::kRecRows].p,
                           (const uint32_t *)rs->slot[fpm_refset::kRecPos].p,
                           (const uint32_t *)rs->slot[fpm_refset::kRecLen].p, rs->mr};
@@ -609,8 +625,7 @@ static int index_phase(Compare &c, SparsePlan &p)
         p.p_len = (const uint32_t *)dqry_len;
         p.p_stride = mq;
     }
-    HIP_TRY(launch_probe_count(p.p_rows, p.p_len ? p.p_len : Q.len, p.p_stride, Q.n,
-                               c.hash_bytes, p.geom, p.dir, p.ctr, p.unsorted(), st));
+    HIP_TRY(launch_probe_count(p.counted(Q), c.hash_bytes, p.geom, p.dir, p.ctr, p.unsorted(), st));
     tl.done();
     if (int rc = read_counters(ctx, p.ctr, kCtrProbeWords, st)) return rc;
     p.ev = host_events(ctx);
@@ -620,17 +635,14 @@ static int index_phase(Compare &c, SparsePlan &p)
     return FPM_OK;
 }
 
-// the rank kernel over the probe's candidates: results into per-candidate slots (cnum / cden)
+// the rank kernel over the probe's candidates: results into cl's per-candidate slots, if any
 // (cmp: the compacted rows the call's probe wrote, if any)
-static hipError_t rank_candidates(const Compare &c, const void *cand, const void *row_seg,
-                                  bool sym, uint32_t *cnum, uint32_t *cden, CmpRows cmp = CmpRows{})
+static hipError_t rank_candidates(const Compare &c, const CandList &cl, const void *row_seg,
+                                  bool sym, CmpRows cmp = CmpRows{})
 {
     uint32_t rank_cap = 0;
-    const hipError_t e =
-        launch_merge_rows((const uint64_t *)cand, (const uint64_t *)row_seg, c.Q.n,
-                          (const uint64_t *)c.R.rows, c.R.len, c.R.stride, c.R.n,
-                          (const uint64_t *)c.Q.rows, c.Q.len, c.Q.stride, c.S, sym, c.cnt, cnum,
-                          cden, c.st, 0, &rank_cap, cmp);
+    const hipError_t e = launch_merge_rows(cl, (const uint64_t *)row_seg, c.R, c.Q, c.S, sym, c.cnt,
+                                           cmp, &rank_cap, c.st);
     c.ctx->last_rank_compact = cmp.rows != nullptr;
     c.ctx->last_cmp_len = cmp.len;
     c.ctx->last_cmp_n = c.R.n;
@@ -674,15 +686,19 @@ static int candidate_phase(Compare &c, SparsePlan &p, bool rows_merge, uint64_t 
     void *cand, *row_seg;
     HIP_TRY(scratch(ctx, kSlotCand, cap * 8, &cand));
     HIP_TRY(scratch(ctx, kSlotRowSeg, (size_t)Q.n * 8, &row_seg));
+    CandList cl{(uint64_t *)cand, p.n_cand(), cap};
     if (!p.spec_probe) {
         TimedLaunch tl(ctx, FPM_K_PROBE, st);
-        HIP_TRY(launch_probe_rows(p.p_rows, Q.len, p.p_stride, Q.n, R.n, c.hash_bytes, p.geom,
-                                  p.dir, p.entries, R.len, c.S, sym, c.probe_defaults(),
-                                  c.self_set, c.cnt, (uint64_t *)cand, p.n_cand(),
-                                  (uint64_t *)row_seg, p.p_len,
-                                  p.skip_count ? p.unsorted() : nullptr,
-                                  p.skip_count ? p.ctr : nullptr, cap, p.cand_over(), st, 0,
-                                  half, cmp));
+        ProbeRows a = probe_args(c, p, cl, (uint64_t *)row_seg);
+        a.sym = sym;
+        a.defaults = c.probe_defaults();
+        a.half = half;
+        a.cmp = cmp;
+        if (p.skip_count) {     // no probe count ran: the probe tests the order and counts
+            a.q_unsorted = p.unsorted();
+            a.events = p.ctr;
+        }
+        HIP_TRY(launch_probe_rows(a, st));
         tl.done();
     }
     // A resident sorted set against a block without a count (skip_count): the rank
@@ -703,8 +719,10 @@ static int candidate_phase(Compare &c, SparsePlan &p, bool rows_merge, uint64_t 
                 HIP_TRY(hipEventRecord(ctx->ev_in, st));
             }
             TimedLaunch tl(ctx, FPM_K_COMPARE, st);
-            HIP_TRY(rank_candidates(c, cand, row_seg, sym, (uint32_t *)cres,
-                                    (uint32_t *)cres + cap));
+            CandList slots = cl;
+            slots.cnum = (uint32_t *)cres;
+            slots.cden = slots.cnum + cap;
+            HIP_TRY(rank_candidates(c, slots, row_seg, sym));
             tl.done();
             rank_done = true;
         }
@@ -721,13 +739,13 @@ static int candidate_phase(Compare &c, SparsePlan &p, bool rows_merge, uint64_t 
     // side stream, and the candidate finalize scatters the results after both.  The
     // literal walk writes cells in place, so it waits for the fill instead.  (Beside the
     // index build or the probe the fill slowed both: they move as many bytes as it does.)
-    uint32_t *cnum = nullptr, *cden = nullptr;
     if (fin && rows_merge) {
         void *cres;
         HIP_TRY(scratch(ctx, kSlotCandRes, cap * 8, &cres));
-        cnum = (uint32_t *)cres;
-        cden = cnum + cap;
+        cl.cnum = (uint32_t *)cres;
+        cl.cden = cl.cnum + cap;
     }
+    const bool cnum = cl.cnum != nullptr;
     // (Submitted before the probe instead, the fill slows the probe more than it gains:
     // C4 one GPU 6.66 -> 6.80-6.86 ms, same box, r04.  Written by the rank kernel's own
     // row workgroups after their candidates instead of beside them: rank 2.7 -> 3.3 ms
@@ -749,11 +767,10 @@ static int candidate_phase(Compare &c, SparsePlan &p, bool rows_merge, uint64_t 
     if (!rank_done) {
         TimedLaunch tl(ctx, FPM_K_COMPARE, st);
         if (rows_merge)
-            HIP_TRY(rank_candidates(c, cand, row_seg, sym, cnum, cden, cmp));
+            HIP_TRY(rank_candidates(c, cl, row_seg, sym, cmp));
         else {
-            HIP_TRY(launch_walk_candidates((const uint64_t *)cand, p.n_cand(), cap, R.rows, R.len,
-                                           R.stride, R.n, Q.rows, Q.len, Q.stride, c.hash_bytes,
-                                           c.S, c.cnt, p.rec_r, p.rec_q, st));
+            HIP_TRY(launch_walk_candidates(cl, R, Q, c.hash_bytes, c.S, c.cnt, p.rec_r, p.rec_q,
+                                           st));
             ctx->last_kernel = FPM_DK_CAND_WALK;
         }
         tl.done();
@@ -769,19 +786,13 @@ static int candidate_phase(Compare &c, SparsePlan &p, bool rows_merge, uint64_t 
         TimedLaunch tl(ctx, FPM_K_FINALIZE, st);
         if (c.compact) {
             const CellList none{};
-            HIP_TRY(launch_dist_cand_list((const uint64_t *)cand, p.n_cand(), cap, sym, cnum, cden,
-                                          c.cnt, R.length, Q.length, R.n, par.kmer_size,
-                                          par.kmer_space, par.max_dist, par.max_pvalue,
-                                          fin->prim.list, mirror ? fin->mir.cnt : Counts{}, Q.n,
+            HIP_TRY(launch_dist_cand_list(cl, sym, c.cnt, R, Q, par, fin->prim.list,
+                                          mirror ? fin->mir.cnt : Counts{},
                                           mirror ? fin->mir.list : none, st));
         } else {
             MirrorOut mir{};
-            if (mirror) mir = MirrorOut{fin->mir.cnt, fin->mir.dist, fin->mir.pval, fin->mir.pass, Q.n};
-            HIP_TRY(launch_dist_cand_finalize((const uint64_t *)cand, p.n_cand(), cap, sym, cnum,
-                                              cden, c.cnt, R.length, Q.length, R.n, par.kmer_size,
-                                              par.kmer_space, par.max_dist, par.max_pvalue,
-                                              fin->prim.dist, fin->prim.pval, fin->prim.pass, mir,
-                                              st));
+            if (mirror) mir = MirrorOut{fin->mir.cnt, fin->mir.cell, Q.n};
+            HIP_TRY(launch_dist_cand_finalize(cl, sym, c.cnt, R, Q, par, fin->prim.cell, mir, st));
         }
         tl.done();
         if (mirror && fin->mirrored) *fin->mirrored = true;
@@ -817,13 +828,11 @@ static int dense_phase(Compare &c)
     }
     TimedLaunch tl(ctx, FPM_K_COMPARE, st);
     if (img) {
-        HIP_TRY(launch_compare_grid_img(R.rows, R.len, R.stride, R.n, Q.rows, Q.len, Q.stride,
-                                        Q.n, c.S, ublk, bimg, c.cnt, st));
+        HIP_TRY(launch_compare_grid_img(R, Q, c.S, ublk, bimg, c.cnt, st));
         ctx->last_kernel = FPM_DK_GRID_IMG;
     } else {
         bool lds = false;
-        HIP_TRY(launch_compare_grid(R.rows, R.len, R.stride, R.n, Q.rows, Q.len, Q.stride, Q.n,
-                                    c.hash_bytes, c.S, c.cnt, st, &lds));
+        HIP_TRY(launch_compare_grid(R, Q, c.hash_bytes, c.S, c.cnt, &lds, st));
         ctx->last_kernel = lds ? FPM_DK_GRID_LDS : FPM_DK_GRID_GLOBAL;
     }
     tl.done();
@@ -942,7 +951,7 @@ static int dist_dev_impl(fpm_ctx *ctx, const RowSet &R, const RowSet &Q, uint32_
     if (!out.cnt.numer || !out.cnt.denom)
         return fail(FPM_EINVAL, std::string(who) + ": numer / denom buffers required");
     if (compact ? (!out.list.qry || !out.list.ref || !out.list.dist || !out.list.pval)
-                : (!out.dist || !out.pval))
+                : (!out.cell.dist || !out.cell.pval))
         return fail(FPM_EINVAL, std::string(who) +
                                     (compact ? ": list qry / ref / distance / p-value buffers required"
                                              : ": distance and p-value buffers required"));
@@ -976,13 +985,9 @@ static int dist_dev_impl(fpm_ctx *ctx, const RowSet &R, const RowSet &Q, uint32_
     if (!finalized) {
         TimedLaunch tl(ctx, FPM_K_FINALIZE, st);
         if (compact)
-            HIP_TRY(launch_dist_grid_list(out.cnt, R.n, Q.n, R.length, Q.length, par.kmer_size,
-                                          par.kmer_space, par.max_dist, par.max_pvalue, out.list,
-                                          st));
+            HIP_TRY(launch_dist_grid_list(out.cnt, R, Q, par, out.list, st));
         else
-            HIP_TRY(launch_dist_finalize(out.cnt, R.length, Q.length, R.n, Q.n, par.kmer_size,
-                                         par.kmer_space, par.max_dist, par.max_pvalue, out.dist,
-                                         out.pval, out.pass, st));
+            HIP_TRY(launch_dist_finalize(out.cnt, R, Q, par, out.cell, st));
         tl.done();
     }
     // the transposed grid, when the compare could not scatter it (dense path, unsorted lists:
@@ -994,7 +999,7 @@ static int dist_dev_impl(fpm_ctx *ctx, const RowSet &R, const RowSet &Q, uint32_
 static DistOut full_out(void *numer, void *denom, bool c16, double *dist, double *pval,
                         uint8_t *pass)
 {
-    return DistOut{Counts{numer, denom, c16}, dist, pval, pass};
+    return DistOut{Counts{numer, denom, c16}, CellOut{dist, pval, pass}};
 }
 
 static int list_out(void *numer, void *denom, bool c16, const fpm_cell_list *l, DistOut &o,
@@ -1205,9 +1210,11 @@ int fpm_dist_finalize_dev(fpm_ctx *ctx, const uint32_t *d_numer, const uint32_t 
     if (int rc = set_device(ctx)) return rc;
     hipStream_t st = pick_stream(ctx, stream);
     TimedLaunch tl(ctx, FPM_K_FINALIZE, st);
-    HIP_TRY(launch_dist_finalize(Counts{(void *)d_numer, (void *)d_denom, false}, d_ref_length,
-                                 d_qry_length, n_ref, n_qry, kmer_size, kmer_space, max_dist,
-                                 max_pvalue, d_dist, d_pvalue, d_pass, st));
+    HIP_TRY(launch_dist_finalize(Counts{(void *)d_numer, (void *)d_denom, false},
+                                 RowSet{nullptr, nullptr, d_ref_length, 0, n_ref},
+                                 RowSet{nullptr, nullptr, d_qry_length, 0, n_qry},
+                                 DistParams{kmer_size, kmer_space, max_dist, max_pvalue},
+                                 CellOut{d_dist, d_pvalue, d_pass}, st));
     tl.done();
     return FPM_OK;
 }
@@ -1223,8 +1230,9 @@ int fpm_pvalue_batch_dev(fpm_ctx *ctx, const void *d_numer, const void *d_denom,
         return fail(FPM_EINVAL, "null input");
     hipStream_t st = pick_stream(ctx, stream);
     TimedLaunch tl(ctx, FPM_K_FINALIZE, st);
-    HIP_TRY(launch_pvalue_batch(d_numer, d_denom, count_bytes, d_len_ref, d_len_qry, n, kmer_size,
-                                kmer_space, d_dist, d_pvalue, st));
+    HIP_TRY(launch_pvalue_batch(Counts{(void *)d_numer, (void *)d_denom, count_bytes == 2},
+                                d_len_ref, d_len_qry, n, DistParams{kmer_size, kmer_space}, d_dist,
+                                d_pvalue, st));
     tl.done();
     return FPM_OK;
 }
@@ -1301,8 +1309,9 @@ int fpm_fp_positional_grid(fpm_ctx *ctx, const void *ref, const uint32_t *ref_le
     g.up(g.ql, qry_len, (size_t)n_qry * 4);
     g.results(np, true);
     if (g.e != hipSuccess) return fail(FPM_ENOMEM, std::string("positional staging: ") + hipGetErrorString(g.e));
-    HIP_TRY(launch_positional_grid(g.r, g.rl, ref_stride, n_ref, g.q, g.ql, qry_stride, n_qry,
-                                   hash_bytes, max_dist, max_pvalue, g.nu, g.de, g.di, g.pv, g.pa,
+    HIP_TRY(launch_positional_grid(RowSet{g.r, g.rl, nullptr, ref_stride, n_ref},
+                                   RowSet{g.q, g.ql, nullptr, qry_stride, n_qry}, hash_bytes,
+                                   max_dist, max_pvalue, g.nu, g.de, CellOut{g.di, g.pv, g.pa},
                                    ctx->stream));
     return g.fetch(np, out_numer, out_denom, out_dist, out_pvalue, out_pass);
 }

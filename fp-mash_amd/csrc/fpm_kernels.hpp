@@ -47,6 +47,40 @@ struct Counts {
     bool c16 = false;
 };
 
+// A set of sketch rows on the device: n rows of `stride` hashes, each row's entry count and
+// (for the distances) each sequence's length, null where a launcher has no use for it.  The two
+// sides of a launch are two of these, ref first: a swap (the transposed fill) shows as one.
+struct RowSet {
+    const void *rows = nullptr;
+    const uint32_t *len = nullptr;
+    const uint64_t *length = nullptr;
+    uint64_t stride = 0;
+    uint32_t n = 0;
+};
+
+// what turns a pair's counts into a distance, a p-value and a pass flag (max_dist / max_pvalue
+// < 0: no -d / -v filter)
+struct DistParams {
+    uint32_t kmer_size = 0;
+    double kmer_space = 0, max_dist = -1, max_pvalue = -1;
+};
+
+// the full per-cell outputs of a grid beside its counts (pass may be null)
+struct CellOut {
+    double *dist = nullptr, *pval = nullptr;
+    uint8_t *pass = nullptr;
+};
+
+// The probe's candidate cells (cell index q * n_ref + r): cand[0 .. *n), at most cap.  cnum /
+// cden non-null: the rank kernel's (numer, denom) of candidate c go to slot c instead of the grid
+// cells, and the candidate finalize / list scatters them; null: the counts are in the grid.
+struct CandList {
+    uint64_t *cand = nullptr;
+    unsigned long long *n = nullptr;
+    uint64_t cap = 0;
+    uint32_t *cnum = nullptr, *cden = nullptr;
+};
+
 // Tile capacity classes (k-mer starts per tile).
 constexpr int kTileClasses = 6;
 constexpr uint32_t kTileCap[kTileClasses] = {256, 512, 1024, 2048, 4096, 8192};
@@ -137,12 +171,9 @@ hipError_t launch_merge(const MergeDesc *d_desc, uint32_t n, uint32_t s, bool sm
 hipError_t launch_fp_hash(const uint64_t *d_vals, const uint64_t *d_line_off, uint64_t n_lines,
                           uint32_t seed, uint32_t use64, void *d_out, hipStream_t st);
 
-hipError_t launch_compare_grid(const void *d_ref, const uint32_t *d_ref_len, uint64_t ref_stride,
-                               uint32_t n_ref, const void *d_qry, const uint32_t *d_qry_len,
-                               uint64_t qry_stride, uint32_t n_qry, uint32_t hash_bytes,
-                               uint32_t sketch_size, Counts cnt, hipStream_t st,
-                               bool *lds = nullptr);
-// (*lds: whether the LDS-staged walk was launched, else the walk from global memory)
+// (*lds, may be null: whether the LDS-staged walk was launched, else the walk from global memory)
+hipError_t launch_compare_grid(const RowSet &ref, const RowSet &qry, uint32_t hash_bytes,
+                               uint32_t sketch_size, Counts cnt, bool *lds, hipStream_t st);
 
 // dense walk of u32 lists on 16-bit rank images (dist.hip), for 64 <= min(S, stride) <= 1023;
 // scratch from compare_grid_img_scratch
@@ -150,11 +181,8 @@ bool compare_grid_img_ok(uint32_t hash_bytes, uint32_t sketch_size, uint64_t ref
                          uint64_t qry_stride);
 void compare_grid_img_scratch(uint32_t n_qry, uint32_t sketch_size, uint64_t ref_stride,
                               uint64_t qry_stride, size_t *ublk_bytes, size_t *bimg_bytes);
-hipError_t launch_compare_grid_img(const void *d_ref, const uint32_t *d_ref_len,
-                                   uint64_t ref_stride, uint32_t n_ref, const void *d_qry,
-                                   const uint32_t *d_qry_len, uint64_t qry_stride, uint32_t n_qry,
-                                   uint32_t sketch_size, void *ublk, void *bimg, Counts cnt,
-                                   hipStream_t st);
+hipError_t launch_compare_grid_img(const RowSet &ref, const RowSet &qry, uint32_t sketch_size,
+                                   void *ublk, void *bimg, Counts cnt, hipStream_t st);
 // the record rows of one side of a candidate walk (launch_record_rows): values, positions,
 // counts, row stride; val == nullptr: none (the walk starts at (0, 0))
 struct RecRows {
@@ -164,10 +192,7 @@ struct RecRows {
 };
 // the literal walk of each candidate pair; with record rows of both sides (unsorted lists),
 // only the stretches where both running maxima equal a shared record are walked
-hipError_t launch_walk_candidates(const uint64_t *d_cand, const unsigned long long *d_n_cand,
-                                  uint64_t cap, const void *d_ref, const uint32_t *d_ref_len,
-                                  uint64_t ref_stride, uint32_t n_ref, const void *d_qry,
-                                  const uint32_t *d_qry_len, uint64_t qry_stride,
+hipError_t launch_walk_candidates(const CandList &cl, const RowSet &ref, const RowSet &qry,
                                   uint32_t hash_bytes, uint32_t S, Counts cnt, RecRows rec_ref,
                                   RecRows rec_qry, hipStream_t st);
 
@@ -200,22 +225,30 @@ struct IdxGeom {
 };
 // entries of the level-1 staging buffer `tent` the build needs
 uint64_t idx_tent_words(const IdxGeom &g, uint64_t E);
-hipError_t launch_idx_build(const void *d_ref, const uint32_t *d_ref_len, uint64_t stride,
-                            uint32_t n_ref, uint32_t hash_bytes, IdxGeom g, uint32_t *tile_hist,
-                            uint32_t *tile_off, uint32_t *scan_s, uint64_t *tent,
-                            uint32_t *dir, uint32_t *entries, uint32_t *unsorted,
-                            unsigned long long *self_events, unsigned long long *zero,
-                            uint32_t nzero, unsigned long long *acc, uint32_t *part_fill,
-                            uint32_t *overflow, hipStream_t st,
-                            unsigned long long *zero_x = nullptr,
-                            unsigned long long *n_entries = nullptr);
-// zero[0..nzero) (and *zero_x when given) is cleared first; acc[0..2]: three words that start at
-// zero and are left at zero.
-// n_entries (may be null, may lie inside zero[]): [0] = the entries indexed (fewer than the
-// rows hold with g.vcut), [1] = the entries the rows hold (sum of the lengths)
-// One-pass build (g.cap != 0): part_fill holds 2^kIdxL1 u32 (cleared by the build), *overflow
-// (inside zero[]) is set when a partition exceeded cap: the index is then unusable and the
-// caller rebuilds with g.cap = 0
+struct IdxBuild {
+    RowSet rows;                  // the rows indexed
+    uint32_t hash_bytes = 8;
+    IdxGeom g{};
+    // scratch: 2^kIdxL1 x g.ntiles u32, one more, scan_scratch_words of that, idx_tent_words u64
+    uint32_t *tile_hist = nullptr, *tile_off = nullptr, *scan_s = nullptr;
+    uint64_t *tent = nullptr;
+    // the index: 2^g.nbits + 1 directory words and one u32 entry per cell of the rows
+    uint32_t *dir = nullptr, *entries = nullptr;
+    uint32_t *unsorted = nullptr;               // set to 1 when some row is not strictly increasing
+    unsigned long long *self_events = nullptr;  // null, or += sum_b |b|^2 over the buckets
+    // zero[0..nzero) (and *zero_x when given) is cleared first
+    unsigned long long *zero = nullptr, *zero_x = nullptr;
+    uint32_t nzero = 0;
+    unsigned long long *acc = nullptr;   // acc[0..2]: three words that start and are left at zero
+    // One-pass build (g.cap != 0): part_fill holds 2^kIdxL1 u32 (cleared by the build), *overflow
+    // (inside zero[]) is set when a partition exceeded cap: the index is then unusable and the
+    // caller rebuilds with g.cap = 0
+    uint32_t *part_fill = nullptr, *overflow = nullptr;
+    // may be null, may lie inside zero[]: [0] = the entries indexed (fewer than the rows hold
+    // with g.vcut), [1] = the entries the rows hold (sum of the lengths)
+    unsigned long long *n_entries = nullptr;
+};
+hipError_t launch_idx_build(const IdxBuild &a, hipStream_t st);
 
 // launch_exscan's shapes: blocks of kScanBlock elements; up to kScanFoldBlocks of them the block
 // totals are folded inside the add kernel (two launches), past that a single workgroup scans
@@ -233,37 +266,33 @@ hipError_t launch_publish(const unsigned long long *d_src, uint32_t n, unsigned 
 // unsorted lists: only pairs sharing a record value can count anything in the literal walk
 // (pos_out, may be null: each record's position in its row, at the same offsets; unsorted,
 // may be null: set to 1 when some row is not strictly increasing, the index build's test)
-hipError_t launch_record_rows(const void *in, const uint32_t *in_len, uint64_t in_stride,
-                              uint32_t n, uint32_t hash_bytes, uint32_t S, void *out,
+hipError_t launch_record_rows(const RowSet &in, uint32_t hash_bytes, uint32_t S, void *out,
                               uint32_t *pos_out, uint32_t *out_len, uint64_t out_stride,
-                              hipStream_t st, uint32_t *unsorted = nullptr);
+                              uint32_t *unsorted, hipStream_t st);
 hipError_t launch_exscan(const uint32_t *in, uint32_t *out, uint32_t *out2, uint64_t n,
                          uint32_t *scratch, uint32_t *total, hipStream_t st);
-hipError_t launch_probe_count(const void *d_qry, const uint32_t *d_qry_len, uint64_t stride,
-                              uint32_t n_qry, uint32_t hash_bytes, IdxGeom g, const uint32_t *dir,
-                              unsigned long long *events, uint32_t *unsorted, hipStream_t st);
+hipError_t launch_probe_count(const RowSet &qry, uint32_t hash_bytes, IdxGeom g,
+                              const uint32_t *dir, unsigned long long *events, uint32_t *unsorted,
+                              hipStream_t st);
 // The final values of a pair that shares no hash: (0, min(S, la+lb)), distance 1 (0 when
 // both lists are empty, numer == denom), p-value 1 and the -d / -v filters
 // (CommandDistance.cpp:404-419 at numer = 0).  launch_dist_fill writes them to every cell
 // of the grid; the candidate cells are then rewritten by the candidate compare and
 // launch_dist_cand_finalize.
 struct PairFill {
-    double *dist = nullptr, *pval = nullptr;
-    uint8_t *pass = nullptr;
+    CellOut out;
     double max_dist = -1, max_pvalue = -1;
 };
 // flat: the fill over the flattened grid (line-aligned wave stores, ~6.5 TB/s alone), else
 // row-aligned workgroups (~4.8 TB/s alone, gentler on a latency-bound kernel beside it).
-// fill.dist == nullptr: the numer / denom defaults only (the compact output)
-hipError_t launch_dist_fill(const uint32_t *d_ref_len, uint32_t n_ref, const uint32_t *d_qry_len,
-                            uint32_t n_qry, uint32_t S, Counts cnt, const PairFill &fill,
-                            hipStream_t st, bool flat = true);
+// fill.out.dist == nullptr: the numer / denom defaults only (the compact output)
+hipError_t launch_dist_fill(const RowSet &ref, const RowSet &qry, uint32_t S, Counts cnt,
+                            const PairFill &fill, bool flat, hipStream_t st);
 // A compact grid's counts written ahead of its dist call (fpm_dist_list_prefill): (0, S) in
 // every cell; then, once the lists are known, denom = la + lb where la + lb < S
 hipError_t launch_dist_counts_const(uint16_t *numer, uint16_t *denom, uint64_t cells, uint32_t S,
                                     hipStream_t st);
-hipError_t launch_dist_counts_fixup(const uint32_t *d_ref_len, uint32_t n_ref,
-                                    const uint32_t *d_qry_len, uint32_t n_qry, uint32_t S,
+hipError_t launch_dist_counts_fixup(const RowSet &ref, const RowSet &qry, uint32_t S,
                                     uint16_t *denom, hipStream_t st);
 // The compacted candidate rows of one sorted u64 set against itself: the half probe
 // writes them, the rank kernel streams them in place of the ref rows.  Row r's block of
@@ -279,42 +308,50 @@ struct CmpRows {
 constexpr uint64_t cmp_row_bytes(uint64_t stride) { return stride * 8 + (stride + 127) / 128 * 256; }
 constexpr uint32_t kCmpMaxRow = 2048;   // the longest row the probe's kept bits cover
 
-// `defaults`: also write (0, min(S, la+lb)) to every numer / denom cell of the row (off
-// when launch_dist_fill already did)
-hipError_t launch_probe_rows(const void *d_qry, const uint32_t *d_qry_len, uint64_t stride,
-                             uint32_t n_qry, uint32_t n_ref, uint32_t hash_bytes, IdxGeom g,
-                             const uint32_t *dir, const uint32_t *entries,
-                             const uint32_t *d_ref_len, uint32_t S, bool sym, bool defaults,
-                             bool self_set, Counts cnt, uint64_t *cand,
-                             unsigned long long *n_cand, uint64_t *row_seg,
-                             const uint32_t *d_qry_it_len, uint32_t *q_unsorted,
-                             unsigned long long *events, uint64_t cap, uint32_t *cand_over,
-                             hipStream_t st, uint32_t q_lo = 0, bool half = false,
-                             CmpRows cmp = CmpRows{});
-// (cmp.rows non-null: the half probe also writes each row's compacted copy.  Needs the half
-// form, u64 rows of stride <= kCmpMaxRow and every ref in one workgroup (n_ref <= 2^19):
-// hipErrorInvalidValue otherwise)
-// (half: the symmetric probe of one sorted set against itself over an index cut at this S
-// (g.cut == S): each row probes only its visited prefix and a pair is taken by its parity
-// owner when that row sees it, else by the other row; dist_index.hip step 2.  Needs sym and
-// self_set, and none of d_qry_it_len / q_unsorted / events: hipErrorInvalidValue otherwise)
-// (q_lo, n_qry: the query rows [q_lo, q_lo + n_qry) of the grid)
-// (d_qry_it_len non-null: the probed query rows are launch_record_rows copies of length
-// d_qry_it_len[q]; d_qry_len stays the original list lengths for the default cells)
-// (self_set: the query set is the indexed ref set, same buffers: buckets of one entry are
-// the row's own hash and are not read)
+struct ProbeRows {
+    // the query rows [q_lo, q_lo + qry.n) of the grid; qry.len stays the original list lengths
+    // (the default cells) when the probed rows are record copies
+    RowSet qry;
+    uint32_t q_lo = 0;
+    RowSet ref;                   // the indexed set: its lengths and n (the rows are not read)
+    uint32_t hash_bytes = 8, S = 0;
+    IdxGeom g{};
+    const uint32_t *dir = nullptr, *entries = nullptr;
+    bool sym = false;
+    // also write (0, min(S, la+lb)) to every numer / denom cell of the row (off when
+    // launch_dist_fill already did)
+    bool defaults = false;
+    // the query set is the indexed ref set, same buffers: buckets of one entry are the row's
+    // own hash and are not read
+    bool self_set = false;
+    // the symmetric probe of one sorted set against itself over an index cut at this S (g.cut
+    // == S): each row probes only its visited prefix and a pair is taken by its parity owner
+    // when that row sees it, else by the other row; dist_index.hip step 2.  Needs sym and
+    // self_set, and none of qry_it_len / q_unsorted / events: hipErrorInvalidValue otherwise
+    bool half = false;
+    Counts cnt;
+    CandList out;                 // cand, n and cap (the slots are the rank kernel's)
+    uint64_t *row_seg = nullptr;
+    // non-null: the probed query rows are launch_record_rows copies of length qry_it_len[q]
+    const uint32_t *qry_it_len = nullptr;
+    uint32_t *q_unsorted = nullptr;
+    unsigned long long *events = nullptr;
+    uint32_t *cand_over = nullptr;
+    // rows non-null: the half probe also writes each row's compacted copy.  Needs the half
+    // form, u64 rows of stride <= kCmpMaxRow and every ref in one workgroup (n_ref <= 2^19):
+    // hipErrorInvalidValue otherwise
+    CmpRows cmp;
+};
+hipError_t launch_probe_rows(const ProbeRows &a, hipStream_t st);
 // sorted-distinct candidates: one workgroup per query row, one wave per pair
-hipError_t launch_merge_rows(const uint64_t *d_cand, const uint64_t *row_seg, uint32_t n_qry,
-                             const uint64_t *d_ref, const uint32_t *d_ref_len, uint64_t ref_stride,
-                             uint32_t n_ref, const uint64_t *d_qry, const uint32_t *d_qry_len,
-                             uint64_t qry_stride, uint32_t S, bool sym, Counts cnt,
-                             uint32_t *d_cnum, uint32_t *d_cden, hipStream_t st, uint32_t q_lo = 0,
-                             uint32_t *rank_cap = nullptr, CmpRows cmp = CmpRows{});
-// (cmp.rows non-null: one set against itself (sym, d_ref == d_qry) whose probe wrote the
+// (cmp.rows non-null: one set against itself (sym, same ref and query rows) whose probe wrote the
 // compacted rows: the candidates are streamed from those, the diagonal answered in closed form)
-// (d_cnum, d_cden non-null: results go to candidate slot c instead of the grid cells;
-// q_lo, n_qry: the query rows [q_lo, q_lo + n_qry), whose probe has run;
-// *rank_cap: the CAP of the rank_rows_kernel instance launched, 1024 or 2048)
+// (cl.cnum, cl.cden non-null: results go to candidate slot c instead of the grid cells;
+// every query row's probe has run; *rank_cap, may be null: the CAP of the rank_rows_kernel
+// instance launched, 1024 or 2048)
+hipError_t launch_merge_rows(const CandList &cl, const uint64_t *row_seg, const RowSet &ref,
+                             const RowSet &qry, uint32_t S, bool sym, Counts cnt, CmpRows cmp,
+                             uint32_t *rank_cap, hipStream_t st);
 
 // -fp CFL text: newline index, then one lane per line (fingerprint.hip)
 uint32_t text_blocks(uint64_t len);
@@ -370,38 +407,28 @@ hipError_t launch_fq_emit(const uint8_t *d_text, uint64_t n_rec, uint64_t *d_rec
                           hipStream_t st);
 
 // triangle -fp positional compare (dist.hip)
-hipError_t launch_positional_grid(const void *d_ref, const uint32_t *d_ref_len,
-                                  uint64_t ref_stride, uint32_t n_ref, const void *d_qry,
-                                  const uint32_t *d_qry_len, uint64_t qry_stride, uint32_t n_qry,
-                                  uint32_t hash_bytes, double max_dist, double max_pvalue,
-                                  uint32_t *d_numer, uint32_t *d_denom, double *d_dist,
-                                  double *d_pvalue, uint8_t *d_pass, hipStream_t st);
+hipError_t launch_positional_grid(const RowSet &ref, const RowSet &qry, uint32_t hash_bytes,
+                                  double max_dist, double max_pvalue, uint32_t *d_numer,
+                                  uint32_t *d_denom, const CellOut &out, hipStream_t st);
 
 // contain (contain.hip): per pair the (common, steps) of containSketches
 // (CommandContain.cpp:368-412), query-major cells q * n_ref + r.
 // flag[0..1] (zeroed by the caller): flag[0] = 1 when some row of either set is not strictly
 // ascending within its length (plain stores), flag[1] = the longest query row (atomic max);
 // the caller reads them back (one stream synchronisation)
-hipError_t launch_rows_ascending(const void *d_ref, const uint32_t *d_ref_len, uint64_t ref_stride,
-                                 uint32_t n_ref, const void *d_qry, const uint32_t *d_qry_len,
-                                 uint64_t qry_stride, uint32_t n_qry, uint32_t hash_bytes,
+hipError_t launch_rows_ascending(const RowSet &ref, const RowSet &qry, uint32_t hash_bytes,
                                  uint32_t *flag, hipStream_t st);
 // the longest query row contain_rows_kernel stages in LDS on the current device (the dynamic
 // LDS limit is raised above 64 KB when the device grants it)
 uint32_t contain_lds_cap(uint32_t hash_bytes);
 // closed form, for strictly ascending rows only; max_qry_len = the longest query row, which
 // picks the LDS-staged or the global-memory instance (*lds)
-hipError_t launch_contain_rows(const void *d_ref, const uint32_t *d_ref_len, uint64_t ref_stride,
-                               uint32_t n_ref, const void *d_qry, const uint32_t *d_qry_len,
-                               uint64_t qry_stride, uint32_t n_qry, uint32_t hash_bytes,
+hipError_t launch_contain_rows(const RowSet &ref, const RowSet &qry, uint32_t hash_bytes,
                                uint32_t max_qry_len, uint32_t *d_common, uint32_t *d_steps,
-                               hipStream_t st, bool *lds);
+                               bool *lds, hipStream_t st);
 // the literal walk, one lane per pair: exact for any lists
-hipError_t launch_contain_literal(const void *d_ref, const uint32_t *d_ref_len,
-                                  uint64_t ref_stride, uint32_t n_ref, const void *d_qry,
-                                  const uint32_t *d_qry_len, uint64_t qry_stride, uint32_t n_qry,
-                                  uint32_t hash_bytes, uint32_t *d_common, uint32_t *d_steps,
-                                  hipStream_t st);
+hipError_t launch_contain_literal(const RowSet &ref, const RowSet &qry, uint32_t hash_bytes,
+                                  uint32_t *d_common, uint32_t *d_steps, hipStream_t st);
 
 // screen (screen.hip, screen_table.hpp; the pool pass in sketch.hip; the p-values in dist.hip)
 struct ScreenTable;
@@ -538,31 +565,21 @@ hipError_t launch_kf_text(const uint8_t *d_seq, const uint64_t *d_rec_pos,
 // sorted distinct lists (numer, denom) is symmetric, and so are distance and p-value.
 struct MirrorOut {
     Counts cnt;
-    double *dist = nullptr, *pval = nullptr;
-    uint8_t *pass = nullptr;
+    CellOut out;
     uint32_t n_qry = 0;
 };
 // distance / p-value / pass of the candidate cells only (after the candidate compare), and
 // of each mirror cell (r, q) when `sym`, or of its cell in the transposed grid `mir` (when
-// mir.dist is set); the other cells hold the probe's PairFill values
-hipError_t launch_dist_cand_finalize(const uint64_t *d_cand, const unsigned long long *d_n_cand,
-                                     uint64_t cap, bool sym, const uint32_t *d_cnum,
-                                     const uint32_t *d_cden, Counts cnt,
-                                     const uint64_t *d_ref_length,
-                                     const uint64_t *d_qry_length, uint32_t n_ref,
-                                     uint32_t kmer_size, double kmer_space, double max_dist,
-                                     double max_pvalue, double *d_dist, double *d_pvalue,
-                                     uint8_t *d_pass, const MirrorOut &mir, hipStream_t st);
+// mir.out.dist is set); the other cells hold the probe's PairFill values
+hipError_t launch_dist_cand_finalize(const CandList &cl, bool sym, Counts cnt, const RowSet &ref,
+                                     const RowSet &qry, const DistParams &par, const CellOut &out,
+                                     const MirrorOut &mir, hipStream_t st);
 // distance and p-value of n cells from their u16 / u32 counts and per-cell genome lengths
-hipError_t launch_pvalue_batch(const void *numer, const void *denom, uint32_t count_bytes,
-                               const uint64_t *len_ref, const uint64_t *len_qry, uint64_t n,
-                               uint32_t kmer_size, double kmer_space, double *dist,
-                               double *pvalue, hipStream_t st);
-hipError_t launch_dist_finalize(Counts cnt, const uint64_t *d_ref_length, const uint64_t *d_qry_length,
-                                uint32_t n_ref, uint32_t n_qry, uint32_t kmer_size,
-                                double kmer_space, double max_dist, double max_pvalue,
-                                double *d_dist, double *d_pvalue, uint8_t *d_pass,
-                                hipStream_t st);
+hipError_t launch_pvalue_batch(Counts cnt, const uint64_t *len_ref, const uint64_t *len_qry,
+                               uint64_t n, const DistParams &par, double *dist, double *pvalue,
+                               hipStream_t st);
+hipError_t launch_dist_finalize(Counts cnt, const RowSet &ref, const RowSet &qry,
+                                const DistParams &par, const CellOut &out, hipStream_t st);
 
 // The compact dist output's list of cells with numer > 0 (fpm_dist_list_dev): entry i =
 // (qry[i], ref[i]) with its distance / p-value / pass; *count (device) counts every entry,
@@ -575,18 +592,12 @@ struct CellList {
     uint64_t cap = 0;
 };
 // candidates: scatter (numer, denom) (mirror cell with `sym`; transposed grid mcnt with its own
-// list mlist) and list the cells with numer > 0; d_cnum == nullptr: counts read from the grid
-hipError_t launch_dist_cand_list(const uint64_t *d_cand, const unsigned long long *d_n_cand,
-                                 uint64_t cap, bool sym, const uint32_t *d_cnum,
-                                 const uint32_t *d_cden, Counts cnt, const uint64_t *d_ref_length,
-                                 const uint64_t *d_qry_length, uint32_t n_ref, uint32_t kmer_size,
-                                 double kmer_space, double max_dist, double max_pvalue,
-                                 const CellList &list, Counts mcnt, uint32_t m_nqry,
-                                 const CellList &mlist, hipStream_t st);
+// list mlist) and list the cells with numer > 0; cl.cnum == nullptr: counts read from the grid
+hipError_t launch_dist_cand_list(const CandList &cl, bool sym, Counts cnt, const RowSet &ref,
+                                 const RowSet &qry, const DistParams &par, const CellList &list,
+                                 Counts mcnt, const CellList &mlist, hipStream_t st);
 // every cell of a computed grid with numer > 0 into the list
-hipError_t launch_dist_grid_list(Counts cnt, uint32_t n_ref, uint32_t n_qry,
-                                 const uint64_t *d_ref_length, const uint64_t *d_qry_length,
-                                 uint32_t kmer_size, double kmer_space, double max_dist,
-                                 double max_pvalue, const CellList &list, hipStream_t st);
+hipError_t launch_dist_grid_list(Counts cnt, const RowSet &ref, const RowSet &qry,
+                                 const DistParams &par, const CellList &list, hipStream_t st);
 
 }  // namespace fpm

@@ -70,7 +70,7 @@ int screen_build(fpm_ctx *ctx, const void *d_db, const uint32_t *d_db_len, uint6
             HIP_TRY(scratch(ctx, kSlotCounters, kCtrWords * 8, &ctr));
             uint32_t *flag = (uint32_t *)((unsigned long long *)ctr + kCtrContain);
             HIP_TRY(hipMemsetAsync(flag, 0, 8, st));
-            HIP_TRY(launch_rows_ascending(d_db, d_db_len, stride, n_db, nullptr, nullptr, 0, 0,
+            HIP_TRY(launch_rows_ascending(RowSet{d_db, d_db_len, nullptr, stride, n_db}, RowSet{},
                                           hash_bytes, flag, st));
             uint32_t host[2] = {0, 0};
             HIP_TRY(hipMemcpyAsync(host, flag, 8, hipMemcpyDeviceToHost, st));

@@ -922,7 +922,7 @@ def test_sketch_merge_dev_matches_whole(ctx, oracle, s):
 
 
 @pytest.mark.parametrize("fillcnt", [False, True])
-@pytest.mark.parametrize("data", ["self", "other", "fp"])
+@pytest.mark.parametrize("data", ["self", "other", "fp", "apart8", "same8", "apart7", "same7"])
 @pytest.mark.parametrize("maxd,maxp", [(-1.0, -1.0), (0.5, 1.0), (1.0, 1e-10)])
 def test_dist_list_equals_dist16(ctx, oracle, data, maxd, maxp, fillcnt, dist_mode):
     """The compact output (fpm_dist_list_dev: u16 counts of every cell + the list of cells
@@ -930,9 +930,18 @@ def test_dist_list_equals_dist16(ctx, oracle, data, maxd, maxp, fillcnt, dist_mo
     five arrays fpm_dist_dev16 writes; counts and p-values also match the oracle.  Sorted
     sketches against themselves (the symmetric path) and against another set, unsorted -fp
     lists, empty lists, the -d / -v filters, every dist mode, and a context whose side fill
-    writes the counts (FPM_FILL_COUNTS=1, the large-grid default)."""
+    writes the counts (FPM_FILL_COUNTS=1, the large-grid default).
+
+    apart / same, 8 or 7 rows a side at S = 64: the shapes at which the sparse path's side fill
+    changes kernel (launch_dist_fill, launch_fill's rule).  8 refs (a multiple of 4) take the
+    4-cell stores, 7 the scalar kernel; `apart` (query values below every bucket the refs fill,
+    three shared values: a handful of posting events) keeps 1.6 x cells above the events, the
+    flattened fill, `same` (equal rows and an empty one: (n - 1)^2 x 64 events) below, the
+    row-aligned one.  The fill's count type is u32 (no counts written) without fillcnt, u16
+    with it.  These cases also hold the pass flags against the oracle's values."""
     import fpmash
     from fpmash import datagen
+    edge = data[:-1] in ("apart", "same")
     if fillcnt:
         os.environ["FPM_FILL_COUNTS"] = "1"
         try:
@@ -949,6 +958,23 @@ def test_dist_list_equals_dist16(ctx, oracle, data, maxd, maxp, fillcnt, dist_mo
         S, k, space, use64 = 300, 1, 10.0, False
         lens = np.array([len(x) * 3 + 7 for x in sk], np.uint64)
         qlens = lens[::-1][:50].copy()
+    elif edge:
+        rng = np.random.default_rng(53)
+        n = int(data[-1])
+        S, k, space, use64 = 64, 21, 4.0 ** 21, True
+        big = np.unique(rng.integers(2 ** 62, 2 ** 63, size=64 * n + 64, dtype=np.uint64))
+        if data.startswith("same"):
+            sk = [big[:64].copy() for _ in range(n - 1)] + [big[:0]]
+            qsk = [x.copy() for x in sk]
+        else:
+            sk = [big[64 * i:64 * i + 64] for i in range(n)]
+            small = np.unique(rng.integers(1, 2 ** 40, size=63 * n + 64, dtype=np.uint64))
+            qsk = [small[63 * i:63 * i + 63] for i in range(n)]
+            # the ref row's smallest value: the 64th of the union, so the walk counts it
+            for i in range(3):
+                qsk[i] = np.append(qsk[i], sk[i][0])
+        lens = rng.integers(10 ** 4, 10 ** 6, size=n).astype(np.uint64)
+        qlens = rng.integers(10 ** 4, 10 ** 6, size=n).astype(np.uint64)
     else:
         P = fpmash.make_params(k=21, s=500)
         seqs = datagen.family_dna(8, 12, 1500, sub_rate=(0.0, 0.08), seed=31)
@@ -971,6 +997,12 @@ def test_dist_list_equals_dist16(ctx, oracle, data, maxd, maxp, fillcnt, dist_mo
     assert np.allclose(comp["distance"], di, rtol=1e-12, atol=0)
     assert np.allclose(comp["pvalue"][dok], pv[dok], rtol=1e-12, atol=0)
     assert (comp["numer"] > 0).any() and (comp["numer"] == 0).any()
+    if edge:
+        pok = pv <= maxp if maxp >= 0 else np.ones(len(pv), bool)
+        assert np.array_equal(comp["pass"], dok & pok)
+        if dist_mode == "sparse":
+            ev = ctx.last_dist_stats()["events"]
+            assert (1.6 * len(sk) * len(qsk) > ev) == data.startswith("apart"), ev
     if fillcnt:
         ctx.close()
 

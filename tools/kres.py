@@ -22,11 +22,10 @@ for line in err.splitlines():
     elif cur is not None and ":" in t:
         k, v = t.split(":", 1)
         cur[k.strip()] = v.strip()
-filt = re.compile(sys.argv[2]) if False else None
 for r in rows:
     d = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip()
     d = re.sub(r"\(.*", "", d)
-    print(f"{d:70s} V{r.get('VGPRs','?'):>4} A{r.get('AGPRs','?'):>3} S{r.get('SGPRs','?'):>4} "
+    print(f"{d:70s} V{r.get('VGPRs','?'):>4} A{r.get('AGPRs','?'):>3} S{r.get('TotalSGPRs','?'):>4} "
           f"scr{r.get('ScratchSize [bytes/lane]','?'):>4} vsp{r.get('VGPRs Spill','?'):>3} "
           f"ssp{r.get('SGPRs Spill','?'):>3} occ{r.get('Occupancy [waves/SIMD]','?'):>3} "
           f"lds{r.get('LDS Size [bytes/block]','?'):>6}")

@@ -41,11 +41,11 @@ __global__ __launch_bounds__(256) void flat_fill(const uint32_t *__restrict__ re
         pv[u] = 1.0;
         pa |= 1u << (8 * u);
     }
-    *(double2 *)(fill.dist + o) = make_double2(dv[0], dv[1]);
-    *(double2 *)(fill.dist + o + 2) = make_double2(dv[2], dv[3]);
-    *(double2 *)(fill.pval + o) = make_double2(pv[0], pv[1]);
-    *(double2 *)(fill.pval + o + 2) = make_double2(pv[2], pv[3]);
-    *(uint32_t *)(fill.pass + o) = pa;
+    *(double2 *)(fill.out.dist + o) = make_double2(dv[0], dv[1]);
+    *(double2 *)(fill.out.dist + o + 2) = make_double2(dv[2], dv[3]);
+    *(double2 *)(fill.out.pval + o) = make_double2(pv[0], pv[1]);
+    *(double2 *)(fill.out.pval + o + 2) = make_double2(pv[2], pv[3]);
+    *(uint32_t *)(fill.out.pass + o) = pa;
 }
 
 int main(int argc, char **argv)
@@ -61,8 +61,9 @@ int main(int argc, char **argv)
     hipMalloc(&di, cells * 8);
     hipMalloc(&pv, cells * 8);
     hipMalloc(&pa, cells);
-    PairFill f;
-    f.dist = di; f.pval = pv; f.pass = pa; f.max_dist = 1.0; f.max_pvalue = 1.0;
+    const PairFill f{CellOut{di, pv, pa}, 1.0, 1.0};
+    // the lengths of one set as both sides of the grid; and a set without lengths
+    const RowSet rows{nullptr, d_len, nullptr, 0, n}, bare{nullptr, nullptr, nullptr, 0, n};
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
     auto run = [&](const char *name, auto launch) {
@@ -79,9 +80,9 @@ int main(int argc, char **argv)
         }
         printf("{\"variant\": \"%s\", \"ms\": %.4f, \"GBps\": %.1f}\n", name, best, 17.0 * cells / best / 1e6);
     };
-    run("dist_fill_kernel", [&] { launch_dist_fill(d_len, n, d_len, n, 1000, Counts{}, f, 0); });
+    run("dist_fill_kernel", [&] { launch_dist_fill(rows, rows, 1000, Counts{}, f, true, 0); });
     // no length loads (the prefill form: every list non-empty, constant cells)
-    run("dist_fill_kernel_no_lengths", [&] { launch_dist_fill(nullptr, n, nullptr, n, 1000, Counts{}, f, 0); });
+    run("dist_fill_kernel_no_lengths", [&] { launch_dist_fill(bare, bare, 1000, Counts{}, f, true, 0); });
     run("flat_fill", [&] { hipLaunchKernelGGL(flat_fill, dim3((uint32_t)((cells / 4 + 255) / 256)), dim3(256), 0, 0, d_len, n, d_len, cells, 1000, f); });
     run("bare_17B_stores", [&] { hipLaunchKernelGGL(bare17, dim3((uint32_t)((cells / 4 + 255) / 256)), dim3(256), 0, 0, di, pv, pa, cells); });
     return 0;
