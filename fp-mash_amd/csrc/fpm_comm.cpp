@@ -212,7 +212,7 @@ int fpm_sketch_min_merge_comm(fpm_comm *c, const uint64_t *d_row, const uint32_t
         // the previous gather into it may still be queued
         if (sl.p && sl.bytes < want && hipStreamSynchronize(st) != hipSuccess)
             return fail(FPM_EHIP, "min_merge_comm: buffer release");
-        const hipError_t e = grow_slot(sl, want, out);
+        const hipError_t e = grow_slot(c->ctx, sl, want, out);
         if (e == hipErrorOutOfMemory) return fail(FPM_ENOMEM, "min_merge_comm: hipMalloc");
         if (e != hipSuccess) return fail(FPM_EHIP, "min_merge_comm: buffer release");
         return FPM_OK;

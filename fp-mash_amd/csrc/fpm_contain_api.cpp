@@ -72,7 +72,7 @@ int fpm_contain(fpm_ctx *ctx, const void *ref, const uint32_t *ref_len, uint64_t
         return fail(FPM_EINVAL, "fpm_contain: null buffer");
     // one set against itself: one upload
     const bool same = ref == qry && ref_len == qry_len && ref_stride == qry_stride && n_ref == n_qry;
-    DevBufs mem;
+    DevBufs mem(ctx);
     void *r, *q = nullptr;
     uint32_t *rl, *ql = nullptr, *co, *stp;
     hipError_t e = mem.upload(ctx, &r, ref, (size_t)n_ref * ref_stride * hash_bytes);

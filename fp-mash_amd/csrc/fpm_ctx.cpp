@@ -209,7 +209,7 @@ hipError_t scratch(fpm_ctx *ctx, ScratchSlot id, size_t bytes, void **out)
 {
     auto &s = ctx->scratch[id];
     const bool grows = s.bytes < bytes;
-    hipError_t e = grow_slot(s, bytes, out);
+    hipError_t e = grow_slot(ctx, s, bytes, out);
     // small buffers (the counters) start zeroed: some words are kept at zero between
     // calls by the kernels themselves (idx_kmax_kernel's accumulator)
     if (e == hipSuccess && grows && s.bytes <= 4096) e = memset_sync(ctx, s.p, 0, s.bytes);
@@ -220,6 +220,37 @@ int set_device(fpm_ctx *ctx)
 {
     if (!ctx) return fail(FPM_EINVAL, "null context");
     HIP_TRY(hipSetDevice(ctx->device));
+    return FPM_OK;
+}
+
+// What the context remembers as addresses into its scratch slots, read into host fields: the
+// last sparse call's candidate count and the compacted rows' lengths (the fpm_ctx_last_*
+// queries read them lazily; fpm_ctx_poison_now reads them before it overwrites the slots).
+static int resolve_last_cand(fpm_ctx *ctx)
+{
+    if (ctx->last_cand != (uint64_t)-1) return FPM_OK;
+    if (int rc = set_device(ctx)) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->last_cand_stream));
+    unsigned long long v = 0;
+    HIP_TRY(hipMemcpy(&v, ctx->last_cand_dev, 8, hipMemcpyDeviceToHost));
+    ctx->last_cand = v;
+    return FPM_OK;
+}
+
+static int resolve_last_cmp_len(fpm_ctx *ctx)
+{
+    if (!ctx->last_rank_compact || !ctx->last_cmp_len) return FPM_OK;
+    // the probe's per-row lengths: read once, after the call's work
+    if (int rc = set_device(ctx)) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->last_cmp_stream));
+    std::vector<uint32_t> len(2 * (size_t)ctx->last_cmp_n);
+    HIP_TRY(hipMemcpy(len.data(), ctx->last_cmp_len, len.size() * 4, hipMemcpyDeviceToHost));
+    ctx->last_kept = ctx->last_cmp_entries = 0;
+    for (uint32_t r = 0; r < ctx->last_cmp_n; r++) {
+        ctx->last_kept += len[r];
+        ctx->last_cmp_entries += len[ctx->last_cmp_n + r];
+    }
+    ctx->last_cmp_len = nullptr;
     return FPM_OK;
 }
 
@@ -258,6 +289,10 @@ int fpm_ctx_create(int device, fpm_ctx **out)
     if (const char *v = getenv("FPM_PROBE_HALF")) ctx->probe_half = atoi(v) != 0;
     if (const char *v = getenv("FPM_INDEX_CUT")) ctx->index_cut = atoi(v) != 0;
     if (const char *v = getenv("FPM_RANK_COMPACT")) ctx->rank_compact = atoi(v) != 0;
+    if (const char *v = getenv("FPM_POISON")) {
+        const int b = atoi(v);
+        if (*v && b >= 0 && b <= 255) ctx->poison = b;
+    }
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
@@ -370,6 +405,11 @@ int fpm_malloc(fpm_ctx *ctx, void **dptr, size_t bytes)
     if (!dptr) return fail(FPM_EINVAL, "null dptr");
     hipError_t e = hipMalloc(dptr, bytes ? bytes : 1);
     if (e != hipSuccess) return fail(FPM_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    if ((e = poison_fill(ctx, *dptr, bytes ? bytes : 1)) != hipSuccess) {
+        (void)hipFree(*dptr);
+        *dptr = nullptr;
+        return fail(FPM_EHIP, std::string("fpm_malloc: poison fill: ") + hipGetErrorString(e));
+    }
     return FPM_OK;
 }
 
@@ -440,13 +480,7 @@ int fpm_ctx_last_dist_stats(fpm_ctx *ctx, int *sparse, uint64_t *events, uint64_
     if (!ctx) return fail(FPM_EINVAL, "null context");
     if (sparse) *sparse = ctx->last_sparse;
     if (events) *events = ctx->last_events;
-    if (ctx->last_cand == (uint64_t)-1) {
-        if (int rc = set_device(ctx)) return rc;
-        HIP_TRY(hipStreamSynchronize(ctx->last_cand_stream));
-        unsigned long long v = 0;
-        HIP_TRY(hipMemcpy(&v, ctx->last_cand_dev, 8, hipMemcpyDeviceToHost));
-        ctx->last_cand = v;
-    }
+    if (int rc = resolve_last_cand(ctx)) return rc;
     if (candidates) *candidates = ctx->last_cand;
     return FPM_OK;
 }
@@ -498,19 +532,7 @@ int fpm_ctx_set_rank_compact(fpm_ctx *ctx, int on)
 int fpm_ctx_last_rank_compact(fpm_ctx *ctx, int *compact, uint64_t *kept, uint64_t *entries)
 {
     if (!ctx) return fail(FPM_EINVAL, "null context");
-    if (ctx->last_rank_compact && ctx->last_cmp_len) {
-        // the probe's per-row lengths: read once, after the call's work
-        if (int rc = set_device(ctx)) return rc;
-        HIP_TRY(hipStreamSynchronize(ctx->last_cmp_stream));
-        std::vector<uint32_t> len(2 * (size_t)ctx->last_cmp_n);
-        HIP_TRY(hipMemcpy(len.data(), ctx->last_cmp_len, len.size() * 4, hipMemcpyDeviceToHost));
-        ctx->last_kept = ctx->last_cmp_entries = 0;
-        for (uint32_t r = 0; r < ctx->last_cmp_n; r++) {
-            ctx->last_kept += len[r];
-            ctx->last_cmp_entries += len[ctx->last_cmp_n + r];
-        }
-        ctx->last_cmp_len = nullptr;
-    }
+    if (int rc = resolve_last_cmp_len(ctx)) return rc;
     if (compact) *compact = ctx->last_rank_compact ? 1 : 0;
     if (kept) *kept = ctx->last_rank_compact ? ctx->last_kept : 0;
     if (entries) *entries = ctx->last_rank_compact ? ctx->last_cmp_entries : 0;
@@ -529,6 +551,46 @@ int fpm_ctx_spec_stats(fpm_ctx *ctx, uint64_t *hits, uint64_t *misses)
     if (!ctx || !hits || !misses) return fail(FPM_EINVAL, "null argument");
     *hits = ctx->spec_hits;
     *misses = ctx->spec_misses;
+    return FPM_OK;
+}
+
+int fpm_ctx_set_poison(fpm_ctx *ctx, int byte)
+{
+    if (!ctx || byte < -1 || byte > 255) return fail(FPM_EINVAL, "bad poison byte");
+    ctx->poison = byte;
+    return FPM_OK;
+}
+
+int fpm_ctx_poison_now(fpm_ctx *ctx)
+{
+    if (int rc = set_device(ctx)) return rc;
+    if (ctx->poison < 0) return fail(FPM_EINVAL, "poison_now: poison is off");
+    HIP_TRY(hipDeviceSynchronize());
+    // nothing the context remembers may point into what is overwritten below
+    if (int rc = resolve_last_cand(ctx)) return rc;
+    if (int rc = resolve_last_cmp_len(ctx)) return rc;
+    ctx->last_cmp_len = nullptr;
+    ctx->last_cand_dev = nullptr;
+    for (int id = 0; id < kSlotCount; id++) {
+        fpm_ctx::Slot &s = ctx->scratch[id];
+        if (!s.p) continue;
+        if (id != kSlotCounters) {
+            HIP_TRY(hipMemsetAsync(s.p, ctx->poison, s.bytes, ctx->stream));
+            continue;
+        }
+        // the counter block: all of it but idx_kmax_kernel's three accumulators, the words the
+        // kernels themselves keep at zero from one call to the next (CtrWord)
+        const size_t lo = (size_t)kCtrKmaxAcc * 8, hi = lo + 3 * 8;
+        HIP_TRY(hipMemsetAsync(s.p, ctx->poison, std::min(lo, s.bytes), ctx->stream));
+        if (s.bytes > hi)
+            HIP_TRY(hipMemsetAsync((char *)s.p + hi, ctx->poison, s.bytes - hi, ctx->stream));
+    }
+    {
+        std::lock_guard<std::mutex> g(ctx->pool_mu);
+        for (auto &b : ctx->pool)
+            HIP_TRY(hipMemsetAsync(b.first, ctx->poison, b.second, ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FPM_OK;
 }
 

@@ -193,8 +193,8 @@ static int refset_build_index(fpm_refset *rs, hipStream_t st)
     if (!rs->kmax) HIP_TRY(rs->mem.get(&rs->kmax, 8));
     auto build = [&](const RowSet &rows, IdxGeom &g, bool raw) -> int {
         void *dir, *entries;
-        HIP_TRY(grow_slot(rs->slot[fpm_refset::kDir], ((1ULL << g.nbits) + 1) * 4, &dir));
-        HIP_TRY(grow_slot(rs->slot[fpm_refset::kEntries], (uint64_t)R.n * rows.stride * 4, &entries));
+        HIP_TRY(grow_slot(rs->ctx, rs->slot[fpm_refset::kDir], ((1ULL << g.nbits) + 1) * 4, &dir));
+        HIP_TRY(grow_slot(rs->ctx, rs->slot[fpm_refset::kEntries], (uint64_t)R.n * rows.stride * 4, &entries));
         // the bucket pass also sums the self events (a query block that is the set itself
         // then needs no probe count)
         return build_index(ctx, rows, rs->hash_bytes, g, (uint32_t *)dir, (uint32_t *)entries,
@@ -209,9 +209,9 @@ static int refset_build_index(fpm_refset *rs, hipStream_t st)
     rs->recorded = rs->ref_unsorted;
     if (rs->recorded) {
         void *dref, *dref_len, *dref_pos;
-        HIP_TRY(grow_slot(rs->slot[fpm_refset::kRecRows], (size_t)R.n * rs->mr * rs->hash_bytes, &dref));
-        HIP_TRY(grow_slot(rs->slot[fpm_refset::kRecLen], (size_t)R.n * 4, &dref_len));
-        HIP_TRY(grow_slot(rs->slot[fpm_refset::kRecPos], (size_t)R.n * rs->mr * 4, &dref_pos));
+        HIP_TRY(grow_slot(rs->ctx, rs->slot[fpm_refset::kRecRows], (size_t)R.n * rs->mr * rs->hash_bytes, &dref));
+        HIP_TRY(grow_slot(rs->ctx, rs->slot[fpm_refset::kRecLen], (size_t)R.n * 4, &dref_len));
+        HIP_TRY(grow_slot(rs->ctx, rs->slot[fpm_refset::kRecPos], (size_t)R.n * rs->mr * 4, &dref_pos));
         {
             TimedLaunch tl(ctx, FPM_K_INDEX, st);
             HIP_TRY(launch_record_rows(R, rs->hash_bytes, rs->sketch_size, dref,
@@ -1018,7 +1018,7 @@ namespace {
 struct GridStage {
     fpm_ctx *ctx;
     hipError_t e = hipSuccess;
-    DevBufs mem;
+    DevBufs mem{ctx};
     void *r = nullptr, *q = nullptr;
     uint32_t *rl = nullptr, *ql = nullptr, *nu = nullptr, *de = nullptr;
     uint64_t *rL = nullptr, *qL = nullptr;
@@ -1097,11 +1097,11 @@ static int refset_stage_query(fpm_refset *rs, const RowSet &h, RowSet &d, int n_
     hipStream_t st = ctx->stream;
     void *q, *ql, *qL;
     const size_t qb = (size_t)h.n * h.stride * rs->hash_bytes;
-    HIP_TRY(grow_slot(rs->qslot[fpm_refset::kQRows], std::max<size_t>(16, qb), &q));
-    HIP_TRY(grow_slot(rs->qslot[fpm_refset::kQLen], (size_t)h.n * 4, &ql));
-    HIP_TRY(grow_slot(rs->qslot[fpm_refset::kQLength], (size_t)h.n * 8, &qL));
+    HIP_TRY(grow_slot(rs->ctx, rs->qslot[fpm_refset::kQRows], std::max<size_t>(16, qb), &q));
+    HIP_TRY(grow_slot(rs->ctx, rs->qslot[fpm_refset::kQLen], (size_t)h.n * 4, &ql));
+    HIP_TRY(grow_slot(rs->ctx, rs->qslot[fpm_refset::kQLength], (size_t)h.n * 8, &qL));
     for (int i = 0; i < n_out; i++)
-        HIP_TRY(grow_slot(rs->qslot[fpm_refset::kQNumer + i], out_bytes[i], &out[i]));
+        HIP_TRY(grow_slot(rs->ctx, rs->qslot[fpm_refset::kQNumer + i], out_bytes[i], &out[i]));
     HIP_TRY(hipStreamSynchronize(st));            // the query slots are free to overwrite
     HIP_TRY(copy_in(ctx, q, h.rows, qb));
     HIP_TRY(copy_in(ctx, ql, h.len, (size_t)h.n * 4));
@@ -1327,7 +1327,7 @@ int fpm_refset_create_dev(fpm_ctx *ctx, const void *d_ref, const uint32_t *d_ref
     if (int rc = set_device(ctx)) return rc;
     if (hash_bytes != 4 && hash_bytes != 8) return fail(FPM_EINVAL, "hash_bytes must be 4 or 8");
     std::unique_ptr<fpm_refset, void (*)(fpm_refset *)> rs(new fpm_refset, fpm_refset_free);
-    rs->ctx = ctx;
+    rs->ctx = rs->mem.ctx = ctx;
     rs->ref = RowSet{d_ref, d_ref_len, d_ref_length, ref_stride, n_ref};
     rs->hash_bytes = hash_bytes;
     rs->sketch_size = sketch_size;
@@ -1346,7 +1346,7 @@ int fpm_refset_create(fpm_ctx *ctx, const void *ref, const uint32_t *ref_len,
     if (int rc = set_device(ctx)) return rc;
     if (hash_bytes != 4 && hash_bytes != 8) return fail(FPM_EINVAL, "hash_bytes must be 4 or 8");
     // device copies of the rows, which the set then owns
-    DevBufs own;
+    DevBufs own(ctx);
     void *rows;
     uint32_t *len;
     uint64_t *length;
@@ -1499,8 +1499,8 @@ int fpm_refset_dist_list(fpm_refset *rs, const void *qry, const uint32_t *qry_le
         void *p[6];
         const size_t eb[6] = {4, 4, 8, 8, 1, 0};
         for (int i = 0; i < 5; i++)
-            HIP_TRY(grow_slot(rs->qslot[fpm_refset::kQList + i], want * eb[i], &p[i]));
-        HIP_TRY(grow_slot(rs->qslot[fpm_refset::kQList + 5], 8, &p[5]));
+            HIP_TRY(grow_slot(rs->ctx, rs->qslot[fpm_refset::kQList + i], want * eb[i], &p[i]));
+        HIP_TRY(grow_slot(rs->ctx, rs->qslot[fpm_refset::kQList + 5], 8, &p[5]));
         rs->list_cap = want;
         const fpm_cell_list L{(uint32_t *)p[0], (uint32_t *)p[1], (double *)p[2], (double *)p[3],
                               (uint8_t *)p[4], want, (uint64_t *)p[5]};

@@ -115,31 +115,78 @@ class CopyPool {
 // ask for the same candidates / row segments / results, and only one of the two runs, or the
 // second reuses what the first wrote; the query-side record rows are built by whichever index
 // source the call takes (resident-recorded or transient), never both.
+//
+// No slot is read before the call that claims it has written what it reads: a slot keeps the
+// last call's bytes (or, under fpm_ctx_set_poison, the poison byte), never a value a kernel may
+// rely on.  "init:" names who writes a slot first in a call; "in full" means every word a later
+// kernel reads was written by that call ("Who initialises device memory";
+// tests/test_gpu_poison.py runs every path over poisoned slots).
 enum ScratchSlot : int {
-    kSlotTileHist = 0,     // index build: level-1 histograms per tile
-    kSlotTileOff = 1,      // index build: their scan
-    kSlotTent = 2,         // index build: level-1 staging entries
-    kSlotCandRes = 3,      // rank kernel: per-candidate numer | denom (shared, see above)
-    kSlotDir = 4,          // bucket directory
-    kSlotEntries = 5,      // bucket entries
-    kSlotScan = 6,         // index build: scan scratch
-    kSlotCounters = 7,     // the counter block (CtrWord)
-    kSlotCand = 8,         // the probe's candidates (shared)
-    kSlotRowSeg = 9,       // their per-query-row segments (shared)
-    kSlotRecRef = 10,      // record rows of the references
-    kSlotRecRefLen = 11,   // their lengths
-    kSlotRecQry = 12,      // record rows of the queries (shared)
-    kSlotRecQryLen = 13,   // their lengths (shared)
-    kSlotImgBlocks = 14,   // dense image compare: union blocks
-    kSlotImg = 15,         // dense image compare: bit images
-    kSlotPartFill = 16,    // index build: one-pass partition fill counts
-    kSlotMergeRows = 16,   // fpm_sketch_merge_dev: intermediate lists (no index build beside it)
-    kSlotMergeCounts = 17, // fpm_sketch_merge_dev: their counts
-    kSlotMergeDescs = 18,  // fpm_sketch_merge_dev: merge descriptors
-    kSlotRecRefPos = 19,   // record positions of the references
-    kSlotRecQryPos = 20,   // record positions of the queries (shared)
-    kSlotCmpRows = 21,     // the compacted candidate rows: values and positions (shared)
-    kSlotCmpLen = 22,      // their lengths, and the rows' own (shared)
+    // index build: level-1 histograms per tile.  init: idx_part_hist_kernel, in full (every
+    // partition x tile); the one-pass build does not use it
+    kSlotTileHist = 0,
+    // index build: their scan.  init: launch_exscan, in full ([0, nh) and the total at nh)
+    kSlotTileOff = 1,
+    // index build: level-1 staging entries.  init: the scatter kernels; the bucket pass reads
+    // only [s0, s1) of each partition, the entries its fill / scan counted as written
+    kSlotTent = 2,
+    // rank kernel: per-candidate numer | denom (shared, see above).  init: rank_rows_kernel,
+    // one pair per candidate; the candidate finalize reads the first n_cand pairs.  A row the
+    // kernel leaves (unsorted, skip-count path) sends the call to the literal walk, which
+    // does not read the slot
+    kSlotCandRes = 3,
+    // bucket directory.  init: idx_bucket_kernel, in full (every sub-bucket and the end word)
+    kSlotDir = 4,
+    // bucket entries.  init: idx_bucket_kernel, [0, indexed entries); the directory bounds
+    // every read
+    kSlotEntries = 5,
+    // index build: scan scratch.  init: scan_local_kernel, every block sum before it is read
+    kSlotScan = 6,
+    // the counter block (CtrWord).  init: zeroed when the slot is made (scratch(): 4096 bytes or
+    // less); then [0, kCtrZeroWords) by idx_kmax_kernel's last workgroup, or [0, kCtrProbeWords)
+    // by a memset on the resident-set paths, before any kernel of the call adds to them;
+    // kCtrKmaxAcc .. +2 are left at zero by idx_kmax_kernel itself (the only words that live
+    // across calls); kCtrContain by a memset in contain / screen; kCtrCandOver is only written
+    kSlotCounters = 7,
+    // the probe's candidates (shared).  init: probe_rows_kernel, [0, n_cand); rows past the
+    // capacity (a speculated probe) write nothing and get an empty segment
+    kSlotCand = 8,
+    // their per-query-row segments (shared).  init: probe_rows_kernel, one word per query row
+    // (the rank kernel's path has one ref chunk: every row writes its own)
+    kSlotRowSeg = 9,
+    // record rows of the references.  init: record_rows_kernel, [0, length) of each row
+    kSlotRecRef = 10,
+    // their lengths.  init: record_rows_kernel, in full
+    kSlotRecRefLen = 11,
+    // record rows of the queries (shared).  init: record_rows_kernel, as the references'
+    kSlotRecQry = 12,
+    // their lengths (shared).  init: record_rows_kernel, in full
+    kSlotRecQryLen = 13,
+    // dense image compare: union blocks.  init: the image build kernel, what the compare reads
+    kSlotImgBlocks = 14,
+    // dense image compare: bit images.  init: the image build kernel, [0, min(len, W)) per row
+    kSlotImg = 15,
+    // index build: one-pass partition fill counts.  init: zeroed by idx_kmax_kernel's last
+    // workgroup (zero32) before the scatter adds to them; the two-pass build does not read it
+    kSlotPartFill = 16,
+    // fpm_sketch_merge_dev: intermediate lists (no index build beside it: calls on a context
+    // are stream-ordered, and each call writes the slot before it reads it).  init:
+    // merge kernel, [0, count) of each list before the next round reads it
+    kSlotMergeRows = 16,
+    // fpm_sketch_merge_dev: their counts.  init: merge kernel, one per intermediate list
+    kSlotMergeCounts = 17,
+    // fpm_sketch_merge_dev: merge descriptors.  init: copied from the host, in full
+    kSlotMergeDescs = 18,
+    // record positions of the references.  init: record_rows_kernel, [0, length) of each row
+    kSlotRecRefPos = 19,
+    // record positions of the queries (shared).  init: record_rows_kernel, as the references'
+    kSlotRecQryPos = 20,
+    // the compacted candidate rows: values and positions (shared).  init: probe_rows_kernel
+    // (CMP), [0, kept length) of each row; the rank kernel masks what lies past it
+    kSlotCmpRows = 21,
+    // their lengths, and the rows' own (shared).  init: probe_rows_kernel (CMP), 2 n words in
+    // full; fpm_ctx_last_rank_compact reads them once (fpm_ctx_poison_now reads them first)
+    kSlotCmpLen = 22,
     kSlotCount
 };
 
@@ -246,6 +293,9 @@ struct fpm_ctx {
     std::vector<std::pair<void *, size_t>> pool;
     size_t pool_bytes = 0;
     std::mutex pool_mu;
+    // fpm_ctx_set_poison (FPM_POISON=<0..255> starts it on): every buffer handed out is filled
+    // with this byte first; -1: off
+    int poison = -1;
 };
 
 // Event bracket: records start before and stop after a launch; done() hands the pair to the
@@ -288,6 +338,9 @@ inline hipStream_t pick_stream(fpm_ctx *ctx, void *stream)
 // device buffers of released jobs, reused by the next (fpm_ctx::pool; fpm_devmem.cpp)
 hipError_t pool_alloc(fpm_ctx *ctx, void **p, size_t bytes);
 void pool_free(fpm_ctx *ctx, void *p, size_t bytes);
+// the poison fill (fpm_ctx_set_poison) of a buffer about to be handed out, synchronous on the
+// context stream; nothing while poison is off or without a context
+hipError_t poison_fill(fpm_ctx *ctx, void *p, size_t bytes);
 
 // copies on the context stream, pageable caller memory through the pinned ring
 hipError_t ensure_ring(fpm_ctx *ctx);
@@ -298,8 +351,9 @@ hipError_t copy_out(fpm_ctx *ctx, void *dst, const void *src, size_t bytes);
 hipError_t copy_in(fpm_ctx *ctx, void *dst, const void *src, size_t bytes);
 hipError_t ensure_aux(fpm_ctx *ctx);
 
-// grow-only device buffers: a slot of at least `bytes`; scratch() is the context's named slot
-hipError_t grow_slot(fpm_ctx::Slot &s, size_t bytes, void **out);
+// grow-only device buffers: a slot of at least `bytes` (poisoned under `ctx`'s setting when it
+// grows); scratch() is the context's named slot
+hipError_t grow_slot(fpm_ctx *ctx, fpm_ctx::Slot &s, size_t bytes, void **out);
 hipError_t scratch(fpm_ctx *ctx, ScratchSlot id, size_t bytes, void **out);
 
 // The owner of device buffers: everything it still holds is freed with it, pooled buffers back
@@ -309,7 +363,7 @@ hipError_t scratch(fpm_ctx *ctx, ScratchSlot id, size_t bytes, void **out);
 class DevBufs {
   public:
     struct Buf { void *p; size_t bytes; bool pooled; };
-    fpm_ctx *ctx = nullptr;            // get_pooled's pool
+    fpm_ctx *ctx = nullptr;            // get_pooled's pool, and whose poison setting get follows
     DevBufs() = default;
     explicit DevBufs(fpm_ctx *c) : ctx(c) {}
     DevBufs(DevBufs &&o) noexcept : ctx(o.ctx), held_(std::move(o.held_)) { o.held_.clear(); }

@@ -44,7 +44,7 @@ int screen_build(fpm_ctx *ctx, const void *d_db, const uint32_t *d_db_len, uint6
         return fail(FPM_EINVAL, "fpm_screen_create: n_db * stride must be below 2^32");
     hipStream_t st = ctx->stream;
     fpm_screen *sc = new fpm_screen;
-    sc->ctx = ctx;
+    sc->ctx = sc->mem.ctx = ctx;
     sc->n_db = n_db;
     sc->s = sketch_size;
     sc->hash_bytes = hash_bytes;
@@ -86,7 +86,7 @@ int screen_build(fpm_ctx *ctx, const void *d_db, const uint32_t *d_db_len, uint6
         sc->E = (uint32_t)E;
         uint32_t nU = 0;
         unsigned long long kmax = 0;
-        DevBufs tmp;   // the build's scratch: freed on return
+        DevBufs tmp(ctx);   // the build's scratch: freed on return
         uint64_t *okey = nullptr;
         uint32_t *ocell = nullptr, *head = nullptr, *hx = nullptr, *scan_s = nullptr;
         if (E) {
@@ -95,7 +95,7 @@ int screen_build(fpm_ctx *ctx, const void *d_db, const uint32_t *d_db_len, uint6
             while (sbits < 22 && (2ull << sbits) < E) sbits++;
             sc->sbits = sbits;
             const uint64_t nb = 1ull << sbits;
-            DevBufs sort_tmp;   // the sort's own scratch: freed at the end of this block
+            DevBufs sort_tmp(ctx);   // the sort's own scratch: freed at the end of this block
             unsigned long long *km;
             uint32_t *hist, *start;
             uint64_t *skey;
@@ -187,7 +187,7 @@ int fpm_screen_create(fpm_ctx *ctx, const void *db, const uint32_t *db_len, uint
     if (int rc = set_device(ctx)) return rc;
     if (hash_bytes != 4 && hash_bytes != 8) return fail(FPM_EINVAL, "hash_bytes must be 4 or 8");
     if (n_db && (!db || !db_len)) return fail(FPM_EINVAL, "fpm_screen_create: null buffer");
-    DevBufs mem;
+    DevBufs mem(ctx);
     void *rows;
     uint32_t *len;
     hipError_t e = mem.get(&rows, (size_t)n_db * stride * hash_bytes);
@@ -288,7 +288,7 @@ int fpm_screen_rows_winner(fpm_screen *sc, const double *scores, const uint64_t 
     if (int rc = set_device(ctx)) return rc;
     HIP_TRY(hipDeviceSynchronize());
     if (!sc->n_db) return screen_rows(sc, nullptr, out_shared, out_median);
-    DevBufs mem;
+    DevBufs mem(ctx);
     double *ds;
     uint64_t *dl;
     hipError_t e = mem.get(&ds, (size_t)sc->n_db * 8);
@@ -311,7 +311,7 @@ int fpm_screen_pvalues(fpm_screen *sc, const uint32_t *shared, double kmer_space
     if (!sc->n_db) return FPM_OK;
     double r = (double)set_size / kmer_space;
     r = std::max(0.0, std::min(1.0, r));
-    DevBufs mem;
+    DevBufs mem(ctx);
     uint32_t *dsh;
     double *dp;
     hipError_t e = mem.get(&dsh, (size_t)sc->n_db * 4);
@@ -372,7 +372,7 @@ int fpm_screen_tax(fpm_screen *sc, const uint32_t *parent, uint32_t n_nodes, uin
     hipStream_t st = ctx->stream;
     const uint32_t nU = sc->tab.n;
     const size_t nb = (size_t)n_nodes * 4;
-    DevBufs mem;
+    DevBufs mem(ctx);
     uint32_t *dpar, *ddep, *dref, *dlca, *c0;
     unsigned long long *d_tot;
     hipError_t e = mem.upload(ctx, &dpar, parent, nb);

@@ -295,7 +295,7 @@ int stage_core(fpm_ctx *ctx, const fpm_sketch_params *p, StageRecords &R,
                      PlanParams{kp.k, kp.s, kp.use64 != 0}, &plan))
         return fail(FPM_EINVAL, "internal: tile exceeds capacity");
     auto *job = new fpm_sketch_job();
-    job->ctx = ctx;
+    job->ctx = job->mem.ctx = ctx;
     job->kp = kp;
     job->plan = std::move(plan);
     job->seq_bytes = R.host_seq ? packed.size() : R.d_seq_bytes;
@@ -765,7 +765,7 @@ int fpm_sketch_reads_run(fpm_sketch_job *job, void *stream)
     if (!ng) return FPM_OK;
     if (!job->d_rrows) {
         // all five or none: a later run must not find some of them missing
-        DevBufs out;
+        DevBufs out(ctx);
         hipError_t e = out.get(&job->d_rrows, ng * s * sizeof(uint64_t));
         if (e == hipSuccess) e = out.get(&job->d_rmult, ng * s * sizeof(uint32_t));
         if (e == hipSuccess) e = out.get(&job->d_rcount, ng * sizeof(uint32_t));

@@ -31,7 +31,7 @@ int fpm_fp_hash_lines(fpm_ctx *ctx, const uint64_t *vals, const uint64_t *line_o
     if (n_lines == 0) return FPM_OK;
     const uint64_t nv = line_off[n_lines];
     const size_t ob = (use64 ? 8 : 4) * n_lines;
-    DevBufs mem;
+    DevBufs mem(ctx);
     uint64_t *dv, *doff;
     void *dout;
     hipError_t e = mem.get(&dv, std::max<uint64_t>(nv, 1) * 8);
@@ -260,7 +260,7 @@ static int fastq_parse(fpm_ctx *ctx, fpm_seqtext *j, uint64_t text_bytes, hipStr
 {
     *ok = false;
     const uint32_t n_seg = (uint32_t)j->seg_off.size();
-    DevBufs tmp;   // the scratch, and until the end the record table and the packed records
+    DevBufs tmp(ctx);   // the scratch, and until the end the record table and the packed records
     const uint32_t nb = text_blocks(text_bytes);
     const uint64_t scan_w = scan_scratch_words(nb ? nb : 1);
     uint32_t *blk;
@@ -342,7 +342,7 @@ int fpm_seq_parse(fpm_ctx *ctx, const char *const *seg_text, const uint64_t *seg
     if (int rc = set_device(ctx)) return rc;
     std::unique_ptr<fpm_seqtext, void (*)(fpm_seqtext *)> j(new fpm_seqtext,
         [](fpm_seqtext *p) { seqtext_release(p); delete p; });
-    j->ctx = ctx;
+    j->ctx = j->mem.ctx = ctx;
     // each file from a chunk boundary, at least one '\n' after it
     uint64_t at = 0;
     for (uint32_t i = 0; i < n_seg; i++) {

@@ -110,6 +110,8 @@ SYMBOLS = [
     ("fpm_ctx_last_index_cut", C.c_int, [vp, C.POINTER(C.c_int), u64p, u64p]),
     ("fpm_ctx_set_rank_compact", C.c_int, [vp, C.c_int]),
     ("fpm_ctx_last_rank_compact", C.c_int, [vp, C.POINTER(C.c_int), u64p, u64p]),
+    ("fpm_ctx_set_poison", C.c_int, [vp, C.c_int]),
+    ("fpm_ctx_poison_now", C.c_int, [vp]),
     ("fpm_sketch_batch", C.c_int, [vp, vp, C.c_char_p, u64p, C.c_uint32, u32p, C.c_uint32,
                                    u64p, u32p]),
     ("fpm_sketch_stage", C.c_int, [vp, vp, C.c_char_p, u64p, C.c_uint32, u32p, C.c_uint32,
@@ -956,6 +958,16 @@ class Context:
         """fpm_ctx_set_rank_compact: the candidates of one sorted set against itself are ranked
         on rows without the probed hashes no other row holds (default on; same results)"""
         _check(lib().fpm_ctx_set_rank_compact(self.h, int(on)))
+
+    def set_poison(self, byte):
+        """fpm_ctx_set_poison: every device buffer the library hands out is first filled with
+        `byte` (0..255; -1 or None turns it off; a test hook)"""
+        _check(lib().fpm_ctx_set_poison(self.h, -1 if byte is None else int(byte)))
+
+    def poison_now(self):
+        """fpm_ctx_poison_now: fills the context's scratch slots and the free buffers of its
+        pool with the poison byte (synchronises; an error while poison is off; a test hook)"""
+        _check(lib().fpm_ctx_poison_now(self.h))
 
     def last_rank_compact(self):
         """fpm_ctx_last_rank_compact: {"compact": whether the last compare ranked compacted

@@ -98,6 +98,46 @@ int main()
         CHECK(ctx.pool.size() == 2 && ctx.pool[1].first == b && ctx.pool[1].second == 16);
         ctx.pool.clear();     // made-up addresses: nothing to free
     }
+    {   // poison on (fpm_ctx_set_poison): without a device the fill of a pooled buffer fails, so
+        // the buffer is not handed out and the pool keeps it at its own size
+        fpm_ctx ctx;
+        ctx.poison = 0xA5;
+        CHECK(poison_fill(nullptr, a, 64) == hipSuccess);     // no context: nothing to do
+        CHECK(poison_fill(&ctx, nullptr, 64) == hipSuccess);
+        CHECK(poison_fill(&ctx, a, 0) == hipSuccess);
+        CHECK(poison_fill(&ctx, a, 64) != hipSuccess);
+        ctx.pool.push_back({a, 8192});
+        ctx.pool.push_back({b, 4096});
+        ctx.pool_bytes = 8192 + 4096;
+        {
+            DevBufs m(&ctx);
+            uint8_t *p = reinterpret_cast<uint8_t *>(c);
+            CHECK(m.get_pooled(&p, 4000) != hipSuccess);      // picks b (the smallest that fits)
+            CHECK(p == nullptr && m.held().empty());
+            CHECK(ctx.pool.size() == 2 && ctx.pool_bytes == 8192 + 4096);
+            CHECK(ctx.pool[0].first == a && ctx.pool[0].second == 8192);
+            CHECK(ctx.pool[1].first == b && ctx.pool[1].second == 4096);
+            // past the pool and a plain get: hipMalloc fails before any fill
+            CHECK(m.get_pooled(&p, 1u << 20) != hipSuccess);
+            CHECK(m.get(&p, 64) != hipSuccess);
+            CHECK(p == nullptr && m.held().empty() && ctx.pool.size() == 2);
+        }
+        // a slot that cannot grow stays empty
+        fpm_ctx::Slot s;
+        void *out = c;
+        CHECK(grow_slot(&ctx, s, 64, &out) != hipSuccess);
+        CHECK(s.p == nullptr && s.bytes == 0);
+        // off again: the pool hands out as before
+        ctx.poison = -1;
+        {
+            DevBufs m(&ctx);
+            uint8_t *p = nullptr;
+            CHECK(m.get_pooled(&p, 4000) == hipSuccess);
+            CHECK(p == b && ctx.pool.size() == 1 && ctx.pool_bytes == 8192);
+            CHECK(m.release(p) == p);
+        }
+        ctx.pool.clear();
+    }
     puts("devmem ok");
     return 0;
 }

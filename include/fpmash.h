@@ -93,6 +93,26 @@ int fpm_memcpy_d2h(fpm_ctx *ctx, void *dst, const void *src, size_t bytes);
  * handed to a collective) */
 int fpm_memcpy_d2d(fpm_ctx *ctx, void *dst, const void *src, size_t bytes);
 int fpm_memset(fpm_ctx *ctx, void *dptr, int value, size_t bytes);
+/* Poisoned device memory (test hooks; off by default).  The library reads device memory from
+ * four places: its pool of released buffers, its grow-only scratch slots (the context's and a
+ * resident set's), plain allocations of its handles, and fpm_malloc.  A fresh allocation is
+ * usually zero and a reused one holds the last call's data, so a kernel that relies on a value
+ * nobody wrote can pass by luck.
+ * set_poison: byte 0..255 turns it on, -1 off (anything else is FPM_EINVAL); a context created
+ * with FPM_POISON=<0..255> in the environment starts with it on.  While on, every buffer from
+ * those four places is filled with the byte before it is handed out (a scratch slot when it
+ * grows), and the context stream is synchronised before the call returns.  Scratch slots of
+ * 4096 bytes or less are still zeroed after they grow: that is the counter block's contract.
+ * poison_now: synchronises the device, then fills the whole of every scratch slot of the
+ * context and every buffer lying free in its pool with the byte.  Only three words of the
+ * counter block are left as they are: the accumulators the index build keeps at zero from one
+ * call to the next.  Before it overwrites anything it reads what the fpm_ctx_last_dist_stats
+ * and fpm_ctx_last_rank_compact queries fetch lazily from scratch, so a later query returns
+ * the values of the last compare and reads no poisoned memory.  Buffers in use (handles,
+ * resident sets, caller memory, a pending fpm_dist_list_prefill) are not touched.  FPM_EINVAL
+ * while poison is off. */
+int fpm_ctx_set_poison(fpm_ctx *ctx, int byte);
+int fpm_ctx_poison_now(fpm_ctx *ctx);
 
 /* Per-kernel timing with HIP events recorded on the launch stream.
  * kernel ids: sketch tiles, sketch merge, fp hash, compare walk, finalize,

@@ -48,6 +48,17 @@ def test_scan_limits_need_no_device():
     fpmash.lib().fpm_scan_limits(None, None)       # NULL outputs are allowed
 
 
+def test_poison_hooks_exported_and_check_arguments():
+    import fpmash
+    L = fpmash.lib()
+    bound = {n for n, _, _ in fpmash.SYMBOLS}
+    assert {"fpm_ctx_set_poison", "fpm_ctx_poison_now"} <= bound
+    assert hasattr(fpmash.Context, "set_poison") and hasattr(fpmash.Context, "poison_now")
+    # no context: an error code, not a crash (no device needed)
+    assert L.fpm_ctx_set_poison(None, 0xA5) == fpmash.FPM_EINVAL
+    assert L.fpm_ctx_poison_now(None) == fpmash.FPM_EINVAL
+
+
 def test_library_is_gfx950_code_object():
     import subprocess
     import fpmash
