@@ -96,6 +96,8 @@ struct fpm_sketch_job {
     std::vector<uint32_t> h_rdone;          // per group: the round that completed it
     int32_t reads_rounds = -1;              // rounds of the last reads run (-1: none yet)
     int32_t reads_sampled = -1;             // long groups its last round's wide job sampled
+    fpm_sketch_plan reads_plan{};           // that wide job's plan and width (reads_width 0: no
+    uint32_t reads_width = 0;               // round yet), kept past the wide job's life
     DevBufs mem;                            // owns every d_* buffer above but a borrowed d_seq
 };
 
@@ -701,6 +703,9 @@ static int reads_round(fpm_sketch_job *job, fpm_sketch_job *wide, uint32_t round
 {
     fpm_ctx *ctx = job->ctx;
     const uint32_t m = job->min_copies, s = job->kp.s, S = wide->kp.s, ng = job->plan.n_groups;
+    // for fpm_sketch_job_reads_plan: the caller frees a staged wide job after the round
+    if (int rc = fpm_sketch_job_plan(wide, &job->reads_plan)) return rc;
+    job->reads_width = S;
     if (int rc = fpm_sketch_run(wide, st)) return rc;
     job->reads_sampled = (int32_t)wide->plan.n_slots;
     // per wide-row entry: a u32 count and min_copies u64 position slots, from the context's
@@ -877,6 +882,15 @@ int fpm_sketch_job_reads_sampled(fpm_sketch_job *job, int32_t *n_sampled)
 {
     if (!job || !n_sampled) return fail(FPM_EINVAL, "null argument");
     *n_sampled = job->reads_rounds < 0 ? -1 : job->reads_sampled;
+    return FPM_OK;
+}
+
+int fpm_sketch_job_reads_plan(fpm_sketch_job *job, fpm_sketch_plan *out, uint32_t *width)
+{
+    if (!job || !out || !width) return fail(FPM_EINVAL, "null argument");
+    if (!job->reads_width) return fail(FPM_EINVAL, "reads_plan before a reads_run round");
+    *out = job->reads_plan;
+    *width = job->reads_width;
     return FPM_OK;
 }
 

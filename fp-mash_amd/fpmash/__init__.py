@@ -131,6 +131,7 @@ SYMBOLS = [
     ("fpm_sketch_job_short_groups", C.c_int, [vp, C.POINTER(C.c_int32)]),
     ("fpm_sketch_job_sample_short", C.c_int, [vp, C.POINTER(C.c_int32)]),
     ("fpm_sketch_job_plan", C.c_int, [vp, vp]),
+    ("fpm_sketch_job_reads_plan", C.c_int, [vp, vp, u32p]),
     ("fpm_sketch_job_free", None, [vp]),
     ("fpm_fp_hash_lines", C.c_int, [vp, u64p, u64p, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
     ("fpm_fp_hash_lines_dev", C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp,
@@ -618,9 +619,21 @@ class SketchJob:
         rounds_small, sample_rounds, sample_rounds_small, merge_kernel (MK_*)"""
         p = SketchPlan()
         _check(lib().fpm_sketch_job_plan(self.h, C.byref(p)))
+        return self._plan_dict(p)
+
+    @staticmethod
+    def _plan_dict(p):
         out = {n: getattr(p, n) for n, _ in SketchPlan._fields_}
         out["tiles"], out["sample_tiles"] = list(p.tiles), list(p.sample_tiles)
         return out
+
+    def reads_plan(self):
+        """fpm_sketch_job_reads_plan: the plan (as plan()) of the wide job of the last round of
+        the last run_reads() and that round's width (a test hook) -> (dict, width); FPM_EINVAL
+        before any round"""
+        p, w = SketchPlan(), C.c_uint32()
+        _check(lib().fpm_sketch_job_reads_plan(self.h, C.byref(p), C.byref(w)))
+        return self._plan_dict(p), w.value
 
     def device_output(self):
         dh, dc = vp(), vp()
@@ -1005,7 +1018,8 @@ class Context:
         job.run_reads()
         rows, cnt, mult, est = job.fetch_reads()
         rounds, per = job.reads_rounds()
-        return {"hashes": [rows[i, : cnt[i]].copy() for i in range(len(cnt))],
+        plan, width = job.reads_plan() if rounds > 0 else (None, 0)      # no groups: no round
+        return {"plan": plan, "width": width, "hashes": [rows[i, : cnt[i]].copy() for i in range(len(cnt))],
                 "counts": [mult[i, : cnt[i]].copy() for i in range(len(cnt))],
                 "estimate": est.copy(), "rounds": rounds, "group_round": per,
                 "sampled": job.reads_sampled()}
@@ -1013,7 +1027,8 @@ class Context:
     def sketch_reads(self, params, seqs, groups=None, n_groups=None, min_copies=1):
         """Reads mode (sketch -r -m min_copies): per group the s smallest hashes seen at least
         min_copies times -> dict of hashes, counts (lists of arrays), estimate (u64 set-size
-        estimates), rounds and group_round (the widening rounds hook)."""
+        estimates), rounds and group_round (the widening rounds hook), plan and width (the
+        last round's wide job, SketchJob.reads_plan)."""
         job = SketchJob(self, params, seqs, groups, n_groups, min_copies)
         try:
             return self._reads_result(job)

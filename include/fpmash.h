@@ -334,6 +334,13 @@ typedef struct fpm_sketch_plan {
     uint32_t merge_kernel;    /* FPM_MK_*: the kernel of the rounds that are not small */
 } fpm_sketch_plan;
 int fpm_sketch_job_plan(fpm_sketch_job *job, fpm_sketch_plan *out);
+/* The same for reads mode, whose wide jobs are staged and freed inside fpm_sketch_reads_run: the
+ * plan of the wide job of the last round of the last reads_run (the job itself at min_copies 1,
+ * else a job over the groups still open in that round) and that round's width s' (a test hook
+ * like fpm_sketch_job_reads_sampled, which is this plan's n_slots).  Recorded when the round
+ * begins, so a round that fails with FPM_ENOMEM still reports its plan.  FPM_EINVAL before any
+ * round of a reads_run; it launches nothing. */
+int fpm_sketch_job_reads_plan(fpm_sketch_job *job, fpm_sketch_plan *out, uint32_t *width);
 void fpm_sketch_job_free(fpm_sketch_job *job);
 
 /* Bottom-s of the union of n_lists sketches (device rows of stride s, ascending and
