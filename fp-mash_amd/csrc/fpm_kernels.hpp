@@ -499,7 +499,8 @@ hipError_t launch_tax_clade(const TaxTree &t, const uint32_t *d_tax_hashes,
                             const uint32_t *d_tax_count, uint32_t *d_clade_hashes,
                             uint32_t *d_clade_count, hipStream_t st);
 
-// kfinger (kfinger.hip): CFL / ICFL / CFL_ICFL k-fingers of sequence records, one lane per line.  A workgroup
+// kfinger (kfinger.hip): CFL / ICFL / CFL_ICFL k-fingers of sequence records and their combined
+// (_COMB) forms, one lane per line.  A workgroup
 // takes one descriptor: kind 0, the window starts [start, start + count) of record rec (its
 // length >= the window); kind 1, the records rec .. rec + count - 1, each shorter than the window
 // (one line each) and together at most kKfStage bytes.  count <= kKfRun; the descriptor's lines
@@ -520,18 +521,58 @@ struct KfDesc {
 // `work`, u16 entries, work_groups regions of kf_wide_work_bytes(w), one per workgroup of a
 // grid that is no larger (the caller sizes it: kf_wide_groups).  A kind or threshold outside
 // these, or a wide window without `work`, is hipErrorInvalidValue from every launch below.
+// comb (fpm_kfinger_set_comb; lyn2vec's CFL_COMB / ICFL_COMB / CFL_ICFL_COMB-T,
+// factorizations_comb.py:178-246): the cuts of the window's factorization together with the
+// mirrored cuts of its reverse complement's, the reverse side of CFL_ICFL at threshold
+// kKfCombRevThreshold whatever `threshold` is (lyn2vec's d_duval_ calls it without one).  A
+// combined line keeps one more bit per window position, behind the ICFL memory: kf_bits_bytes
+// per workgroup.  Where that no longer fits the workgroup's 64 KB of LDS beside the kernels'
+// static kKfStaticLds, past kf_lds_window(kind, comb), the whole working memory is a region of
+// kf_region_bytes in `work` (CFL_COMB too, which has nothing but those bits).
 constexpr uint32_t kKfCfl = 0, kKfIcfl = 1, kKfCflIcfl = 2;
 constexpr uint32_t kKfLdsWindow = 192;    // entries < 256 fit u8 and the workgroup's LDS 64 KB
+constexpr uint32_t kKfCombRevThreshold = 30;   // cfl_icfl_'s default cfl_max
 struct KfFact {
     uint32_t kind = kKfCfl, threshold = 0;
     void *work = nullptr;
     uint32_t work_groups = 0;
+    uint32_t comb = 0;
 };
 constexpr uint32_t kf_lds_work_bytes(uint32_t w) { return kKfRun * ((w + 31) / 32 * 4 + w); }
 constexpr size_t kf_wide_work_bytes(uint32_t w)
 {
     return (size_t)kKfRun * ((w + 31) / 32 * 4 + (size_t)w * 2);
 }
+constexpr uint32_t kf_bits_bytes(uint32_t w) { return kKfRun * ((w + 31) / 32 * 4); }
+// the dynamic LDS of a workgroup, and its region of `work` in the wide modes (icfl: the kind is
+// ICFL or CFL_ICFL)
+constexpr uint32_t kf_lds_bytes(bool icfl, bool comb, uint32_t w)
+{
+    return (icfl ? kf_lds_work_bytes(w) : 0) + (comb ? kf_bits_bytes(w) : 0);
+}
+constexpr size_t kf_region_bytes(bool icfl, bool comb, uint32_t w)
+{
+    return (icfl ? kf_wide_work_bytes(w) : 0) + (comb ? kf_bits_bytes(w) : 0);
+}
+// what the kernels hold statically: the stage, the short-record offsets, the block sum
+constexpr uint32_t kKfStaticLds = (kKfStage + 3) / 4 * 4 + kKfRun * 4 + kKfRun / 64 * 8;
+constexpr uint32_t kKfGroupLds = 64 * 1024;
+// The widest window whose working memory stays in LDS.  Combined ICFL kinds: 256 x (w + 2 x 4 x
+// ceil(w / 32)) + 5,392 <= 65,536 holds up to w = 186 (65,296 B; 187 takes 65,552).  CFL_COMB:
+// 1,024 x ceil(w / 32) + 5,392 <= 65,536 holds up to 58 words, w = 1,856 (64,784 B).
+constexpr uint32_t kKfCombLdsWindow = 186, kKfCombCflLdsWindow = 1856;
+constexpr uint32_t kf_lds_window(uint32_t kind, uint32_t comb)
+{
+    return kind == kKfCfl ? (comb ? kKfCombCflLdsWindow : kKfMaxWindow)
+                          : (comb ? kKfCombLdsWindow : kKfLdsWindow);
+}
+static_assert(kf_lds_bytes(true, false, kKfLdsWindow) + kKfStaticLds <= kKfGroupLds, "ICFL LDS");
+static_assert(kf_lds_bytes(true, true, kKfCombLdsWindow) + kKfStaticLds <= kKfGroupLds &&
+              kf_lds_bytes(true, true, kKfCombLdsWindow + 1) + kKfStaticLds > kKfGroupLds,
+              "combined ICFL LDS");
+static_assert(kf_lds_bytes(false, true, kKfCombCflLdsWindow) + kKfStaticLds <= kKfGroupLds &&
+              kf_lds_bytes(false, true, kKfCombCflLdsWindow + 1) + kKfStaticLds > kKfGroupLds,
+              "combined CFL LDS");
 // workgroups of a wide-window grid: two per compute unit, no more than there are descriptors
 constexpr uint32_t kf_wide_groups(uint32_t n_desc, uint32_t n_cu)
 {

@@ -1,6 +1,6 @@
 // fpm_kfinger_api.cpp — the k-finger part of the C ABI declared in include/fpmash.h: CFL,
-// ICFL or CFL_ICFL k-fingers of sequence records (kfinger.hip), their line hashes, and the
-// lines as u16 values or as text.
+// ICFL or CFL_ICFL k-fingers of sequence records and their combined (_COMB) forms (kfinger.hip),
+// their line hashes, and the lines as u16 values or as text.
 #include "fpm_internal.hpp"
 
 #include <memory>
@@ -11,8 +11,9 @@ struct fpm_kfinger {
     uint64_t n_in = 0;                       // input records (taken or not)
     uint64_t n_lines = 0;
     bool ran = false;
-    KfFact fact;                             // CFL unless fpm_kfinger_set_factorization said else;
-                                             // its work: the wide windows' ICFL memory (pooled)
+    KfFact fact;                             // CFL unless fpm_kfinger_set_factorization said else,
+                                             // combined where fpm_kfinger_set_comb said so;
+                                             // its work: the wide windows' working memory (pooled)
     hipStream_t stream = nullptr;            // the last run's
     std::vector<uint64_t> rec_first_line;    // n_in + 1
     std::vector<uint32_t> src;               // input record of each kept record
@@ -123,17 +124,18 @@ int plan(fpm_kfinger *j, const std::vector<uint64_t> &pos, const std::vector<uin
 
 bool window_ok(uint32_t w) { return w >= 1 && w <= kKfMaxWindow; }
 
-// ICFL's working memory for windows past kKfLdsWindow: one region per workgroup of a grid of
-// two workgroups per compute unit, whatever the job's line count
+// The working memory for windows past kf_lds_window of the job's factorization: one region per
+// workgroup of a grid of two workgroups per compute unit, whatever the job's line count
 int wide_work(fpm_kfinger *j)
 {
-    if (j->fact.kind == kKfCfl || j->window <= kKfLdsWindow || j->fact.work || !j->n_desc)
+    if (j->window <= kf_lds_window(j->fact.kind, j->fact.comb) || j->fact.work || !j->n_desc)
         return FPM_OK;
     int n_cu = 0;
     HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, j->ctx->device));
     const uint32_t groups = kf_wide_groups(j->n_desc, (uint32_t)std::max(n_cu, 1));
     uint8_t *work = nullptr;
-    HIP_TRY(j->mem.get_pooled(&work, groups * kf_wide_work_bytes(j->window)));
+    HIP_TRY(j->mem.get_pooled(&work, groups * kf_region_bytes(j->fact.kind != kKfCfl,
+                                                               j->fact.comb != 0, j->window)));
     j->fact.work = work;
     j->fact.work_groups = groups;
     return FPM_OK;
@@ -212,6 +214,15 @@ int fpm_kfinger_set_factorization(fpm_kfinger *j, uint32_t kind, uint32_t thresh
         return fail(FPM_EINVAL, "kfinger_set_factorization: threshold out of range");
     j->fact.kind = kind;
     j->fact.threshold = kind == FPM_KF_CFL_ICFL ? threshold : 0;
+    return FPM_OK;
+}
+
+int fpm_kfinger_set_comb(fpm_kfinger *j, uint32_t on)
+{
+    if (!j) return fail(FPM_EINVAL, "kfinger_set_comb: null job");
+    if (j->ran) return fail(FPM_EINVAL, "kfinger_set_comb: the job has run");
+    if (on > 1) return fail(FPM_EINVAL, "kfinger_set_comb: on is 0 or 1");
+    j->fact.comb = on;
     return FPM_OK;
 }
 
@@ -392,6 +403,15 @@ void fpm_kfinger_limits(uint32_t *max_window, uint32_t *run_length)
 {
     if (max_window) *max_window = kKfMaxWindow;
     if (run_length) *run_length = kKfRun;
+}
+
+int fpm_kfinger_lds_window(uint32_t kind, uint32_t comb, uint32_t *window)
+{
+    if (!window) return fail(FPM_EINVAL, "kfinger_lds_window: null output");
+    if ((kind != FPM_KF_CFL && kind != FPM_KF_ICFL && kind != FPM_KF_CFL_ICFL) || comb > 1)
+        return fail(FPM_EINVAL, "kfinger_lds_window: unknown factorization");
+    *window = kf_lds_window(kind, comb);
+    return FPM_OK;
 }
 
 }  // extern "C"

@@ -22,6 +22,16 @@
 // is left are the factor boundaries, read left to right).  Windows up to kKfLdsWindow keep that
 // in LDS, u8 entries, lane-interleaved; wider ones in a device buffer of u16 entries, one region
 // per resident workgroup, which then walks the descriptors in a grid-stride loop.
+//
+// The combined forms (lyn2vec `--type_factorization CFL_COMB` / `ICFL_COMB` / `CFL_ICFL_COMB-T`;
+// factorizations_comb.py:178-246, d_duval_) cut a window of n bytes where its own factorization
+// does and where the factorization of its reverse complement does, mirrored: at n - c for a cut c
+// of the other strand.  The reverse complement is not staged: the routines take a byte view, and
+// the reverse view reads the lane's slice backwards (descending LDS addresses, the same
+// ds_read_u8) through the complement.  A lane factorizes the reverse side first, then the forward
+// one, marks the cuts of both in one more bit array (a cut both share is one bit), and reads it
+// left to right into the same emit callbacks.  The reverse side of CFL_ICFL_COMB-T runs at
+// threshold 30 whatever T is, as lyn2vec's does (d_duval_ calls it without k, :221, :164).
 #include "fpm_device.hpp"
 #include "fpm_kernels.hpp"
 
@@ -41,9 +51,26 @@ __device__ __forceinline__ uint8_t kf_upper(uint8_t c)
     return (c >= 'a' && c <= 'z') ? (uint8_t)(c - 32) : c;
 }
 
-// Duval (factorizations.py:102-126), bytes compared unsigned; emit(len) per Lyndon factor
-template <typename Emit>
-__device__ __forceinline__ void kf_duval(const uint8_t *s, uint32_t n, Emit emit)
+// the complement of an upper-cased byte (factorizations_comb.py:8-10): A <-> T, C <-> G; N and
+// every byte lyn2vec has no complement for stay as they are
+__device__ __forceinline__ uint8_t kf_comp(uint8_t c)
+{
+    const uint32_t at = (c == 'A') | (c == 'T'), cg = (c == 'C') | (c == 'G');
+    return (uint8_t)(c ^ (at ? ('A' ^ 'T') : 0) ^ (cg ? ('C' ^ 'G') : 0));
+}
+
+// The byte view of the reverse complement of a slice: byte i is the complement of the i-th byte
+// from the slice's end (p: its last byte).  The forward view of a slice is the pointer itself.
+struct KfRc {
+    const uint8_t *p;
+    __device__ __forceinline__ uint8_t operator[](uint32_t i) const { return kf_comp(*(p - i)); }
+    __device__ __forceinline__ KfRc operator+(uint32_t k) const { return KfRc{p - k}; }
+};
+
+// Duval (factorizations.py:102-126), bytes compared unsigned; emit(len) per Lyndon factor.
+// S: the byte view, const uint8_t * or KfRc.
+template <typename S, typename Emit>
+__device__ __forceinline__ void kf_duval(S s, uint32_t n, Emit emit)
 {
     uint32_t k = 0;
     while (k < n) {
@@ -96,16 +123,15 @@ struct KfWork {
 // start) lie below st, and st + j < n.
 // Backward: the piece of a step starts a new factor when the factor behind it is longer than
 // the step's `last`, else it is glued onto that factor.
-template <typename E, typename Emit>
-__device__ __forceinline__ void kf_icfl(const uint8_t *s, uint32_t n, const KfWork<E> &wk,
-                                        Emit emit)
+template <typename S, typename E, typename Emit>
+__device__ __forceinline__ void kf_icfl(S s, uint32_t n, const KfWork<E> &wk, Emit emit)
 {
     if (!n) return;
     const uint32_t nw = (n + 31) / 32;
     for (uint32_t i = 0; i < nw; i++) wk.word(i) = 0;
     uint32_t st = 0;
     for (;;) {
-        const uint8_t *w = s + st;
+        const S w = s + st;
         const uint32_t m = n - st;
         uint32_t i = 0, j = 1;
         while (j < m) {
@@ -163,17 +189,30 @@ __device__ __forceinline__ void kf_icfl(const uint8_t *s, uint32_t n, const KfWo
     emit(n - prev);
 }
 
-// how a kernel instance factorizes: Duval alone (the instances CFL has always had), or ICFL /
-// CFL_ICFL with the working memory in LDS, or in the device buffer
-enum : int { kKfModeCfl = 0, kKfModeLds = 1, kKfModeWide = 2 };
+// how a kernel instance factorizes: Duval alone (the instances CFL has always had; combined, with
+// its cut bits in LDS), or ICFL / CFL_ICFL with the working memory in LDS, or in the device
+// buffer; kKfModeCflWide is the combined Duval with its cut bits in the device buffer
+enum : int { kKfModeCfl = 0, kKfModeLds = 1, kKfModeWide = 2, kKfModeCflWide = 3 };
+
+constexpr bool kf_mode_icfl(int mode) { return mode == kKfModeLds || mode == kKfModeWide; }
+constexpr bool kf_mode_wide(int mode) { return mode == kKfModeWide || mode == kKfModeCflWide; }
 
 template <int MODE>
 using KfWorkOf = KfWork<typename std::conditional<MODE == kKfModeWide, uint16_t, uint8_t>::type>;
 
+// the workgroup's region of the device buffer (wide modes; else nullptr)
+template <int MODE, bool COMB>
+__device__ __forceinline__ uint8_t *kf_region(uint32_t w, uint8_t *work, uint32_t group)
+{
+    if constexpr (kf_mode_wide(MODE))
+        return work + (size_t)group * kf_region_bytes(kf_mode_icfl(MODE), COMB, w);
+    return nullptr;
+}
+
 // the lane's working memory.  LDS (dynamic, kf_lds_work_bytes(w)): the bit words of all lanes,
-// then the u8 entries.  Wide: the same with u16 entries, in region `group` of `work`.
+// then the u8 entries.  Wide: the same with u16 entries, at the head of the workgroup's region.
 template <int MODE>
-__device__ __forceinline__ KfWorkOf<MODE> kf_work(uint32_t w, uint8_t *work, uint32_t group)
+__device__ __forceinline__ KfWorkOf<MODE> kf_work(uint32_t w, uint8_t *region)
 {
     KfWorkOf<MODE> wk{nullptr, nullptr};
     const uint32_t nw = (w + 31) / 32;
@@ -182,20 +221,35 @@ __device__ __forceinline__ KfWorkOf<MODE> kf_work(uint32_t w, uint8_t *work, uin
         wk.bits = s_work + threadIdx.x;
         wk.a = reinterpret_cast<uint8_t *>(s_work + (size_t)nw * kKfRun) + threadIdx.x;
     } else if constexpr (MODE == kKfModeWide) {
-        uint8_t *base = work + (size_t)group * kf_wide_work_bytes(w);
-        wk.bits = reinterpret_cast<uint32_t *>(base) + threadIdx.x;
-        wk.a = reinterpret_cast<uint16_t *>(base + (size_t)nw * kKfRun * 4) + threadIdx.x;
+        wk.bits = reinterpret_cast<uint32_t *>(region) + threadIdx.x;
+        wk.a = reinterpret_cast<uint16_t *>(region + (size_t)nw * kKfRun * 4) + threadIdx.x;
     }
     return wk;
 }
 
+// the lane's cut bits of a combined factorization: (w + 31) / 32 words, kKfRun words apart like
+// the ICFL bits, behind the ICFL working memory where the mode has one
+template <int MODE, bool COMB>
+__device__ __forceinline__ uint32_t *kf_cut_bits(uint32_t w, uint8_t *region)
+{
+    if constexpr (!COMB) {
+        return nullptr;
+    } else if constexpr (kf_mode_wide(MODE)) {
+        return reinterpret_cast<uint32_t *>(region + kf_region_bytes(kf_mode_icfl(MODE), false, w)) +
+               threadIdx.x;
+    } else {
+        extern __shared__ uint32_t s_work[];
+        return s_work + kf_lds_bytes(kf_mode_icfl(MODE), false, w) / 4 + threadIdx.x;
+    }
+}
+
 // the factor lengths of s[0 .. n): thr 0, ICFL; else CFL_ICFL-thr, a Lyndon factor longer than
 // thr replaced by its own ICFL factors (CFL_icfl, factorizations.py:265-301)
-template <int MODE, typename Emit>
-__device__ __forceinline__ void kf_factorize(const uint8_t *s, uint32_t n, uint32_t thr,
+template <int MODE, typename S, typename Emit>
+__device__ __forceinline__ void kf_factorize(S s, uint32_t n, uint32_t thr,
                                              const KfWorkOf<MODE> &wk, Emit emit)
 {
-    if constexpr (MODE == kKfModeCfl) {
+    if constexpr (!kf_mode_icfl(MODE)) {
         kf_duval(s, n, emit);
     } else if (!thr) {
         kf_icfl(s, n, wk, emit);
@@ -206,6 +260,49 @@ __device__ __forceinline__ void kf_factorize(const uint8_t *s, uint32_t n, uint3
             else kf_icfl(s + at, len, wk, emit);
             at += len;
         });
+    }
+}
+
+// The lengths of a line, s[0 .. n): kf_factorize, or with COMB the gaps between the cuts of
+// d_duval_ (factorizations_comb.py:213-246): every cut c < n of the reverse complement's
+// factorization marked at n - c in `cuts`, every cut of the window's own marked where it is, and
+// the marks read left to right.  The lane clears its (n + 31) / 32 words first, every line.  The
+// reverse side's threshold is kKfCombRevThreshold where the forward one has any.
+template <int MODE, bool COMB, typename Emit>
+__device__ __forceinline__ void kf_line(const uint8_t *s, uint32_t n, uint32_t thr,
+                                        const KfWorkOf<MODE> &wk, uint32_t *cuts, Emit emit)
+{
+    if constexpr (!COMB) {
+        kf_factorize<MODE>(s, n, thr, wk, emit);
+    } else {
+        if (!n) return;
+        const uint32_t nw = (n + 31) / 32;
+        for (uint32_t i = 0; i < nw; i++) cuts[(size_t)i * kKfRun] = 0;
+        uint32_t at = 0;
+        kf_factorize<MODE>(KfRc{s + n - 1}, n, thr ? kKfCombRevThreshold : 0, wk,
+                           [&](uint32_t len) {
+                               at += len;
+                               if (at < n) {
+                                   const uint32_t p = n - at;
+                                   cuts[(size_t)(p >> 5) * kKfRun] |= 1u << (p & 31);
+                               }
+                           });
+        at = 0;
+        kf_factorize<MODE>(s, n, thr, wk, [&](uint32_t len) {
+            at += len;
+            if (at < n) cuts[(size_t)(at >> 5) * kKfRun] |= 1u << (at & 31);
+        });
+        uint32_t prev = 0;
+        for (uint32_t wd = 0; wd < nw; wd++) {
+            uint32_t v = cuts[(size_t)wd * kKfRun];
+            while (v) {
+                const uint32_t p = wd * 32 + (uint32_t)__ffs((int)v) - 1;
+                v &= v - 1;
+                emit(p - prev);
+                prev = p;
+            }
+        }
+        emit(n - prev);
     }
 }
 
@@ -275,13 +372,14 @@ __device__ __forceinline__ unsigned long long kf_block_sum(unsigned long long v,
 
 // Pass one.  hash: u32 or u64 per line; n_vals: factors per line; body: the text bytes of the
 // line after its ID (" <len>" per factor and the '\n'); *val_total += the factors of all lines.
-template <int MODE>
+template <int MODE, bool COMB>
 __device__ __forceinline__ void kf_hash_desc(
     const uint8_t *__restrict__ seq, const uint64_t *__restrict__ rec_pos,
     const uint32_t *__restrict__ rec_len, const KfDesc &d, uint32_t w, uint32_t seed,
     uint32_t use64, void *__restrict__ hash, uint32_t *__restrict__ n_vals,
     uint32_t *__restrict__ body, unsigned long long *__restrict__ val_total, uint32_t thr,
-    const KfWorkOf<MODE> &wk, uint8_t *s_seq, uint32_t *s_off, unsigned long long *s_red)
+    const KfWorkOf<MODE> &wk, uint32_t *cuts, uint8_t *s_seq, uint32_t *s_off,
+    unsigned long long *s_red)
 {
     uint32_t base, n, rec;
     const bool active = kf_stage(seq, rec_pos, rec_len, d, w, s_seq, s_off, base, n, rec);
@@ -291,7 +389,7 @@ __device__ __forceinline__ void kf_hash_desc(
         uint64_t h1 = seed, h2 = seed, pend = 0;
         // Murmur over the lengths as little-endian u64 (hash.cpp:45-73): a 16-byte block per two
         // values, an odd last value as the 8-byte tail, 8 * count folded in at the end
-        kf_factorize<MODE>(s_seq + base, n, thr, wk, [&](uint32_t len) {
+        kf_line<MODE, COMB>(s_seq + base, n, thr, wk, cuts, [&](uint32_t len) {
             bytes += 1 + kf_digits(len);
             if (cnt & 1) mur_block(h1, h2, pend, len);
             else pend = len;
@@ -314,9 +412,9 @@ __device__ __forceinline__ void kf_hash_desc(
     if (threadIdx.x == 0 && t) atomicAdd(val_total, t);
 }
 
-// One descriptor per workgroup; kKfModeWide: workgroup g owns region g of `work` and takes the
+// One descriptor per workgroup; the wide modes: workgroup g owns region g of `work` and takes the
 // descriptors g, g + gridDim.x, ...
-template <int MODE>
+template <int MODE, bool COMB>
 __global__ __launch_bounds__(kKfRun) void kf_hash_kernel(
     const uint8_t *__restrict__ seq, const uint64_t *__restrict__ rec_pos,
     const uint32_t *__restrict__ rec_len, const KfDesc *__restrict__ descs, uint32_t n_desc,
@@ -327,16 +425,18 @@ __global__ __launch_bounds__(kKfRun) void kf_hash_kernel(
     __shared__ uint8_t s_seq[kKfLds];
     __shared__ uint32_t s_off[kKfRun];
     __shared__ unsigned long long s_red[kKfRun / 64];
-    const KfWorkOf<MODE> wk = kf_work<MODE>(w, work, blockIdx.x);
-    if constexpr (MODE == kKfModeWide) {
+    uint8_t *region = kf_region<MODE, COMB>(w, work, blockIdx.x);
+    const KfWorkOf<MODE> wk = kf_work<MODE>(w, region);
+    uint32_t *cuts = kf_cut_bits<MODE, COMB>(w, region);
+    if constexpr (kf_mode_wide(MODE)) {
         // (kf_block_sum's barrier stands between one descriptor's reads of the stage and the
         // next one's writes)
         for (uint32_t b = blockIdx.x; b < n_desc; b += gridDim.x)
-            kf_hash_desc<MODE>(seq, rec_pos, rec_len, descs[b], w, seed, use64, hash, n_vals, body,
-                               val_total, thr, wk, s_seq, s_off, s_red);
+            kf_hash_desc<MODE, COMB>(seq, rec_pos, rec_len, descs[b], w, seed, use64, hash, n_vals,
+                                     body, val_total, thr, wk, cuts, s_seq, s_off, s_red);
     } else {
-        kf_hash_desc<MODE>(seq, rec_pos, rec_len, descs[blockIdx.x], w, seed, use64, hash, n_vals,
-                           body, val_total, thr, wk, s_seq, s_off, s_red);
+        kf_hash_desc<MODE, COMB>(seq, rec_pos, rec_len, descs[blockIdx.x], w, seed, use64, hash,
+                                 n_vals, body, val_total, thr, wk, cuts, s_seq, s_off, s_red);
     }
 }
 
@@ -362,14 +462,14 @@ __global__ __launch_bounds__(kKfRun) void kf_text_size_kernel(
 
 // Pass two.  TEXT: the line "<id> <len> <len> ...\n" at out + off[line], the ID copied from
 // ids[id_off[rec] .. + id_len[rec]); else the lengths as u16 at vals + off[line].
-template <bool TEXT, int MODE>
+template <bool TEXT, int MODE, bool COMB>
 __device__ __forceinline__ void kf_emit_desc(
     const uint8_t *__restrict__ seq, const uint64_t *__restrict__ rec_pos,
     const uint32_t *__restrict__ rec_len, const KfDesc &d, uint32_t w,
     const uint32_t *__restrict__ off, const uint8_t *__restrict__ ids,
     const uint64_t *__restrict__ id_off, const uint32_t *__restrict__ id_len,
     uint8_t *__restrict__ out, uint16_t *__restrict__ vals, uint32_t thr,
-    const KfWorkOf<MODE> &wk, uint8_t *s_seq, uint32_t *s_off)
+    const KfWorkOf<MODE> &wk, uint32_t *cuts, uint8_t *s_seq, uint32_t *s_off)
 {
     uint32_t base, n, rec;
     if (!kf_stage(seq, rec_pos, rec_len, d, w, s_seq, s_off, base, n, rec)) return;
@@ -380,7 +480,7 @@ __device__ __forceinline__ void kf_emit_desc(
         const uint32_t il = id_len[rec];
         for (uint32_t t = 0; t < il; t++) o[t] = id[t];
         o += il;
-        kf_factorize<MODE>(s_seq + base, n, thr, wk, [&](uint32_t len) {
+        kf_line<MODE, COMB>(s_seq + base, n, thr, wk, cuts, [&](uint32_t len) {
             const uint32_t nd = kf_digits(len);
             *o = ' ';
             uint32_t v = len;
@@ -393,11 +493,12 @@ __device__ __forceinline__ void kf_emit_desc(
         *o = '\n';
     } else {
         uint16_t *o = vals + off[line];
-        kf_factorize<MODE>(s_seq + base, n, thr, wk, [&](uint32_t len) { *o++ = (uint16_t)len; });
+        kf_line<MODE, COMB>(s_seq + base, n, thr, wk, cuts,
+                            [&](uint32_t len) { *o++ = (uint16_t)len; });
     }
 }
 
-template <bool TEXT, int MODE>
+template <bool TEXT, int MODE, bool COMB>
 __global__ __launch_bounds__(kKfRun) void kf_emit_kernel(
     const uint8_t *__restrict__ seq, const uint64_t *__restrict__ rec_pos,
     const uint32_t *__restrict__ rec_len, const KfDesc *__restrict__ descs, uint32_t n_desc,
@@ -408,16 +509,18 @@ __global__ __launch_bounds__(kKfRun) void kf_emit_kernel(
 {
     __shared__ uint8_t s_seq[kKfLds];
     __shared__ uint32_t s_off[kKfRun];
-    const KfWorkOf<MODE> wk = kf_work<MODE>(w, work, blockIdx.x);
-    if constexpr (MODE == kKfModeWide) {
+    uint8_t *region = kf_region<MODE, COMB>(w, work, blockIdx.x);
+    const KfWorkOf<MODE> wk = kf_work<MODE>(w, region);
+    uint32_t *cuts = kf_cut_bits<MODE, COMB>(w, region);
+    if constexpr (kf_mode_wide(MODE)) {
         for (uint32_t b = blockIdx.x; b < n_desc; b += gridDim.x) {
-            kf_emit_desc<TEXT, MODE>(seq, rec_pos, rec_len, descs[b], w, off, ids, id_off, id_len,
-                                     out, vals, thr, wk, s_seq, s_off);
+            kf_emit_desc<TEXT, MODE, COMB>(seq, rec_pos, rec_len, descs[b], w, off, ids, id_off,
+                                           id_len, out, vals, thr, wk, cuts, s_seq, s_off);
             __syncthreads();   // every lane is done with the stage before the next one fills it
         }
     } else {
-        kf_emit_desc<TEXT, MODE>(seq, rec_pos, rec_len, descs[blockIdx.x], w, off, ids, id_off,
-                                 id_len, out, vals, thr, wk, s_seq, s_off);
+        kf_emit_desc<TEXT, MODE, COMB>(seq, rec_pos, rec_len, descs[blockIdx.x], w, off, ids,
+                                       id_off, id_len, out, vals, thr, wk, cuts, s_seq, s_off);
     }
 }
 
@@ -429,29 +532,43 @@ namespace {
 // nothing).
 struct KfShape {
     int mode = kKfModeCfl;
+    bool comb = false;
     uint32_t grid = 0, lds = 0, thr = 0;
 };
 
 bool kf_shape(const KfFact &f, uint32_t w, uint32_t n_desc, KfShape &sh)
 {
     sh.grid = n_desc;
-    if (f.kind == kKfCfl) return true;
+    if (f.comb > 1) return false;
+    sh.comb = f.comb != 0;
     if (f.kind == kKfCflIcfl) {
         if (f.threshold < 1 || f.threshold > kKfMaxWindow) return false;
         sh.thr = f.threshold;
-    } else if (f.kind != kKfIcfl) {
+    } else if (f.kind != kKfIcfl && f.kind != kKfCfl) {
         return false;
     }
-    if (w <= kKfLdsWindow) {
-        sh.mode = kKfModeLds;
-        sh.lds = kf_lds_work_bytes(w);
+    const bool icfl = f.kind != kKfCfl;
+    if (w <= kf_lds_window(f.kind, f.comb)) {
+        sh.mode = icfl ? kKfModeLds : kKfModeCfl;
+        sh.lds = kf_lds_bytes(icfl, sh.comb, w);
         return true;
     }
     if (n_desc && (!f.work || !f.work_groups)) return false;
-    sh.mode = kKfModeWide;
+    sh.mode = icfl ? kKfModeWide : kKfModeCflWide;
     sh.grid = std::min(n_desc, f.work_groups);
     return true;
 }
+
+// the instance of a kernel template K<MODE, COMB> that sh names (kKfModeCflWide exists combined
+// only: plain Duval has no working memory)
+#define KF_PICK(K, ...)                                                                          \
+    (!sh.comb ? (sh.mode == kKfModeCfl   ? K<__VA_ARGS__ kKfModeCfl, false>                      \
+                 : sh.mode == kKfModeLds ? K<__VA_ARGS__ kKfModeLds, false>                      \
+                                         : K<__VA_ARGS__ kKfModeWide, false>)                    \
+              : (sh.mode == kKfModeCfl    ? K<__VA_ARGS__ kKfModeCfl, true>                      \
+                 : sh.mode == kKfModeLds  ? K<__VA_ARGS__ kKfModeLds, true>                      \
+                 : sh.mode == kKfModeWide ? K<__VA_ARGS__ kKfModeWide, true>                     \
+                                          : K<__VA_ARGS__ kKfModeCflWide, true>))
 
 }  // namespace
 
@@ -464,9 +581,7 @@ hipError_t launch_kf_hash(const uint8_t *d_seq, const uint64_t *d_rec_pos,
     KfShape sh;
     if (w < 1 || w > kKfMaxWindow || !kf_shape(f, w, n_desc, sh)) return hipErrorInvalidValue;
     if (!n_desc) return hipSuccess;
-    auto kernel = sh.mode == kKfModeCfl   ? kf_hash_kernel<kKfModeCfl>
-                  : sh.mode == kKfModeLds ? kf_hash_kernel<kKfModeLds>
-                                          : kf_hash_kernel<kKfModeWide>;
+    auto kernel = KF_PICK(kf_hash_kernel, );
     hipLaunchKernelGGL(kernel, dim3(sh.grid), dim3(kKfRun), sh.lds, st, d_seq, d_rec_pos, d_rec_len,
                        d_descs, n_desc, w, seed, use64, d_hash, d_n_vals, d_body, d_val_total,
                        sh.thr, (uint8_t *)f.work);
@@ -496,9 +611,7 @@ hipError_t kf_launch_emit(const uint8_t *d_seq, const uint64_t *d_rec_pos,
     KfShape sh;
     if (w < 1 || w > kKfMaxWindow || !kf_shape(f, w, n_desc, sh)) return hipErrorInvalidValue;
     if (!n_desc) return hipSuccess;
-    auto kernel = sh.mode == kKfModeCfl   ? kf_emit_kernel<TEXT, kKfModeCfl>
-                  : sh.mode == kKfModeLds ? kf_emit_kernel<TEXT, kKfModeLds>
-                                          : kf_emit_kernel<TEXT, kKfModeWide>;
+    auto kernel = KF_PICK(kf_emit_kernel, TEXT, );
     hipLaunchKernelGGL(kernel, dim3(sh.grid), dim3(kKfRun), sh.lds, st, d_seq, d_rec_pos, d_rec_len,
                        d_descs, n_desc, w, d_off, d_ids, d_id_off, d_id_len, d_out, d_vals, sh.thr,
                        (uint8_t *)f.work);

@@ -4,7 +4,8 @@ A ctypes mirror of the reference's engine calls for this path:
   Sketch sketching (addMinHashes/MinHashHeap, Sketch.cpp:664-735, 1490-1517) -> Context.sketch
   -fp line hashing (getHashFingerPrint, hash.cpp:45-73)                    -> Context.fp_hash_lines
   lyn2vec CFL k-fingers (fingerprint_utils.py:95-110, 443-476) + their hashes -> Context.kfinger
-    (factorization="ICFL" / "CFL_ICFL-<T>": factorizations.py:143-248, 265-301)
+    (factorization="ICFL" / "CFL_ICFL-<T>": factorizations.py:143-248, 265-301; "CFL_COMB" /
+    "ICFL_COMB" / "CFL_ICFL_COMB-<T>": factorizations_comb.py:178-246)
   compare/compareSketches/pValue (CommandDistance.cpp:335-450)             -> Context.dist
   contain/containSketches (CommandContain.cpp:314-412)                     -> Context.contain
   screen: hashSequence, sums, -w, pValueWithin (CommandScreen.cpp:133-406) -> Context.screen
@@ -147,6 +148,7 @@ SYMBOLS = [
     ("fpm_kfinger_stage_seq", C.c_int, [vp, vp, u8p, C.c_uint32, C.c_uint64, C.POINTER(vp),
                                         u64p]),
     ("fpm_kfinger_set_factorization", C.c_int, [vp, C.c_uint32, C.c_uint32]),
+    ("fpm_kfinger_set_comb", C.c_int, [vp, C.c_uint32]),
     ("fpm_kfinger_run", C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
     ("fpm_kfinger_fetch", C.c_int, [vp, u64p, vp, u32p]),
     ("fpm_kfinger_device_output", C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), u64p, u32p]),
@@ -155,6 +157,7 @@ SYMBOLS = [
     ("fpm_kfinger_free", None, [vp]),
     ("fpm_kfinger_limits", None, [u32p, u32p]),
     ("fpm_kfinger_wide_groups", C.c_int, [vp, u32p]),
+    ("fpm_kfinger_lds_window", C.c_int, [C.c_uint32, C.c_uint32, u32p]),
     ("fpm_compare_grid", C.c_int, [vp, vp, u32p, C.c_uint64, C.c_uint32, vp, u32p, C.c_uint64,
                                    C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p]),
     ("fpm_compare_grid_dev", C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64,
@@ -392,21 +395,38 @@ KF_CFL, KF_ICFL, KF_CFL_ICFL = 0, 1, 2   # FPM_KF_*
 def parse_factorization(name: str, max_threshold=None):
     """("CFL" | "ICFL" | "CFL_ICFL", T) of lyn2vec's --type_factorization spelling
     (lyn2vec.py:47-59): CFL, ICFL or CFL_ICFL-<T> with T >= 1 in plain decimal digits (and at
-    most max_threshold, when given); ValueError for anything else."""
-    if name in ("CFL", "ICFL"):
+    most max_threshold, when given); ("CFL_COMB" | "ICFL_COMB" | "CFL_ICFL_COMB", T) of the
+    combined forms CFL_COMB, ICFL_COMB and CFL_ICFL_COMB-<T> (lyn2vec.py:60-72) by the same
+    rules; ValueError for anything else."""
+    if name in ("CFL", "ICFL", "CFL_COMB", "ICFL_COMB"):
         return name, 0
     head, sep, t = name.partition("-")
-    if head == "CFL_ICFL" and sep and t.isascii() and t.isdigit() and len(t) <= 9 and int(t) >= 1:
+    if head in ("CFL_ICFL", "CFL_ICFL_COMB") and sep and t.isascii() and t.isdigit() and \
+            len(t) <= 9 and int(t) >= 1:
         if max_threshold is None or int(t) <= max_threshold:
             return head, int(t)
-    raise ValueError(f"unknown factorization {name!r}: CFL, ICFL or CFL_ICFL-<T>")
+    raise ValueError(f"unknown factorization {name!r}: CFL, ICFL, CFL_ICFL-<T>, CFL_COMB, "
+                     "ICFL_COMB or CFL_ICFL_COMB-<T>")
 
 
 def kfinger_factorization(name):
     """(FPM_KF_* kind, threshold) of lyn2vec's spelling "CFL", "ICFL" or "CFL_ICFL-<T>"
-    (lyn2vec.py:47-59), T from 1 to the widest window; ValueError for anything else."""
+    (lyn2vec.py:47-59), T from 1 to the widest window; (kind, threshold, 1) of the combined
+    "CFL_COMB", "ICFL_COMB" or "CFL_ICFL_COMB-<T>" (the 1: fpm_kfinger_set_comb); ValueError for
+    anything else."""
     kind, thr = parse_factorization(name, kfinger_limits()[0])
-    return {"CFL": KF_CFL, "ICFL": KF_ICFL, "CFL_ICFL": KF_CFL_ICFL}[kind], thr
+    comb = kind.endswith("_COMB")
+    k = {"CFL": KF_CFL, "ICFL": KF_ICFL, "CFL_ICFL": KF_CFL_ICFL}[kind[:-5] if comb else kind]
+    return (k, thr, 1) if comb else (k, thr)
+
+
+def kfinger_lds_window(name):
+    """the widest window whose working memory stays in LDS under the factorization of that
+    spelling (fpm_kfinger_lds_window; no device needed): the next one keeps it in device memory"""
+    kind, _thr, *comb = kfinger_factorization(name)
+    w = C.c_uint32()
+    _check(lib().fpm_kfinger_lds_window(kind, 1 if comb else 0, C.byref(w)))
+    return w.value
 
 
 def kfinger_id(header: bytes) -> bytes:
@@ -1452,12 +1472,14 @@ class Context:
     @staticmethod
     def _kfinger_out(job, n, n_rec, seed, use64, ids, values, text, fact=(KF_CFL, 0)):
         """run + fetch (+ the pass-two outputs) of a staged k-finger job under the factorization
-        fact = (FPM_KF_* kind, threshold); frees it"""
+        fact = (FPM_KF_* kind, threshold) or, combined, (kind, threshold, 1); frees it"""
         L = lib()
         try:
-            kind, thr = fact
+            kind, thr, *comb = fact
             if kind != KF_CFL:
                 _check(L.fpm_kfinger_set_factorization(job, kind, thr))
+            if comb and comb[0]:
+                _check(L.fpm_kfinger_set_comb(job, 1))
             _check(L.fpm_kfinger_run(job, seed, int(use64), None))
             first = np.zeros(n_rec + 1, np.uint64)
             h = np.zeros(max(n, 1), np.uint64 if use64 else np.uint32)
@@ -1493,7 +1515,8 @@ class Context:
                 values=False, text=False, factorization="CFL"):
         """k-fingers of the records `seqs` (lyn2vec --type basic --type_factorization CFL,
         fingerprint_utils.py:95-110, 443-476; factorization "ICFL" or "CFL_ICFL-<T>" for lyn2vec's
-        factorizations of those names, fpm_kfinger_set_factorization) and their line hashes
+        factorizations of those names, fpm_kfinger_set_factorization; "CFL_COMB", "ICFL_COMB" or
+        "CFL_ICFL_COMB-<T>" for the combined ones, fpm_kfinger_set_comb) and their line hashes
         (hash.cpp:45-73), on the device.  -> n_lines, rec_first_line (len(seqs) + 1), hash and n_vals per line; with
         values the factor lengths (vals u16, line l's at val_off[l] .. val_off[l + 1]); with
         text the lines' text, ids[r] being record r's full ID bytes (lyn2vec's "<id>_0").

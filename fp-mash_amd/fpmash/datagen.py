@@ -7,7 +7,8 @@
 - Family-structured variants (ancestor + members with a substitution rate) so
   that dist has non-trivial shared-hash counts (unrelated random genomes give
   common = 0 for nearly every pair).
-- CFL k-finger text (lyn2vec `--type basic --type_factorization CFL`,
+- CFL k-finger text (lyn2vec `--type basic --type_factorization CFL`; also ICFL, CFL_ICFL-T and
+  the combined CFL_COMB, ICFL_COMB, CFL_ICFL_COMB-T of factorizations_comb.py:178-246;
   fingerprint_utils.py:95-110, 443-476; factorizations.py:102-126): one line per
   100-char cyclic window, `<Gid>_0 l1 l2 ...` with the Lyndon factor lengths of
   Duval's algorithm.
@@ -158,16 +159,56 @@ def cfl_icfl_lengths(word: bytes, T: int, stats=None):
     return out
 
 
+COMB_REV_THRESHOLD = 30   # cfl_icfl_'s default cfl_max (factorizations_comb.py:164)
+_COMPLEMENT = bytes.maketrans(b"ACGT", b"TGCA")
+
+
+def reverse_complement(word: bytes):
+    """lyn2vec's reverse_complement (factorizations_comb.py:8-10) of an upper-cased word: A <-> T,
+    C <-> G, N -> N; every other byte, on which lyn2vec raises KeyError, is its own complement"""
+    return word[::-1].translate(_COMPLEMENT)
+
+
+def comb_lengths(word: bytes, fwd, rev):
+    """lyn2vec's d_duval_ (factorizations_comb.py:213-246) in closed form: the gaps between the
+    cuts of fwd(word) together with the cuts of rev(reverse_complement(word)) mirrored to
+    n - c; a cut both share is one cut"""
+    n = len(word)
+    cuts = set()
+    at = 0
+    for ln in fwd(word):
+        at += ln
+        cuts.add(at)
+    at = 0
+    for ln in rev(reverse_complement(word)):
+        cuts.add(n - at)
+        at += ln
+    cuts.discard(0)
+    out, prev = [], 0
+    for c in sorted(cuts):
+        out.append(c - prev)
+        prev = c
+    return out
+
+
 def factor_lengths(word: bytes, factorization="CFL", stats=None):
-    """the factor lengths of `word` under "CFL", "ICFL" or "CFL_ICFL-<T>" (the binding's
-    parse_factorization reads the name)"""
+    """the factor lengths of `word` under "CFL", "ICFL" or "CFL_ICFL-<T>", or under the combined
+    "CFL_COMB", "ICFL_COMB" or "CFL_ICFL_COMB-<T>", whose reverse side runs at threshold 30
+    whatever T is, as lyn2vec's does (the binding's parse_factorization reads the name)"""
     from . import parse_factorization
     kind, T = parse_factorization(factorization)
     if kind == "CFL":
         return duval_cfl_lengths(word)
     if kind == "ICFL":
         return icfl_lengths(word, stats)
-    return cfl_icfl_lengths(word, T, stats)
+    if kind == "CFL_ICFL":
+        return cfl_icfl_lengths(word, T, stats)
+    if kind == "CFL_COMB":
+        return comb_lengths(word, duval_cfl_lengths, duval_cfl_lengths)
+    if kind == "ICFL_COMB":
+        return comb_lengths(word, lambda w: icfl_lengths(w, stats), lambda w: icfl_lengths(w, stats))
+    return comb_lengths(word, lambda w: cfl_icfl_lengths(w, T, stats),
+                        lambda w: cfl_icfl_lengths(w, COMB_REV_THRESHOLD, stats))
 
 
 def cfl_lines(seq: bytes, gid: str, window=100, factorization="CFL"):

@@ -2,7 +2,8 @@
 // device (fpm_kfinger_*: the cyclic windows, Duval and the line text of lyn2vec's
 // fingerprint_utils.py:95-110, 443-476 and factorizations.py:102-126), or with -F the ICFL or
 // CFL_ICFL-T lines (ICFL_recursive, CFL_icfl, factorizations.py:143-248, 265-301; the names of
-// lyn2vec.py:47-59).  By default the lines
+// lyn2vec.py:47-59) or their combined forms CFL_COMB, ICFL_COMB and CFL_ICFL_COMB-T (d_cfl, d_icfl,
+// d_cfl_icfl, factorizations_comb.py:178-246; lyn2vec.py:60-72).  By default the lines
 // are written as one text, the input of `sketch -fp`; with -S they are hashed where they are
 // made (getHashFingerPrint, hash.cpp:45-73) and grouped into the References
 // Sketch::initFromFingerprints (Sketch.cpp:56-151) makes of that text, so the .msh is the one
@@ -56,15 +57,23 @@ std::string lineId(const std::string &name, const std::string &comment)
     return (b > a ? comment.substr(a, b - a) : name) + "_0";
 }
 
-// lyn2vec's --type_factorization spelling -> FPM_KF_* and the threshold: CFL, ICFL, or
-// CFL_ICFL-<T> with T in 1 .. the widest window, plain decimal digits
-bool parseFactorization(const std::string &name, uint32_t &kind, uint32_t &threshold)
+// lyn2vec's --type_factorization spelling -> FPM_KF_*, the threshold and whether the form is a
+// combined one: CFL, ICFL, or CFL_ICFL-<T> with T in 1 .. the widest window, plain decimal
+// digits; CFL_COMB, ICFL_COMB or CFL_ICFL_COMB-<T> by the same rules
+bool parseFactorization(const std::string &name, uint32_t &kind, uint32_t &threshold, bool &comb)
 {
     threshold = 0;
+    comb = false;
     if (name == "CFL") { kind = FPM_KF_CFL; return true; }
     if (name == "ICFL") { kind = FPM_KF_ICFL; return true; }
-    const std::string head = "CFL_ICFL-";
-    if (name.compare(0, head.size(), head) != 0) return false;
+    if (name == "CFL_COMB") { kind = FPM_KF_CFL; comb = true; return true; }
+    if (name == "ICFL_COMB") { kind = FPM_KF_ICFL; comb = true; return true; }
+    std::string head = "CFL_ICFL-";
+    if (name.compare(0, head.size(), head) != 0) {
+        head = "CFL_ICFL_COMB-";
+        if (name.compare(0, head.size(), head) != 0) return false;
+        comb = true;
+    }
     const std::string t = name.substr(head.size());
     if (t.empty() || t.size() > 9 || t.find_first_not_of("0123456789") != std::string::npos)
         return false;
@@ -79,6 +88,7 @@ struct Generator {
     fpm_ctx *ctx = nullptr;
     uint32_t window = 100;
     uint32_t factKind = FPM_KF_CFL, factThreshold = 0;
+    bool factComb = false;
     bool sketch = false;
     uint32_t seed = 42;
     bool use64 = false;
@@ -119,6 +129,7 @@ struct Generator {
         std::unique_ptr<fpm_kfinger, void (*)(fpm_kfinger *)> hold(job, fpm_kfinger_free);
         if (factKind != FPM_KF_CFL)
             check(fpm_kfinger_set_factorization(job, factKind, factThreshold), "kfinger");
+        if (factComb) check(fpm_kfinger_set_comb(job, 1), "kfinger");
         check(fpm_kfinger_run(job, seed, use64, nullptr), "kfinger");
         if (sketch) {
             std::vector<uint64_t> first(ids.size() + 1);
@@ -249,13 +260,16 @@ struct Generator {
 CommandKFinger::CommandKFinger()
 {
     name = "kfinger";
-    summary = "Create k-finger fingerprints (CFL, ICFL, CFL_ICFL-T) from sequences.";
+    summary = "Create k-finger fingerprints (CFL, ICFL, CFL_ICFL-T, their _COMB forms) from sequences.";
     description = "Create the k-finger lines of sequences (lyn2vec --type basic "
                   "--type_factorization CFL, ICFL or CFL_ICFL-T, chosen with -F): for every "
                   "record and every cyclic window of it, the lengths of the window's Lyndon "
                   "factors (CFL), of its inverse Lyndon factors (ICFL), or of its Lyndon factors "
                   "with each one longer than T replaced by its own inverse Lyndon factors "
-                  "(CFL_ICFL-T). Inputs can be fasta or fastq files "
+                  "(CFL_ICFL-T). CFL_COMB, ICFL_COMB and CFL_ICFL_COMB-T cut the window where that "
+                  "factorization cuts it and, mirrored, where it cuts the window's reverse "
+                  "complement (there CFL_ICFL runs at T = 30 whatever T is given, as lyn2vec's "
+                  "does). Inputs can be fasta or fastq files "
                   "(gzipped or not), and \"-\" can be given to read from standard input. The lines "
                   "of all inputs are written to <prefix>.txt, the input of `sketch -fp`; with -S "
                   "they are sketched instead, into the <prefix>.msh that `sketch -fp` writes for "
@@ -266,8 +280,8 @@ CommandKFinger::CommandKFinger()
         "Window size. Each record of at least this many bases gives one line per cyclic window "
         "start, a shorter record one line.", "100", 1, maxWindow()));
     addOption("factorization", Option(Option::String, "F", "Input",
-        "Factorization of a window: CFL, ICFL or CFL_ICFL-<T>, T from 1 to the largest window "
-        "size.", "CFL"));
+        "Factorization of a window: CFL, ICFL, CFL_ICFL-<T>, CFL_COMB, ICFL_COMB or "
+        "CFL_ICFL_COMB-<T>, T from 1 to the largest window size.", "CFL"));
     addOption("prefix", Option(Option::File, "o", "Output",
         "Output prefix (first input file used if unspecified). The suffix '.txt' (or '.msh' with "
         "-S) will be appended.", ""));
@@ -305,9 +319,10 @@ int CommandKFinger::run() const
     const uint32_t window = (uint32_t)options.at("window").getArgumentAsNumber();
     Generator g;
     const std::string &fact = options.at("factorization").argument;
-    if (!parseFactorization(fact, g.factKind, g.factThreshold)) {
-        std::cerr << "ERROR: unknown factorization " << fact << " for -F: CFL, ICFL or CFL_ICFL-<T> "
-                  << "with T from 1 to " << maxWindow() << "." << std::endl;
+    if (!parseFactorization(fact, g.factKind, g.factThreshold, g.factComb)) {
+        std::cerr << "ERROR: unknown factorization " << fact << " for -F: CFL, ICFL, CFL_ICFL-<T>, "
+                  << "CFL_COMB, ICFL_COMB or CFL_ICFL_COMB-<T> with T from 1 to " << maxWindow()
+                  << "." << std::endl;
         return 1;
     }
     if (!checkInputArguments(arguments, 0, "input")) return 1;

@@ -453,6 +453,17 @@ void fpm_fp_text_limits(uint32_t *text_chunk, uint32_t *span_bytes, uint32_t *he
  * known out of band: a 0x24 byte is a byte like any other, where lyn2vec's in-band '$' is not.
  * Another kind, a threshold out of range, or a call after fpm_kfinger_run is FPM_EINVAL and
  * leaves the job as it was.
+ * fpm_kfinger_set_comb (lyn2vec --type_factorization CFL_COMB / ICFL_COMB / CFL_ICFL_COMB-T:
+ * d_cfl, d_icfl, d_cfl_icfl and d_duval_, factorizations_comb.py:178-246), between stage and run:
+ * with on = 1 a line of n bytes is cut where the job's factorization cuts it and at n - c for
+ * every cut c of the same factorization of its reverse complement (A <-> T, C <-> G, every other
+ * byte itself, after the upper-casing), and its lengths are the gaps between those cuts; a cut
+ * both sides share is one cut.  The reverse side of FPM_KF_CFL_ICFL runs at threshold 30
+ * whatever the job's threshold is: lyn2vec's d_duval_ calls cfl_icfl on the reverse complement
+ * without it (:221), so its default cfl_max = 30 (:164) holds there, and the lines are lyn2vec's
+ * byte for byte.  lyn2vec's reverse_complement raises KeyError on a byte outside ACGTN; here
+ * such a byte is its own complement.  on = 0 is what a job that never calls it makes.  on > 1, a
+ * NULL job or a call after fpm_kfinger_run is FPM_EINVAL and leaves the job as it was.
  * fpm_kfinger_run (factorizations.py:102-126 + hash.cpp:45-73): pass one on `stream` (NULL: the
  * context's): per line the hash of its 8 x count little-endian bytes (u32, or u64 with use64:
  * what fpm_fp_hash_lines gives for the same values) and its value count.
@@ -478,6 +489,8 @@ int fpm_kfinger_stage_seq(fpm_ctx *ctx, fpm_seqtext *seq, const uint8_t *take, u
 #define FPM_KF_ICFL 1
 #define FPM_KF_CFL_ICFL 2
 int fpm_kfinger_set_factorization(fpm_kfinger *job, uint32_t kind, uint32_t threshold);
+/* lyn2vec --type_factorization CFL_COMB / ICFL_COMB / CFL_ICFL_COMB-T (factorizations_comb.py:178-246) */
+int fpm_kfinger_set_comb(fpm_kfinger *job, uint32_t on);   /* before fpm_kfinger_run; else FPM_EINVAL */
 int fpm_kfinger_run(fpm_kfinger *job, uint32_t seed, uint32_t use64, void *stream);
 int fpm_kfinger_fetch(fpm_kfinger *job, uint64_t *rec_first_line, void *hash, uint32_t *n_vals);
 int fpm_kfinger_device_output(fpm_kfinger *job, void **d_hash, uint32_t **d_n_vals,
@@ -488,12 +501,17 @@ int fpm_kfinger_text(fpm_kfinger *job, const char *ids, const uint64_t *id_off, 
                      uint64_t cap, uint64_t *n_bytes);
 void fpm_kfinger_free(fpm_kfinger *job);
 void fpm_kfinger_limits(uint32_t *max_window, uint32_t *run_length);
-/* The workgroups of the grid the job's run used for a window whose ICFL working memory lies in
- * device memory (a test hook like fpm_sketch_job_plan, the result does not depend on it): at
- * most two per compute unit and no more than the job has descriptors, each taking every
- * *groups-th descriptor.  0 for CFL, for a window that keeps that memory in LDS, for a job
- * without lines, and before fpm_kfinger_run. */
+/* The workgroups of the grid the job's run used for a window whose working memory (ICFL's, a
+ * combined form's cut bits) lies in device memory (a test hook like fpm_sketch_job_plan, the
+ * result does not depend on it): at most two per compute unit and no more than the job has
+ * descriptors, each taking every *groups-th descriptor.  0 for CFL, for a window that keeps that
+ * memory in LDS, for a job without lines, and before fpm_kfinger_run. */
 int fpm_kfinger_wide_groups(fpm_kfinger *job, uint32_t *groups);
+/* The widest window whose working memory stays in LDS under factorization `kind` (FPM_KF_*),
+ * combined (comb = 1) or not; the next window is the first to keep it in device memory.  The
+ * widest window of fpm_kfinger_limits for plain FPM_KF_CFL, which has no working memory.  No
+ * device needed; an unknown kind or comb > 1 is FPM_EINVAL. */
+int fpm_kfinger_lds_window(uint32_t kind, uint32_t comb, uint32_t *window);
 
 /* ---- dist ---------------------------------------------------------------------
  * Replaces compare()/compareSketches()/pValue() (CommandDistance.cpp:335-450) over

@@ -5,7 +5,8 @@ Kernel times: both passes of fpm_kfinger_* over the whole set in one job, from t
 HIP events (FPM_K_KFINGER: factorization + line hash; FPM_K_KFINGER_OUT: sizes, scan and the
 text lines), best of --repeat after one warm-up call, every repeat listed beside it.  With
 --factorization ICFL or CFL_ICFL-<T> the CFL passes over the same records are timed in the same
-process, as the yardstick.  --period P replaces the random records by text of period P broken
+process, as the yardstick; with a combined form (CFL_COMB, ICFL_COMB, CFL_ICFL_COMB-<T>) also the
+passes of the form it combines (plain_*).  --period P replaces the random records by text of period P broken
 once per window length (ICFL's longest scans and border chains); --no-wall leaves the wall times
 out.
 Wall times, best of --repeat: `fpmash kfinger -S` on the FASTA, against the route to the same
@@ -66,7 +67,11 @@ def main():
     ids = datagen.lyn2vec_ids(a.n_seqs)
     full = [("G00000" + i + "_0").encode() for i in ids]
     fact = a.factorization
-    fpmash.parse_factorization(fact)
+    kind, thr = fpmash.parse_factorization(fact)
+    # the form a combined one combines: CFL_COMB -> CFL, CFL_ICFL_COMB-T -> CFL_ICFL-T
+    plain = None
+    if kind.endswith("_COMB"):
+        plain = kind[:-5] + ("-%d" % thr if thr else "")
     res = {"n_seqs": a.n_seqs, "seq_len": a.seq_len, "window": a.window, "factorization": fact,
            "period": a.period, "build": fpmash.build_id()}
 
@@ -87,6 +92,10 @@ def main():
             _, k1, k2 = passes("CFL")
             res.update(cfl_pass1_ms=min(k1), cfl_pass2_text_ms=min(k2), cfl_pass1_all_ms=k1,
                        cfl_pass2_text_all_ms=k2)
+        if plain and plain != "CFL":
+            _, k1, k2 = passes(plain)
+            res.update(plain=plain, plain_pass1_ms=min(k1), plain_pass2_text_ms=min(k2),
+                       plain_pass1_all_ms=k1, plain_pass2_text_all_ms=k2)
         r, k1, k2 = passes(fact)
         res.update(lines=int(r["n_lines"]), text_bytes=len(r["text"]), pass1_ms=min(k1),
                    pass2_text_ms=min(k2), pass1_all_ms=k1, pass2_text_all_ms=k2)
