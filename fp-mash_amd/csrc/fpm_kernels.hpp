@@ -600,6 +600,25 @@ hipError_t launch_kf_text(const uint8_t *d_seq, const uint64_t *d_rec_pos,
                           uint32_t w, const uint32_t *d_off, const uint8_t *d_ids,
                           const uint64_t *d_id_off, const uint32_t *d_id_len, uint8_t *d_out,
                           const KfFact &f, hipStream_t st);
+// Split jobs (lyn2vec --type generalized): the units of rec_pos / rec_len are a record's
+// consecutive pieces, all in kind-1 descriptors, and d_piece_rec[p] (ascending, n_piece entries)
+// is the record of piece p, which indexes the IDs.  d_piece_rec null: a window job.
+// The sizes of the text below per line / piece (fact: of the factor text), from pass one's
+// d_n_vals and d_body; *d_text_total (zeroed by the caller) += the sum
+hipError_t launch_kf_ext_size(const KfDesc *d_descs, uint32_t n_desc, const uint32_t *d_rec_len,
+                              const uint32_t *d_piece_rec, uint32_t n_piece, uint32_t w,
+                              bool fact, const uint32_t *d_n_vals, const uint32_t *d_body,
+                              const uint32_t *d_id_len, uint32_t *d_size,
+                              unsigned long long *d_text_total, hipStream_t st);
+// pass two of a split job's text, "<id>  <len> <len> | <len> | \n" per record, or with fact the
+// factor text of either kind of job: the same line with each factor's upper-cased bytes for its
+// length (a window job's line: "<id> <factor> <factor>\n")
+hipError_t launch_kf_ext_text(const uint8_t *d_seq, const uint64_t *d_rec_pos,
+                              const uint32_t *d_rec_len, const KfDesc *d_descs, uint32_t n_desc,
+                              uint32_t w, const uint32_t *d_off, const uint8_t *d_ids,
+                              const uint64_t *d_id_off, const uint32_t *d_id_len,
+                              const uint32_t *d_piece_rec, uint32_t n_piece, bool fact,
+                              uint8_t *d_out, const KfFact &f, hipStream_t st);
 
 // The transposed grid of a rectangular compare (fpm_refset_dist_mirror_dev): cell (r, q) at
 // r * n_qry + q holds the pair "query r of the ref set against ref q of the query set".  For

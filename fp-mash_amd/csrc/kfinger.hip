@@ -32,6 +32,15 @@
 // one, marks the cuts of both in one more bit array (a cut both share is one bit), and reads it
 // left to right into the same emit callbacks.  The reverse side of CFL_ICFL_COMB-T runs at
 // threshold 30 whatever T is, as lyn2vec's does (d_duval_ calls it without k, :221, :164).
+//
+// Long reads (lyn2vec `--type generalized --split N`; factors_string, fingerprint_utils.py:114-130,
+// compute_long_fingerprint_by_list, :480-518) cut a record into consecutive pieces of N bytes and
+// factorize each on its own.  The pieces take the place of the records in rec_pos / rec_len and
+// ride in pack descriptors, so every kernel above runs over them as it stands; piece_rec maps a
+// piece to its record for the one text line per record, "<id>  <lengths> | <lengths> | \n"
+// (kf_ext_size_kernel, kf_emit_ext_kernel).  The same two kernels write the factor text of
+// lyn2vec's `--fact create` (:471-474, :509-511) for either kind of job: a factor's upper-cased
+// bytes, copied from the stage, where the fingerprint has its length.
 #include "fpm_device.hpp"
 #include "fpm_kernels.hpp"
 
@@ -524,6 +533,136 @@ __global__ __launch_bounds__(kKfRun) void kf_emit_kernel(
     }
 }
 
+// The record a unit (a line's record, or a split job's piece) belongs to, and whether the unit
+// opens and closes that record's text line.  piece_rec null: a window job, whose every line is
+// a text line of its own; else piece_rec[p] is the record of piece p of n_piece, ascending.
+struct KfUnit {
+    uint32_t rec;
+    bool first, last;
+};
+
+__device__ __forceinline__ KfUnit kf_unit(const uint32_t *__restrict__ piece_rec,
+                                          uint32_t n_piece, uint32_t unit)
+{
+    if (!piece_rec) return KfUnit{unit, true, true};
+    const uint32_t rec = piece_rec[unit];
+    return KfUnit{rec, unit == 0 || piece_rec[unit - 1] != rec,
+                  unit + 1 == n_piece || piece_rec[unit + 1] != rec};
+}
+
+// The sizes of the layouts kf_emit_ext_kernel writes, from what pass one kept (body: 1 + per
+// factor 1 + its digits; n_vals: the factors).  A line's tokens joined by single spaces take
+// body - 2 bytes as lengths and n + factors - 1 as factor bytes (fact).  A window job's line
+// (piece_rec null) is "<id> <tokens>\n"; a split job's unit is "<tokens> | ", behind
+// "<id>  " where it opens its record's line and before "\n" where it closes it.
+// *text_total += the sum.
+__global__ __launch_bounds__(kKfRun) void kf_ext_size_kernel(
+    const KfDesc *__restrict__ descs, const uint32_t *__restrict__ rec_len,
+    const uint32_t *__restrict__ piece_rec, uint32_t n_piece, uint32_t w, uint32_t fact,
+    const uint32_t *__restrict__ n_vals, const uint32_t *__restrict__ body,
+    const uint32_t *__restrict__ id_len, uint32_t *__restrict__ size,
+    unsigned long long *__restrict__ text_total)
+{
+    __shared__ unsigned long long s_red[kKfRun / 64];
+    const KfDesc d = descs[blockIdx.x];
+    uint32_t sz = 0;
+    if (threadIdx.x < d.count) {
+        const uint64_t line = d.line_base + threadIdx.x;
+        const uint32_t unit = d.kind == 0 ? d.rec : d.rec + threadIdx.x;
+        const uint32_t n = d.kind == 0 ? w : rec_len[unit];
+        const KfUnit u = kf_unit(piece_rec, n_piece, unit);
+        sz = fact ? n + n_vals[line] - 1 : body[line] - 2;
+        if (piece_rec) sz += 3 + (u.first ? id_len[u.rec] + 2 : 0) + (u.last ? 1 : 0);
+        else sz += id_len[u.rec] + 2;
+        size[line] = sz;
+    }
+    const unsigned long long t = kf_block_sum(sz, s_red);
+    if (threadIdx.x == 0 && t) atomicAdd(text_total, t);
+}
+
+// Pass two of the layouts above, at out + off[line]: the lane factorizes its line again and
+// writes per factor its length in digits or, with FACT, its upper-cased bytes from the stage.
+template <bool FACT, int MODE, bool COMB>
+__device__ __forceinline__ void kf_emit_ext_desc(
+    const uint8_t *__restrict__ seq, const uint64_t *__restrict__ rec_pos,
+    const uint32_t *__restrict__ rec_len, const KfDesc &d, uint32_t w,
+    const uint32_t *__restrict__ off, const uint8_t *__restrict__ ids,
+    const uint64_t *__restrict__ id_off, const uint32_t *__restrict__ id_len,
+    const uint32_t *__restrict__ piece_rec, uint32_t n_piece, uint8_t *__restrict__ out,
+    uint32_t thr, const KfWorkOf<MODE> &wk, uint32_t *cuts, uint8_t *s_seq, uint32_t *s_off)
+{
+    uint32_t base, n, unit;
+    if (!kf_stage(seq, rec_pos, rec_len, d, w, s_seq, s_off, base, n, unit)) return;
+    const uint64_t line = d.line_base + threadIdx.x;
+    const bool split = piece_rec != nullptr;
+    const KfUnit u = kf_unit(piece_rec, n_piece, unit);
+    uint8_t *o = out + off[line];
+    if (u.first) {
+        const uint8_t *id = ids + id_off[u.rec];
+        const uint32_t il = id_len[u.rec];
+        for (uint32_t t = 0; t < il; t++) o[t] = id[t];
+        o += il;
+        if (split) {
+            o[0] = o[1] = ' ';
+            o += 2;
+        }
+    }
+    bool lead = !split;                      // a space goes before this token
+    const uint8_t *s = s_seq + base;
+    kf_line<MODE, COMB>(s_seq + base, n, thr, wk, cuts, [&](uint32_t len) {
+        if (lead) *o++ = ' ';
+        lead = true;
+        if (FACT) {
+            for (uint32_t t = 0; t < len; t++) o[t] = s[t];
+            s += len;
+            o += len;
+        } else {
+            const uint32_t nd = kf_digits(len);
+            uint32_t v = len;
+            for (uint32_t t = nd; t > 0; t--) {
+                o[t - 1] = (uint8_t)('0' + v % 10);
+                v /= 10;
+            }
+            o += nd;
+        }
+    });
+    if (split) {
+        o[0] = ' ';
+        o[1] = '|';
+        o[2] = ' ';
+        o += 3;
+    }
+    if (u.last) *o = '\n';
+}
+
+template <bool FACT, int MODE, bool COMB>
+__global__ __launch_bounds__(kKfRun) void kf_emit_ext_kernel(
+    const uint8_t *__restrict__ seq, const uint64_t *__restrict__ rec_pos,
+    const uint32_t *__restrict__ rec_len, const KfDesc *__restrict__ descs, uint32_t n_desc,
+    uint32_t w, const uint32_t *__restrict__ off, const uint8_t *__restrict__ ids,
+    const uint64_t *__restrict__ id_off, const uint32_t *__restrict__ id_len,
+    const uint32_t *__restrict__ piece_rec, uint32_t n_piece, uint8_t *__restrict__ out,
+    uint32_t thr, uint8_t *__restrict__ work)
+{
+    __shared__ uint8_t s_seq[kKfLds];
+    __shared__ uint32_t s_off[kKfRun];
+    uint8_t *region = kf_region<MODE, COMB>(w, work, blockIdx.x);
+    const KfWorkOf<MODE> wk = kf_work<MODE>(w, region);
+    uint32_t *cuts = kf_cut_bits<MODE, COMB>(w, region);
+    if constexpr (kf_mode_wide(MODE)) {
+        for (uint32_t b = blockIdx.x; b < n_desc; b += gridDim.x) {
+            kf_emit_ext_desc<FACT, MODE, COMB>(seq, rec_pos, rec_len, descs[b], w, off, ids,
+                                               id_off, id_len, piece_rec, n_piece, out, thr, wk,
+                                               cuts, s_seq, s_off);
+            __syncthreads();   // every lane is done with the stage before the next one fills it
+        }
+    } else {
+        kf_emit_ext_desc<FACT, MODE, COMB>(seq, rec_pos, rec_len, descs[blockIdx.x], w, off, ids,
+                                           id_off, id_len, piece_rec, n_piece, out, thr, wk, cuts,
+                                           s_seq, s_off);
+    }
+}
+
 namespace {
 
 // What a launch with factorization f over window w takes: the instance, its grid, its dynamic
@@ -637,6 +776,55 @@ hipError_t launch_kf_text(const uint8_t *d_seq, const uint64_t *d_rec_pos,
 {
     return kf_launch_emit<true>(d_seq, d_rec_pos, d_rec_len, d_descs, n_desc, w, d_off, d_ids,
                                 d_id_off, d_id_len, d_out, nullptr, f, st);
+}
+
+hipError_t launch_kf_ext_size(const KfDesc *d_descs, uint32_t n_desc, const uint32_t *d_rec_len,
+                              const uint32_t *d_piece_rec, uint32_t n_piece, uint32_t w,
+                              bool fact, const uint32_t *d_n_vals, const uint32_t *d_body,
+                              const uint32_t *d_id_len, uint32_t *d_size,
+                              unsigned long long *d_text_total, hipStream_t st)
+{
+    if (!n_desc) return hipSuccess;
+    hipLaunchKernelGGL(kf_ext_size_kernel, dim3(n_desc), dim3(kKfRun), 0, st, d_descs, d_rec_len,
+                       d_piece_rec, n_piece, w, fact ? 1u : 0u, d_n_vals, d_body, d_id_len, d_size,
+                       d_text_total);
+    return hipGetLastError();
+}
+
+namespace {
+
+template <bool FACT>
+hipError_t kf_launch_ext(const uint8_t *d_seq, const uint64_t *d_rec_pos,
+                         const uint32_t *d_rec_len, const KfDesc *d_descs, uint32_t n_desc,
+                         uint32_t w, const uint32_t *d_off, const uint8_t *d_ids,
+                         const uint64_t *d_id_off, const uint32_t *d_id_len,
+                         const uint32_t *d_piece_rec, uint32_t n_piece, uint8_t *d_out,
+                         const KfFact &f, hipStream_t st)
+{
+    KfShape sh;
+    if (w < 1 || w > kKfMaxWindow || !kf_shape(f, w, n_desc, sh)) return hipErrorInvalidValue;
+    if (!n_desc) return hipSuccess;
+    auto kernel = KF_PICK(kf_emit_ext_kernel, FACT, );
+    hipLaunchKernelGGL(kernel, dim3(sh.grid), dim3(kKfRun), sh.lds, st, d_seq, d_rec_pos, d_rec_len,
+                       d_descs, n_desc, w, d_off, d_ids, d_id_off, d_id_len, d_piece_rec, n_piece,
+                       d_out, sh.thr, (uint8_t *)f.work);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_kf_ext_text(const uint8_t *d_seq, const uint64_t *d_rec_pos,
+                              const uint32_t *d_rec_len, const KfDesc *d_descs, uint32_t n_desc,
+                              uint32_t w, const uint32_t *d_off, const uint8_t *d_ids,
+                              const uint64_t *d_id_off, const uint32_t *d_id_len,
+                              const uint32_t *d_piece_rec, uint32_t n_piece, bool fact,
+                              uint8_t *d_out, const KfFact &f, hipStream_t st)
+{
+    return fact ? kf_launch_ext<true>(d_seq, d_rec_pos, d_rec_len, d_descs, n_desc, w, d_off,
+                                      d_ids, d_id_off, d_id_len, d_piece_rec, n_piece, d_out, f, st)
+                : kf_launch_ext<false>(d_seq, d_rec_pos, d_rec_len, d_descs, n_desc, w, d_off,
+                                       d_ids, d_id_off, d_id_len, d_piece_rec, n_piece, d_out, f,
+                                       st);
 }
 
 }  // namespace fpm

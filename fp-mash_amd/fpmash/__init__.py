@@ -5,7 +5,8 @@ A ctypes mirror of the reference's engine calls for this path:
   -fp line hashing (getHashFingerPrint, hash.cpp:45-73)                    -> Context.fp_hash_lines
   lyn2vec CFL k-fingers (fingerprint_utils.py:95-110, 443-476) + their hashes -> Context.kfinger
     (factorization="ICFL" / "CFL_ICFL-<T>": factorizations.py:143-248, 265-301; "CFL_COMB" /
-    "ICFL_COMB" / "CFL_ICFL_COMB-<T>": factorizations_comb.py:178-246)
+    "ICFL_COMB" / "CFL_ICFL_COMB-<T>": factorizations_comb.py:178-246; split=N: the long-read
+    fingerprints, fingerprint_utils.py:114-130, 480-518; fact_text=True: the --fact create text)
   compare/compareSketches/pValue (CommandDistance.cpp:335-450)             -> Context.dist
   contain/containSketches (CommandContain.cpp:314-412)                     -> Context.contain
   screen: hashSequence, sums, -w, pValueWithin (CommandScreen.cpp:133-406) -> Context.screen
@@ -155,6 +156,10 @@ SYMBOLS = [
     ("fpm_kfinger_values", C.c_int, [vp, u64p, u16p, C.c_uint64, u64p]),
     ("fpm_kfinger_text", C.c_int, [vp, C.c_char_p, u64p, vp, C.c_uint64, u64p]),
     ("fpm_kfinger_free", None, [vp]),
+    ("fpm_kfinger_stage_split", C.c_int, [vp, C.c_char_p, u64p, C.c_uint32, C.c_uint32,
+                                          C.POINTER(vp), u64p]),
+    ("fpm_kfinger_stage_split_seq", C.c_int, [vp, vp, u8p, C.c_uint32, C.POINTER(vp), u64p]),
+    ("fpm_kfinger_fact_text", C.c_int, [vp, C.c_char_p, u64p, vp, C.c_uint64, u64p]),
     ("fpm_kfinger_limits", None, [u32p, u32p]),
     ("fpm_kfinger_wide_groups", C.c_int, [vp, u32p]),
     ("fpm_kfinger_lds_window", C.c_int, [C.c_uint32, C.c_uint32, u32p]),
@@ -440,6 +445,15 @@ def kfinger_id(header: bytes) -> bytes:
     else:
         name, rest = tok[0], tok[1:]
     return (rest[0] if rest else name) + b"_0"
+
+
+def kfinger_long_id(header: bytes) -> bytes:
+    """The ID of a record's long-read line (kfinger split=N, `fpmash kfinger -L`) from its header
+    line: the record's name, its first whitespace-separated token, with no "_0"."""
+    if header[:1].isspace():
+        return b""
+    tok = header.split(None, 1)
+    return tok[0] if tok else b""
 
 
 def _p(a, t):
@@ -1470,7 +1484,8 @@ class Context:
 
     # --- k-fingers from sequence ----------------------------------------------------
     @staticmethod
-    def _kfinger_out(job, n, n_rec, seed, use64, ids, values, text, fact=(KF_CFL, 0)):
+    def _kfinger_out(job, n, n_rec, seed, use64, ids, values, text, fact=(KF_CFL, 0),
+                     fact_text=False):
         """run + fetch (+ the pass-two outputs) of a staged k-finger job under the factorization
         fact = (FPM_KF_* kind, threshold) or, combined, (kind, threshold, 1); frees it"""
         L = lib()
@@ -1497,22 +1512,24 @@ class Context:
                 _check(L.fpm_kfinger_values(job, _p(off, u64p), _p(vals, u16p), tot.value,
                                             C.byref(tot)))
                 res["val_off"], res["vals"] = off, vals[:tot.value]
-            if text:
+            for want, key, call in ((text, "text", L.fpm_kfinger_text),
+                                    (fact_text, "fact_text", L.fpm_kfinger_fact_text)):
+                if not want:
+                    continue
                 if ids is None or len(ids) != n_rec:
-                    raise ValueError("text=True needs one ID per record")
+                    raise ValueError("text=True and fact_text=True need one ID per record")
                 blob, off = pack_records([bytes(i) for i in ids])
                 nb = C.c_uint64()
-                _check(L.fpm_kfinger_text(job, blob, _p(off, u64p), None, 0, C.byref(nb)))
+                _check(call(job, blob, _p(off, u64p), None, 0, C.byref(nb)))
                 out = np.zeros(max(nb.value, 1), np.uint8)
-                _check(L.fpm_kfinger_text(job, blob, _p(off, u64p), out.ctypes.data, nb.value,
-                                          C.byref(nb)))
-                res["text"] = out[:nb.value].tobytes()
+                _check(call(job, blob, _p(off, u64p), out.ctypes.data, nb.value, C.byref(nb)))
+                res[key] = out[:nb.value].tobytes()
             return res
         finally:
             L.fpm_kfinger_free(job)
 
     def kfinger(self, seqs, window=100, seed=42, use64=False, max_lines=None, ids=None,
-                values=False, text=False, factorization="CFL"):
+                values=False, text=False, factorization="CFL", split=None, fact_text=False):
         """k-fingers of the records `seqs` (lyn2vec --type basic --type_factorization CFL,
         fingerprint_utils.py:95-110, 443-476; factorization "ICFL" or "CFL_ICFL-<T>" for lyn2vec's
         factorizations of those names, fpm_kfinger_set_factorization; "CFL_COMB", "ICFL_COMB" or
@@ -1521,21 +1538,39 @@ class Context:
         values the factor lengths (vals u16, line l's at val_off[l] .. val_off[l + 1]); with
         text the lines' text, ids[r] being record r's full ID bytes (lyn2vec's "<id>_0").
         wide_groups: fpm_kfinger_wide_groups of the run (a test hook).
-        max_lines: only the first so many lines exist (None: all)."""
+        max_lines: only the first so many lines exist (None: all).
+        split=N: the long-read job instead (lyn2vec --type generalized --split N,
+        fpm_kfinger_stage_split): a line is one of a record's consecutive pieces of N bytes, the
+        text has one line per record, "<id>  <lengths> | <lengths> | ", and ids[r] is the ID as
+        it is to appear; window and max_lines do not apply.  fact_text: also the factor text
+        (lyn2vec --fact create, fpm_kfinger_fact_text), the text with each factor's bytes in
+        place of its length."""
         fact = kfinger_factorization(factorization)      # (refused before anything is staged)
         data, off = pack_records([bytes(s) for s in seqs])
         job, n = vp(), C.c_uint64()
-        cap = 0xFFFFFFFFFFFFFFFF if max_lines is None else int(max_lines)
-        _check(lib().fpm_kfinger_stage(self.h, data, _p(off, u64p), len(seqs), window, cap,
-                                       C.byref(job), C.byref(n)))
-        return self._kfinger_out(job, n.value, len(seqs), seed, use64, ids, values, text, fact)
+        if split is not None:
+            if max_lines is not None:
+                raise ValueError("a split job has no max_lines")
+            _check(lib().fpm_kfinger_stage_split(self.h, data, _p(off, u64p), len(seqs), int(split),
+                                                 C.byref(job), C.byref(n)))
+        else:
+            cap = 0xFFFFFFFFFFFFFFFF if max_lines is None else int(max_lines)
+            _check(lib().fpm_kfinger_stage(self.h, data, _p(off, u64p), len(seqs), window, cap,
+                                           C.byref(job), C.byref(n)))
+        return self._kfinger_out(job, n.value, len(seqs), seed, use64, ids, values, text, fact,
+                                 fact_text)
 
     def kfinger_fasta(self, files, take=None, window=100, seed=42, use64=False, max_lines=None,
-                      ids=None, values=False, text=False, factorization="CFL"):
+                      ids=None, values=False, text=False, factorization="CFL", split=None,
+                      fact_text=False):
         """kfinger over the records of FASTA / FASTQ file images parsed on the device
         (fpm_seq_parse + fpm_kfinger_stage_seq); take[r] false leaves record r out.  ids None:
-        each record's ID by kfinger_id of its header line.  Also returns the parse's records."""
+        each record's ID by kfinger_id of its header line (with split, kfinger_long_id: the
+        record's name).  split, fact_text: as in kfinger (fpm_kfinger_stage_split_seq).  Also
+        returns the parse's records."""
         fact = kfinger_factorization(factorization)
+        if split is not None and max_lines is not None:
+            raise ValueError("a split job has no max_lines")
         seq_job, recs, quality = self.seq_parse(files)
         try:
             if quality:
@@ -1546,19 +1581,24 @@ class Context:
                 for r in range(n_rec):
                     img = files[int(recs["seg"][r])]
                     o, ln = int(recs["hdr_off"][r]), int(recs["hdr_len"][r])
-                    ids.append(kfinger_id(img[o + 1:o + ln]))
+                    ids.append((kfinger_id if split is None else kfinger_long_id)(img[o + 1:o + ln]))
             t = None
             if take is not None:
                 t = np.ascontiguousarray(np.asarray(take, dtype=bool), dtype=np.uint8)
                 if t.size == 0:
                     t = np.zeros(1, np.uint8)
             job, n = vp(), C.c_uint64()
-            cap = 0xFFFFFFFFFFFFFFFF if max_lines is None else int(max_lines)
-            _check(lib().fpm_kfinger_stage_seq(self.h, seq_job, _p(t, u8p), window, cap,
-                                               C.byref(job), C.byref(n)))
+            if split is not None:
+                _check(lib().fpm_kfinger_stage_split_seq(self.h, seq_job, _p(t, u8p), int(split),
+                                                         C.byref(job), C.byref(n)))
+            else:
+                cap = 0xFFFFFFFFFFFFFFFF if max_lines is None else int(max_lines)
+                _check(lib().fpm_kfinger_stage_seq(self.h, seq_job, _p(t, u8p), window, cap,
+                                                   C.byref(job), C.byref(n)))
         finally:
             lib().fpm_seq_free(seq_job)
-        res = self._kfinger_out(job, n.value, n_rec, seed, use64, ids, values, text, fact)
+        res = self._kfinger_out(job, n.value, n_rec, seed, use64, ids, values, text, fact,
+                                fact_text)
         res["records"] = recs
         return res
 

@@ -9,6 +9,10 @@
 // Sketch::initFromFingerprints (Sketch.cpp:56-151) makes of that text, so the .msh is the one
 // `sketch -fp` writes for it, with no text in between.  Records are found by kseq's rules, like
 // every other verb's; the inputs are streamed in slices of whole records bounded by bytes.
+// -L N is lyn2vec's long-read mode (`--type generalized --split N`, lyn2vec.py:100-177,
+// fingerprint_utils.py:114-130, 480-518): a record's consecutive pieces of N bases are factorized
+// each on its own and the record is one line; -f writes the factor text of `--fact create`
+// (fingerprint_utils.py:471-474, 509-511) beside the k-finger text, in either mode.
 #include "CommandKFinger.h"
 #include "Device.h"
 #include "ParsedFile.h"
@@ -57,6 +61,12 @@ std::string lineId(const std::string &name, const std::string &comment)
     return (b > a ? comment.substr(a, b - a) : name) + "_0";
 }
 
+// the factor text's path beside the k-finger text's: <prefix>.fact.txt for <prefix>.txt
+std::string factPathOf(const std::string &textPath)
+{
+    return textPath.substr(0, textPath.size() - 4) + ".fact.txt";
+}
+
 // lyn2vec's --type_factorization spelling -> FPM_KF_*, the threshold and whether the form is a
 // combined one: CFL, ICFL, or CFL_ICFL-<T> with T in 1 .. the widest window, plain decimal
 // digits; CFL_COMB, ICFL_COMB or CFL_ICFL_COMB-<T> by the same rules
@@ -89,11 +99,15 @@ struct Generator {
     uint32_t window = 100;
     uint32_t factKind = FPM_KF_CFL, factThreshold = 0;
     bool factComb = false;
+    uint32_t split = 0;                   // -L: the long-read mode's piece length (0: windows)
+    bool factText = false;                // -f
     bool sketch = false;
     uint32_t seed = 42;
     bool use64 = false;
     std::string outPath;
     FILE *out = nullptr;
+    std::string factPath;
+    FILE *factOut = nullptr;
     uint64_t records = 0;                 // kseq records read, empty ones included
     uint64_t linesLeft = ~0ull;           // -S: what is left of the 1,000,000 lines (Sketch.cpp:37, 82)
     // -S: the lines' hashes and their References so far
@@ -111,6 +125,10 @@ struct Generator {
             fclose(out);
             remove(outPath.c_str());
         }
+        if (factOut) {
+            fclose(factOut);
+            remove(factPath.c_str());
+        }
         std::cerr << "ERROR: " << msg << std::endl;
         fatalExit();
     }
@@ -120,6 +138,16 @@ struct Generator {
         if (out || sketch) return;
         out = fopen(outPath.c_str(), "wb");
         if (!out) die("could not open " + outPath + " for writing.");
+        if (!factText) return;
+        factOut = fopen(factPath.c_str(), "wb");
+        if (!factOut) die("could not open " + factPath + " for writing.");
+    }
+
+    // a record's ID: the long-read mode's is the name alone (lyn2vec appends "_0" only under
+    // --rev_comb true, lyn2vec.py:179-183)
+    std::string idOf(const std::string &name, const std::string &comment) const
+    {
+        return split ? name : lineId(name, comment);
     }
 
     // Run a staged job over records with the IDs `ids` and take its lines.  false: the job's
@@ -160,13 +188,27 @@ struct Generator {
             blob += ids[r];
             off[r + 1] = blob.size();
         }
-        uint64_t bytes = 0;
-        const int rc = fpm_kfinger_text(job, blob.data(), off.data(), nullptr, 0, &bytes);
+        // both texts are sized before either is written
+        uint64_t bytes = 0, factBytes = 0;
+        int rc = fpm_kfinger_text(job, blob.data(), off.data(), nullptr, 0, &bytes);
         if (rc == FPM_EINVAL && bytes > 0xFFFFFFFFull) return false;
         check(rc, "kfinger");
+        if (factText) {
+            rc = fpm_kfinger_fact_text(job, blob.data(), off.data(), nullptr, 0, &factBytes);
+            if (rc == FPM_EINVAL && factBytes > 0xFFFFFFFFull) return false;
+            check(rc, "kfinger");
+        }
+        openText();
+        if (factText) {
+            std::unique_ptr<char[]> text(new char[factBytes ? factBytes : 1]);
+            check(fpm_kfinger_fact_text(job, blob.data(), off.data(), text.get(), factBytes,
+                                        &factBytes),
+                  "kfinger");
+            if (fwrite(text.get(), 1, factBytes, factOut) != factBytes)
+                die("could not write " + factPath + ".");
+        }
         std::unique_ptr<char[]> text(new char[bytes ? bytes : 1]);
         check(fpm_kfinger_text(job, blob.data(), off.data(), text.get(), bytes, &bytes), "kfinger");
-        openText();
         if (fwrite(text.get(), 1, bytes, out) != bytes) die("could not write " + outPath + ".");
         return true;
     }
@@ -178,9 +220,14 @@ struct Generator {
         if (lo == hi || done()) return;
         fpm_kfinger *job = nullptr;
         uint64_t n = 0;
-        check(fpm_kfinger_stage(ctx, packed.data(), off.data() + lo, (uint32_t)(hi - lo), window,
-                                linesLeft, &job, &n),
-              "kfinger");
+        if (split)
+            check(fpm_kfinger_stage_split(ctx, packed.data(), off.data() + lo, (uint32_t)(hi - lo),
+                                          split, &job, &n),
+                  "kfinger");
+        else
+            check(fpm_kfinger_stage(ctx, packed.data(), off.data() + lo, (uint32_t)(hi - lo),
+                                    window, linesLeft, &job, &n),
+                  "kfinger");
         if (consume(job, n, std::vector<std::string>(ids.begin() + lo, ids.begin() + hi))) return;
         if (hi - lo == 1)
             die("the k-finger text of record " + ids[lo] + " reaches 2^32 bytes; one record is "
@@ -209,7 +256,7 @@ struct Generator {
             if (!ids.empty() && packed.size() + rd.seq.size() > budget) flush();
             packed += rd.seq;
             off.push_back(packed.size());
-            ids.push_back(lineId(rd.name, rd.comment));
+            ids.push_back(idOf(rd.name, rd.comment));
         }
         flush();
         return l == -1;
@@ -235,14 +282,19 @@ struct Generator {
                     std::string name, comment;
                     splitHeader(image.data() + parsed.headOff[r] + 1, parsed.headLen[r] - 1, name,
                                 comment);
-                    ids[r] = lineId(name, comment);
+                    ids[r] = idOf(name, comment);
                 }
                 if (found && !done()) {
                     fpm_kfinger *job = nullptr;
                     uint64_t n = 0;
-                    check(fpm_kfinger_stage_seq(ctx, parsed.text, take.data(), window, linesLeft, &job,
-                                                &n),
-                          "kfinger");
+                    if (split)
+                        check(fpm_kfinger_stage_split_seq(ctx, parsed.text, take.data(), split, &job,
+                                                          &n),
+                              "kfinger");
+                    else
+                        check(fpm_kfinger_stage_seq(ctx, parsed.text, take.data(), window, linesLeft,
+                                                    &job, &n),
+                              "kfinger");
                     ok = consume(job, n, ids);
                 }
                 if (ok) {
@@ -273,7 +325,12 @@ CommandKFinger::CommandKFinger()
                   "(gzipped or not), and \"-\" can be given to read from standard input. The lines "
                   "of all inputs are written to <prefix>.txt, the input of `sketch -fp`; with -S "
                   "they are sketched instead, into the <prefix>.msh that `sketch -fp` writes for "
-                  "that text.";
+                  "that text. With -L <N> the long-read fingerprints are made instead (lyn2vec "
+                  "--type generalized --split N): each record is cut into consecutive pieces of N "
+                  "bases, each piece is factorized on its own, and the record is one line, its "
+                  "ID, two spaces, then per piece the lengths and \" | \". With -f the factors "
+                  "themselves are also written, to <prefix>.fact.txt (lyn2vec --fact create): the "
+                  "same lines with each factor's bases in place of its length.";
     argumentString = "<input> [<input>] ...";
     useOption("help");
     addOption("window", Option(Option::Integer, "w", "Input",
@@ -282,12 +339,18 @@ CommandKFinger::CommandKFinger()
     addOption("factorization", Option(Option::String, "F", "Input",
         "Factorization of a window: CFL, ICFL, CFL_ICFL-<T>, CFL_COMB, ICFL_COMB or "
         "CFL_ICFL_COMB-<T>, T from 1 to the largest window size.", "CFL"));
+    addOption("long", Option(Option::String, "L", "Input",
+        "Long-read mode: cut each record into consecutive pieces of this many bases (1 to the "
+        "largest window size) and write one line per record. Not with -w or -S.", ""));
     addOption("prefix", Option(Option::File, "o", "Output",
         "Output prefix (first input file used if unspecified). The suffix '.txt' (or '.msh' with "
         "-S) will be appended.", ""));
     addOption("sketch", Option(Option::Boolean, "S", "Output",
         "Write the sketch of the k-finger lines (as `sketch -fp` of the text) instead of the "
         "text.", ""));
+    addOption("factors", Option(Option::Boolean, "f", "Output",
+        "Also write the factors themselves, one line per k-finger line, to <prefix>.fact.txt. "
+        "Not with -S.", ""));
     // the sketch options of `sketch -fp` (its -w, the k-mer size warning, does not apply to
     // fingerprints; its seed is -seed here, -S and -w being taken)
     for (const char *n : {"threads", "kmer", "noncanonical", "protein", "alphabet", "case",
@@ -325,10 +388,34 @@ int CommandKFinger::run() const
                   << "." << std::endl;
         return 1;
     }
+    g.sketch = options.at("sketch").active;
+    g.factText = options.at("factors").active;
+    if (options.at("long").active) {
+        // plain decimal digits, 1 .. the widest window
+        const std::string &v = options.at("long").argument;
+        const bool digits = !v.empty() && v.size() <= 9 &&
+                            v.find_first_not_of("0123456789") == std::string::npos;
+        const unsigned long n = digits ? strtoul(v.c_str(), nullptr, 10) : 0;
+        if (n < 1 || n > maxWindow()) {
+            std::cerr << "ERROR: Argument to -L must be an integer from 1 to " << maxWindow()
+                      << " (" << v << " given)." << std::endl;
+            return 1;
+        }
+        if (options.at("window").active) {
+            std::cerr << "ERROR: -L cuts records into pieces and takes no window: -w does not "
+                      << "apply with it." << std::endl;
+            return 1;
+        }
+        g.split = (uint32_t)n;
+    }
+    if (g.sketch && (g.split || g.factText)) {
+        std::cerr << "ERROR: -S sketches the k-finger lines of windows: it does not apply with "
+                  << (g.split ? "-L" : "-f") << "." << std::endl;
+        return 1;
+    }
     if (!checkInputArguments(arguments, 0, "input")) return 1;
     warmDevices();
     g.window = window;
-    g.sketch = options.at("sketch").active;
     g.seed = parameters.seed;
     g.use64 = parameters.use64;
     if (g.sketch) g.linesLeft = kLimitReadFingerprint;
@@ -338,6 +425,7 @@ int CommandKFinger::run() const
     const char *suffix = g.sketch ? suffixSketch : ".txt";
     if (!hasSuffix(prefix, suffix)) prefix += suffix;
     g.outPath = prefix;
+    if (g.factText) g.factPath = factPathOf(prefix);
     g.ctx = device();
     phaseMark("device context");
 
@@ -355,6 +443,12 @@ int CommandKFinger::run() const
         if (fclose(g.out) != 0) {
             g.out = nullptr;
             g.die("could not write " + g.outPath + ".");
+        }
+        g.out = nullptr;
+        if (g.factOut && fclose(g.factOut) != 0) {
+            g.factOut = nullptr;
+            remove(g.outPath.c_str());
+            g.die("could not write " + g.factPath + ".");
         }
         phaseMark("text write");
         return 0;

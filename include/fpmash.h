@@ -512,6 +512,32 @@ int fpm_kfinger_wide_groups(fpm_kfinger *job, uint32_t *groups);
  * widest window of fpm_kfinger_limits for plain FPM_KF_CFL, which has no working memory.  No
  * device needed; an unknown kind or comb > 1 is FPM_EINVAL. */
 int fpm_kfinger_lds_window(uint32_t kind, uint32_t comb, uint32_t *window);
+/* Long reads: lyn2vec --type generalized --split N (factors_string, fingerprint_utils.py:114-130;
+ * compute_long_fingerprint_by_list, :480-518).  A record of n > 0 bytes and a split N is cut
+ * into pieces: the whole record when n < N, else [0, N) [N, 2N) ... with a last piece of n mod N
+ * bytes where that is not 0.  Each piece is factorized on its own (no window, no cyclic wrap)
+ * under the job's factorization, by the byte rules above.  The job's unit, the "line" of every
+ * call above, is a piece: fpm_kfinger_set_factorization, _set_comb, _run, _fetch
+ * (rec_first_line[r]: record r's first piece), _device_output, _values and _wide_groups work
+ * per piece with no other change of meaning.  split runs from 1 to the widest window of
+ * fpm_kfinger_limits, else FPM_EINVAL; the working memory of a split leaves LDS where that of
+ * the same window does (fpm_kfinger_lds_window).  There is no max_lines.  Pieces share
+ * workgroups in packs of at most run_length pieces and run_length + widest window - 1 bytes
+ * (fpm_kfinger_limits), across records.
+ * fpm_kfinger_text of a split job writes one line per record with a piece, "<id>" + two spaces,
+ * then per piece its lengths joined by single spaces and " | ", then "\n"; ids holds the
+ * record's ID as it is to appear (lyn2vec's, without "_0").
+ * fpm_kfinger_fact_text (lyn2vec --fact create, :471-474 and :509-511), after run, for window
+ * and split jobs: the same lines with each factor's upper-cased bytes in place of its length; a
+ * window job's line is "<id> <factor> <factor> ...\n".  Sizing, errors and the 2^32 bound are
+ * those of fpm_kfinger_text. */
+int fpm_kfinger_stage_split(fpm_ctx *ctx, const char *seq, const uint64_t *rec_off,
+                            uint32_t n_rec, uint32_t split, fpm_kfinger **job,
+                            uint64_t *n_pieces);
+int fpm_kfinger_stage_split_seq(fpm_ctx *ctx, fpm_seqtext *seq, const uint8_t *take,
+                                uint32_t split, fpm_kfinger **job, uint64_t *n_pieces);
+int fpm_kfinger_fact_text(fpm_kfinger *job, const char *ids, const uint64_t *id_off, char *out,
+                          uint64_t cap, uint64_t *n_bytes);
 
 /* ---- dist ---------------------------------------------------------------------
  * Replaces compare()/compareSketches()/pValue() (CommandDistance.cpp:335-450) over
